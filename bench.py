@@ -1,18 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio samples/s, encode_audio + decode_audio, 1kbps @ 16 kHz, batch 256 x 1 s per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one batch of synthetic clips already resident in HBM.  With N > 1 every
 rank (one process per GPU) runs its own 256 clips (weak scaling, clips are independent) and the quantiser indices
 and waveforms are all-gathered over RCCL at the end of the step.  Rank 0 prints ONE JSON line.
 
-Besides the headline fields the line carries (N = 1, default flags):
+A plain run only sets up, warms up, times the K steps (`ms_per_step`, `value`) and prints the line.  `--dump-outputs DIR`
+writes what the last timed step returned (q_feature, indices, level_indices, waveform) as DIR/<name>.npy; inputs and weights
+are seeded, so two builds can be compared output for output.
+
+With --full the line also carries (N = 1; the per-kernel table and rooflines also at N > 1):
   roofline       the dominant kernel of the step against its own roofline (HIP-event durations measured in this run)
   cpu_baseline   the oracle timed on a bounded sample of the same workload on this box's host cores, plus
                  index_agreement: EVERY token of the headline batch compared with the oracle, on both GEMM routes
   configs        BASELINE.json configs 3 and 5 and the explicit-codebook argmin kernel, each with its own steps x ms
+  fsq_kernel, exact_f32_mfma_route, kernels, gemm_shapes: the quantiser's stand-alone HBM roofline, the step on the exact
+                 fp32 route, and the per-kernel HIP-event times of one extra profiled step
 """
 import argparse
 import hashlib
@@ -244,8 +250,13 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL all-gather of outputs (N > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (3kbps batch, streaming graph, argmin kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline figure: per-kernel roofline, "
+                         "quantiser HBM roofline, exact fp32 route, other configs, CPU baseline and index agreement with the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the `configs` object (3kbps batch, streaming graph, argmin kernel)")
     ap.add_argument("--cpu-batch", type=int, default=16)
     ap.add_argument("--cpu-threads", type=int, default=32,
                     help="host threads for the CPU baseline (32 measured fastest on the 256-thread GPU box; "
@@ -254,8 +265,8 @@ def main():
                     help="clips of the batch whose tokens are compared with the oracle (default: all of them)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph")
     ap.add_argument("--pipeline-only", action="store_true",
-                    help="skip the stand-alone FSQ launch, the exact-route reference steps, the configs object and the CPU baseline "
-                         "(profiling runs: keeps the kernel trace to the timed workload)")
+                    help="with --full: skip the stand-alone FSQ launch, the exact-route reference steps, the configs object and the CPU "
+                         "baseline, keeping the per-kernel table (profiling runs: keeps the kernel trace to the timed workload)")
     ap.add_argument("--gemm", choices=["split", "exact"], default="split",
                     help="split: large fp32 contractions as exact bf16x3 operand splits on the bf16 matrix cores (default); "
                          "exact: every product on the fp32 MFMA instruction")
@@ -336,7 +347,7 @@ def main():
             # step's kernels and overlap the NEXT step's encode; each step retires the previous step's pair.
             pending.push(gather_batch_async(ind["indices"], world * b, force=force_dist),
                          gather_batch_async(wave, world * b, force=force_dist))
-        return ind, wave
+        return q, ind, wave
 
     run = step
     if args.graph:
@@ -353,7 +364,7 @@ def main():
 
     # the quantiser's stand-alone HBM roofline (its own large-N launch) is taken first, on an idle chip: after the MFMA-heavy
     # pipeline the same launch measures ~10 % lower while the clocks recover
-    extras = rank == 0 and world == 1 and not args.pipeline_only and not dry
+    extras = args.full and rank == 0 and world == 1 and not args.pipeline_only and not dry
     fsq_line = fsq_microbench(codec, dev) if extras else None
     rccl_ranks = None
     if world > 1 or force_dist:  # proof that RCCL sees every rank: an all-reduce of ones
@@ -368,7 +379,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ind, wave = run()
+        q, ind, wave = run()
     pending.drain()  # the last step's gathers are part of the timed work
     sync()
     if world > 1:
@@ -388,8 +399,14 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = world * b * samples * args.steps / elapsed
         gflop_clip = algorithmic_gflop_per_clip_second(mc) * args.seconds
-        if dry:
-            kernels, shapes, total_ms, roof, runner_up = [], [], 0.0, None, None
+        if args.dump_outputs:
+            if gather:  # what every rank receives: the all-gathered tokens and waveforms of the last step
+                outs = dict(zip(("indices", "waveform"), pending.results))
+            else:
+                outs = {"q_feature": q, "indices": ind["indices"], "level_indices": ind["level_indices"], "waveform": wave}
+            dump_outputs(args.dump_outputs, outs)
+        if dry or not args.full:
+            kernels, shapes, total_ms, roof, runner_up = [], [], (0.0 if dry else None), None, None
         else:
             # ---- per-kernel roofline: one extra, untimed step with HIP events around every launch ----------
             with _capi.profile() as prof:
@@ -415,7 +432,7 @@ def main():
                            "(error vs fp64 <= the fp32 fmaf chain's, tests/test_gpu_blocks.py::test_gemm_split_accuracy); "
                            "all other products use v_mfma_f32_32x32x2_f32") if l3ac_amd.get_gemm_split() else
                           "fp32 everywhere: every product on v_mfma_f32_32x32x2_f32 (--gemm exact)",
-            "dry_run_cpu": dry,
+            "dry_run_cpu": dry, "full": args.full,
             "parity_note": "'indices bit-exact' is the BASELINE metric's wording; what is measured: the quantiser kernel is bit-exact "
                            "for identical inputs (reference known-answer vectors incl. exact rounding boundaries), and end to end "
                            "every token of this batch is compared with the CPU oracle in cpu_baseline.index_agreement (mismatch "
@@ -443,10 +460,10 @@ def main():
         if dry:
             out["collective_backend"] = "gloo"
         ind_exact = None
-        if args.gemm == "split" and world == 1 and not args.graph and not args.pipeline_only and not dry:
+        if args.full and args.gemm == "split" and world == 1 and not args.graph and not args.pipeline_only and not dry:
             # the same step with every product on the exact fp32 MFMA instruction, for reference (5 steps, untimed above)
             l3ac_amd.set_gemm_split(False)
-            dt, (ind_x, _) = time_steps(step, 5, 2, pending.drain)
+            dt, (_, ind_x, _) = time_steps(step, 5, 2, pending.drain)
             l3ac_amd.set_gemm_split(True)
             ind_exact = ind_x["indices"]
             out["exact_f32_mfma_route"] = {"ms_per_step": dt / 5 * 1e3, "value": b * samples * 5 / dt, "unit": "samples/s", "steps": 5,
@@ -454,7 +471,7 @@ def main():
         out["fsq_kernel"] = fsq_line
         if extras and not args.no_configs and not args.graph:
             out["configs"] = other_configs(dev, args)
-        if not args.no_cpu_baseline and not args.pipeline_only and world == 1 and not dry:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and not args.pipeline_only and world == 1 and not dry:  # rank 0 at N = 1 only
             routes = {"split" if l3ac_amd.get_gemm_split() else "exact": ind["indices"]}
             if ind_exact is not None:
                 routes["exact"] = ind_exact
@@ -474,6 +491,27 @@ def main():
         dist.barrier()
     if world > 1 or force_dist:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 63_000_000  # array data: the files stay under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, outs):
+    """Each output as out_dir/<name>.npy: integer tensors as float64 (exact), the others as float32.  If the whole batch would
+    exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of batch rows (sorted) is written for every output."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().to(torch.float32 if v.is_floating_point() else torch.float64) for k, v in outs.items()}
+    rows = min(a.shape[0] for a in arrays.values())
+    row_bytes = sum(a[0].numel() * a.element_size() for a in arrays.values())
+    keep = max(1, min(rows, DUMP_LIMIT_BYTES // max(row_bytes, 1)))
+    if keep < rows:
+        sel = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: a[sel] for k, a in arrays.items()}
+        print(f"bench.py: --dump-outputs keeps {keep} of {rows} batch rows (seeded sample, 64 MB limit)", file=sys.stderr)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", a.numpy())
 
 
 def summary_of(out):

@@ -346,6 +346,38 @@ def test_bench_rank_path_runs_at_world_2_on_cpu():
         assert r.returncode != 0
 
 
+def test_bench_plain_run_dumps_the_last_step_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, measures nothing else, and `--dump-outputs DIR` writes what the
+    last timed step returned as DIR/<name>.npy (float32, integer outputs as float64); two runs with the same arguments write the same
+    arrays (seeded inputs and weights).  Executed on the `--dry-run-cpu` path with the oracle stand-in codec."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "2"
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run-cpu",
+                            "--codec-factory", "tests.standin_codec:make_codec", "--batch", "4", "--seconds", "0.05",
+                            "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, env=env, timeout=600, cwd=str(REPO))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and line["ms_per_step"] > 0
+        assert abs(line["value"] - 4 * 800 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+        assert line["unit"] == "samples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["roofline"] is None and line["fsq_kernel"] is None and "cpu_baseline" not in line and "configs" not in line
+        dumps.append({f.stem: np.load(f) for f in (tmp_path / run).glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["indices", "level_indices", "q_feature", "waveform"]
+    assert a["indices"].shape == (4, 67) and a["indices"].dtype == np.float64 and (a["indices"] == np.round(a["indices"])).all()
+    assert a["waveform"].shape == (4, 804) and a["waveform"].dtype == np.float32 and a["q_feature"].dtype == np.float32
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_bench_rank_path_runs_at_world_8_at_config_4_shape():
     """BASELINE config 4 (2048 clips sharded over 8 ranks, outputs gathered) through bench.py's N-rank path with EIGHT real processes on
     CPU (gloo), 256 clips x 1 s per rank at the 1kbps geometry (tests/standin_codec.py::make_shape_codec: the real shapes, trivial

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Counter A/B of an environment switch on one box (separate --pmc passes, never combined with a trace):
 #   tools/pmc_ab.sh <outdir under gpurun_out> <VAR> <value> [<value> ...]
-# per value: bench.py --pipeline-only --steps 3 under an SQ pass and two cache passes; summarise with tools/pmc_ab_summary.py
+# per value: bench.py --full --pipeline-only --steps 3 under an SQ pass and two cache passes; summarise with tools/pmc_ab_summary.py
 # PROG="tools/hc_time.py 24480x2048x512" profiles that program (path relative to the repo) instead of bench.py
 OUT=$GRAFT_REPO_ROOT/$1; VAR=$2; shift 2
 mkdir -p $OUT
@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"
 SQ2="SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE"
-P="$R/bench.py --steps 3 --warmup 1 --pipeline-only $BENCH_ARGS"
+P="$R/bench.py --full --steps 3 --warmup 1 --pipeline-only $BENCH_ARGS"
 [ -n "$PROG" ] && P="$R/$PROG"
 for v in "$@"; do
     export $VAR=$v

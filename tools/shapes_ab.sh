@@ -4,7 +4,7 @@ out=$1; var=$2; shift 2
 mkdir -p "$(dirname "$out")"
 for round in 1 2; do
 for v in "$@"; do
-  env $var=$v timeout 200 python bench.py --pipeline-only --steps 20 --warmup 3 $BENCH_ARGS 2>/dev/null | python -c "
+  env $var=$v timeout 200 python bench.py --full --pipeline-only --steps 20 --warmup 3 $BENCH_ARGS 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$var=$v step', round(d['ms_per_step'],3))
