@@ -204,6 +204,25 @@ int l3ac_pack_indices(const int32_t* indices, int32_t batch, int32_t n_tok, int3
 int l3ac_unpack_indices(const uint32_t* packed, int32_t batch, int32_t n_tok, int32_t bits, int32_t words_per_clip,
                         int32_t* indices, void* stream);
 
+/* ---- sample-rate conversion (the reference resamples on the CPU before encoding: example.py, librosa.resample) ---------
+ * scipy.signal.resample_poly(x, up, down) with its defaults, for in_rate -> out_rate: g = gcd, up = out_rate / g,
+ * down = in_rate / g, half_len = 10 max(up, down), prototype firwin(2 half_len + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up
+ * (designed on the host in fp64, each tap rounded once to fp32), zero padding at both ends, n_out = ceil(n_in up / down).
+ * Supported: positive rates whose reduced max(up, down) <= 1024 (every standard rate from 8 to 192 kHz to and from 16 kHz);
+ * anything else returns L3AC_EINVAL before any device work.  Context-free, like l3ac_pack_indices.
+ *   l3ac_resample_length: n_out, or < 0 for unsupported rates / a negative n_in.
+ *   l3ac_resample_bank:   HOST only: the polyphase bank's length in floats (0 when in_rate == out_rate), or < 0 for unsupported
+ *                         rates; fills `bank` (host memory) when it is non-null and cap >= that length.  The caller copies it to
+ *                         the device once per rate pair.
+ *   l3ac_resample:        x [batch][x_stride] (first n_in samples of each row) -> y [batch][y_stride] (first n_out samples);
+ *                         `bank` is the DEVICE copy of l3ac_resample_bank's output (unused when in_rate == out_rate: a copy).
+ *                         fp32 fmaf chain per output in a fixed tap order: the bits of a clip do not depend on the batch, its
+ *                         position in it, the strides or the launch geometry.  Enqueue only; capturable into a hipGraph. */
+int64_t l3ac_resample_length(int32_t in_rate, int32_t out_rate, int64_t n_in);
+int64_t l3ac_resample_bank(int32_t in_rate, int32_t out_rate, float* bank, int64_t cap);
+int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
+                  const float* bank, float* y, int64_t y_stride, void* stream);
+
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */

@@ -10,6 +10,13 @@ Drop-in for the reference package on this path (``import l3ac_amd as l3ac``):
     audio = codec.decode_audio(q_feature)                   reference l3ac/__init__.py:116-121
     audio = codec.decode_audio(indices=indices["indices"])
 
+Audio at another rate (44.1 kHz, 48 kHz, ...) is converted on the GPU, where the reference resamples on the CPU first
+(its example.py: librosa.resample):
+
+    y16 = l3ac.resample(audio, 48000, codec.config.sample_rate)      scipy.signal.resample_poly's defaults, HIP kernel
+    q_feature, indices = codec.encode_audio(audio, sample_rate=48000)    == encode_audio(resample(audio, 48000, 16000))
+    audio = codec.decode_audio(q_feature, sample_rate=44100)             == resample(decode_audio(q_feature), 16000, 44100)
+
 All arithmetic runs in hand-written HIP kernels inside libl3ac_hip.so (include/l3ac_hip.h) on gfx950; torch
 supplies device memory and streams only.  There is no CPU path: calling encode/decode with CPU tensors, or
 without the built extension, raises.
@@ -31,7 +38,7 @@ from .chunking import ChunkData, plan as _chunk_plan
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
-           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData"]
+           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -224,10 +231,19 @@ class L3AC:
                 "clip were not co-resident: another process or a CU mask on the device?); this call's outputs are invalid. The "
                 "context now runs the one-workgroup form (same bits): repeat the call")
 
+    def _rate(self, sample_rate) -> Optional[int]:
+        """None when `sample_rate` is absent or the codec's own rate (the plain path runs), else the validated rate."""
+        if sample_rate is None or int(sample_rate) == self.config.sample_rate:
+            return None
+        resample_length(int(sample_rate), self.config.sample_rate, 1)  # unsupported rates raise before any device work
+        return int(sample_rate)
+
     @torch.no_grad()
-    def encode_audio(self, audio_data: torch.Tensor, validate: bool = False):
+    def encode_audio(self, audio_data: torch.Tensor, validate: bool = False, sample_rate: Optional[int] = None):
         """audio (B, T) fp32 -> (q_feature (B, T_tok, C) fp32, {"indices": int32 (B, T_tok),
         "level_indices": fp32 (B, T_tok, D)}); the zero right-padding to a hop multiple happens in-kernel.
+        ``sample_rate``: the rate of ``audio_data`` when it is not ``config.sample_rate``: the audio is first converted on the GPU,
+        exactly as ``resample(audio_data, sample_rate, config.sample_rate)`` (T_tok then counts the converted samples).
         ``validate=True`` synchronises before and after the call: it raises — without running anything — if an EARLIER, unvalidated
         call on the context lost a cooperative transformer launch to its time limit, and raises if a launch of THIS call did.  Without
         it a later call on the context returns L3AC_ECOOP once, after the fact and possibly several calls late (the entry check does
@@ -235,6 +251,9 @@ class L3AC:
         ctx = self._check_input(audio_data, "audio_data")
         if audio_data.dim() != 2:
             raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
+        rate = self._rate(sample_rate)
+        if rate is not None:
+            audio_data = resample(audio_data, rate, self.config.sample_rate)
         audio = audio_data.to(torch.float32)
         if audio.stride(-1) != 1 or audio.stride(0) % 4 != 0 or audio.data_ptr() % 16 != 0:
             audio = audio.contiguous()
@@ -258,8 +277,11 @@ class L3AC:
         return q_feature, {"indices": indices, "level_indices": level_indices}
 
     @torch.no_grad()
-    def decode_audio(self, audio_feature: torch.Tensor = None, indices: torch.Tensor = None, validate: bool = False) -> torch.Tensor:
+    def decode_audio(self, audio_feature: torch.Tensor = None, indices: torch.Tensor = None, validate: bool = False,
+                     sample_rate: Optional[int] = None) -> torch.Tensor:
         """(B, T_tok, C) features, or int indices (B, T_tok) -> audio (B, T_tok * hop), not trimmed.
+        ``sample_rate``: return the audio at this rate instead, exactly ``resample(decode_audio(...), config.sample_rate,
+        sample_rate)``: (B, resample_length(config.sample_rate, sample_rate, T_tok * hop)), not trimmed either.
         Indices outside [0, codebook_size) — a corrupted or truncated token stream — are clamped into range and counted on
         the device (``codec.network.context().bad_index_count()``); with ``validate=True`` the call synchronises and raises
         if this call met any — or if a cooperative transformer launch of this call timed out (as encode_audio)."""
@@ -267,6 +289,7 @@ class L3AC:
         if src is None:
             raise ValueError("decode_audio needs audio_feature or indices")
         ctx = self._check_input(src, "decode input")
+        rate = self._rate(sample_rate)
         mc = self.network.mc
         if audio_feature is not None:
             if audio_feature.dim() != 3 or audio_feature.shape[-1] != mc.feature_dim:
@@ -297,7 +320,7 @@ class L3AC:
                 if bad:
                     raise ValueError(f"{bad} of {b * n_tok} indices lie outside [0, {mc.codebook_size}): corrupted token stream")
         del keep
-        return audio
+        return audio if rate is None else resample(audio, self.config.sample_rate, rate)
 
 
     # ---- long audio (reference l3ac/codec.py:124-156, corrected: see l3ac_amd/chunking.py) ---------------------------
@@ -429,6 +452,68 @@ def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int) -> torch.Tensor:
         _capi.check(lib.l3ac_unpack_indices(src.data_ptr(), packed.shape[0], n_tok, bits, words, out.data_ptr(),
                                             torch.cuda.current_stream(packed.device).cuda_stream))
     return out
+
+
+def resample_length(orig_sr: int, target_sr: int, n_in: int) -> int:
+    """Samples out of ``resample`` for ``n_in`` samples in: ceil(n_in * up / down).  Raises ValueError for rates the library does
+    not support (non-positive, or a reduced max(up, down) above 1024)."""
+    n = _capi.load_library().l3ac_resample_length(int(orig_sr), int(target_sr), int(n_in))
+    if n < 0:
+        raise ValueError(_capi.load_library().l3ac_last_error().decode())
+    return int(n)
+
+
+_banks = {}  # (device, orig_sr, target_sr) -> device copy of the library's polyphase filter bank
+
+
+def _resample_bank(device: torch.device, orig_sr: int, target_sr: int) -> Optional[torch.Tensor]:
+    key = (device, orig_sr, target_sr)
+    if key in _banks:
+        return _banks[key]
+    lib = _capi.load_library()
+    n = lib.l3ac_resample_bank(orig_sr, target_sr, None, 0)
+    if n < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    if n > 0 and torch.cuda.is_current_stream_capturing():
+        # uploading the bank would be a host -> device copy inside the graph; the eager warm-up call before capture fills the cache
+        raise RuntimeError(f"resample {orig_sr} -> {target_sr}: this rate pair's filter bank is not on {device} yet; run the call "
+                           "once outside stream capture (the warm-up call before graph capture) to upload it")
+    bank = None
+    if n > 0:
+        host = torch.empty(n, dtype=torch.float32)
+        lib.l3ac_resample_bank(orig_sr, target_sr, host.data_ptr(), n)
+        bank = host.to(device)
+    _banks[key] = bank
+    return bank
+
+
+@torch.no_grad()
+def resample(audio: torch.Tensor, orig_sr: int, target_sr: int) -> torch.Tensor:
+    """(B, T) fp32 CUDA audio at ``orig_sr`` -> (B, resample_length(orig_sr, target_sr, T)) at ``target_sr``, on the GPU.
+    ``scipy.signal.resample_poly(audio, up, down, axis=-1)`` with its defaults (Kaiser-windowed sinc, beta 5, zero padding at
+    both ends; up / down = target_sr / orig_sr reduced), in fp32: each output is one fmaf chain in a fixed tap order, so a clip's
+    bits do not depend on the batch it is in.  Equal rates return a copy.  No CPU path: CPU tensors raise.  Each rate pair's
+    filter bank is uploaded once per device and cached; under stream capture a pair that has not run on the device yet raises."""
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if not isinstance(audio, torch.Tensor) or not audio.is_cuda:
+        raise RuntimeError("resample needs a CUDA tensor: l3ac_amd has no CPU path")
+    if audio.dim() != 2:
+        raise ValueError(f"audio must be (batch, samples), got {tuple(audio.shape)}")
+    b, t = audio.shape
+    if b == 0 or t == 0:
+        raise ValueError("empty audio")
+    n_out = resample_length(orig_sr, target_sr, t)  # validates the rates before any device work
+    x = audio.to(torch.float32)
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    dev = x.device
+    bank = _resample_bank(dev, orig_sr, target_sr)
+    y = torch.empty((b, n_out), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.load_library().l3ac_resample(
+            x.data_ptr(), b, t, x.stride(0) if b > 1 else t, orig_sr, target_sr, None if bank is None else bank.data_ptr(),
+            y.data_ptr(), n_out, torch.cuda.current_stream(dev).cuda_stream))
+    return y
 
 
 def get_model(config_name, model_dir=None, synthetic_seed: Optional[int] = None, synthetic_profile: str = "mild") -> L3AC:

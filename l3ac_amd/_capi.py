@@ -92,6 +92,9 @@ SIGNATURES = {
     "l3ac_gemm_split_f32": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I32, _I32, _P]),
     "l3ac_pack_indices": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P]),
     "l3ac_unpack_indices": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "l3ac_resample_length": (_I64, [_I32, _I32, _I64]),
+    "l3ac_resample_bank": (_I64, [_I32, _I32, _P, _I64]),
+    "l3ac_resample": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

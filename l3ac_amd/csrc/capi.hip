@@ -525,6 +525,26 @@ int l3ac_unpack_indices(const uint32_t* packed, int32_t batch, int32_t n_tok, in
     return launch_unpack_indices((hipStream_t)stream, packed, batch, n_tok, bits, words_per_clip, indices);
 }
 
+int64_t l3ac_resample_length(int32_t in_rate, int32_t out_rate, int64_t n_in) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    L3AC_REQUIRE(n_in >= 0 && n_in <= (INT64_MAX / 1024), "resample: bad input length %lld", (long long)n_in);
+    return resample_length(p, n_in);
+}
+
+int64_t l3ac_resample_bank(int32_t in_rate, int32_t out_rate, float* bank, int64_t cap) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    const int64_t need = resample_bank_floats(p);
+    if (bank && need > 0 && cap >= need) resample_fill_bank(p, bank);
+    return need;
+}
+
+int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
+                  const float* bank, float* y, int64_t y_stride, void* stream) {
+    return launch_resample((hipStream_t)stream, x, batch, n_in, x_stride, in_rate, out_rate, bank, y, y_stride);
+}
+
 int l3ac_profile_begin(void) {
     L3AC_REQUIRE(g_profiler == nullptr, "profile already active on this thread");
     g_profiler = new (std::nothrow) Profiler();

@@ -164,6 +164,18 @@ int launch_fsq_copy_ceiling(hipStream_t s, const float* x, int64_t n, float* q, 
 // token bit stream (kernels/bitpack.hip)
 int launch_pack_indices(hipStream_t s, const int32_t* idx, int batch, int n_tok, int bits, uint32_t* out, int words_per_clip);
 int launch_unpack_indices(hipStream_t s, const uint32_t* in, int batch, int n_tok, int bits, int words_per_clip, int32_t* idx);
+// polyphase sample-rate conversion, scipy.signal.resample_poly's defaults (kernels/resample.hip)
+struct ResamplePlan {
+    int up, down;   // out_rate / gcd, in_rate / gcd
+    int half_len;   // 10 max(up, down)
+    int K, KE;      // taps per output; bank row length (even, >= K + 1)
+};
+int resample_plan(int32_t in_rate, int32_t out_rate, ResamplePlan* p);  // L3AC_EINVAL (message set) on unsupported rates
+int64_t resample_length(const ResamplePlan& p, int64_t n_in);
+int64_t resample_bank_floats(const ResamplePlan& p);                     // 0 when up == down (a copy needs no filter)
+void resample_fill_bank(const ResamplePlan& p, float* bank);             // host: [up][2][KE] fp32, each tap rounded once from fp64
+int launch_resample(hipStream_t s, const float* x, int batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
+                    const float* bank, float* y, int64_t y_stride);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)
