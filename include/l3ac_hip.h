@@ -242,6 +242,11 @@ int l3ac_op_up_layer(l3ac_ctx* ctx, const char* block, const float* x, int32_t b
 int l3ac_op_enhance_up(l3ac_ctx* ctx, const char* enhance_block, const char* up_block, const float* x, int32_t batch,
                        int32_t frames, float* y, void* stream);
 int l3ac_op_last_block(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t frames, float* audio, void* stream);
+/* The output stage's parts as l3ac_op_last_block runs them: LegacyUnit `unit` (0, 1, 2 = dilation 1, 3, 9: modules.py order),
+ * x -> y [batch][frames][c] (x must not alias y); the head, x [batch][frames][c] -> audio [batch][frames] (honours
+ * l3ac_ctx_set_head_pretanh).  l3ac_op_last_block(x) = op_head(op_legacy_unit(2, op_legacy_unit(1, op_legacy_unit(0, x)))). */
+int l3ac_op_legacy_unit(l3ac_ctx* ctx, int32_t unit, const float* x, int32_t batch, int32_t frames, float* y, void* stream);
+int l3ac_op_head(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t frames, float* audio, void* stream);
 int l3ac_op_local_trans(l3ac_ctx* ctx, const char* block, const float* x, int32_t batch, int32_t frames, float* y,
                         void* stream);
 /* whole sub-modules */

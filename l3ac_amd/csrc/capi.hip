@@ -449,6 +449,25 @@ int l3ac_op_last_block(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t fra
     return run_last_block(ctx, s, ctx->ws.x0, audio, batch, frames);
 }
 
+int l3ac_op_legacy_unit(l3ac_ctx* ctx, int32_t unit, const float* x, int32_t batch, int32_t frames, float* y, void* stream) {
+    L3AC_ENTER_WS(ctx, stream);
+    L3AC_REQUIRE(unit >= 0 && unit < (int)ctx->legacy.size(), "op_legacy_unit: unit %d of %d", unit, (int)ctx->legacy.size());
+    L3AC_REQUIRE(batch > 0 && frames > 0, "op_legacy_unit: bad shape %d x %d", batch, frames);
+    // (the fused kernel cannot run in place: in-place calls are refused instead of silently taking another form)
+    L3AC_REQUIRE(x != y, "op_legacy_unit: x and y must not alias");
+    const LegacyW& l = ctx->legacy[unit];
+    L3AC_OP_SCRATCH(l.c);
+    return run_legacy_unit(ctx, (hipStream_t)stream, l, x, y, batch, frames);
+}
+
+int l3ac_op_head(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t frames, float* audio, void* stream) {
+    L3AC_ENTER_WS(ctx, stream);
+    L3AC_REQUIRE(batch > 0 && frames > 0, "op_head: bad shape %d x %d", batch, frames);
+    const int c = ctx->head.c;
+    L3AC_OP_SCRATCH(c);
+    return run_head(ctx, (hipStream_t)stream, x, audio, batch, frames);
+}
+
 int l3ac_op_local_trans(l3ac_ctx* ctx, const char* block, const float* x, int32_t batch, int32_t frames, float* y,
                         void* stream) {
     L3AC_ENTER_WS(ctx, stream);

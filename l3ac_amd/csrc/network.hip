@@ -819,37 +819,53 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     return launch_rows(s, r);
 }
 
-int run_last_block(l3ac_ctx* ctx, hipStream_t s, float* x, float* audio, int batch, int frames) {
-    Workspace& ws = ctx->ws;
-    const int64_t rows = (int64_t)batch * frames;
+// The output stage's form depends on the head's width and the largest dilation only: fused kernels (bf16x3 or exact fp32 by the
+// context's route) for every unit and the head, or snake + implicit GEMM + GEMM and snake + head kernel.
+static bool last_block_fused(const l3ac_ctx* ctx) {
     int max_dil = 1;
     for (const LegacyW& l : ctx->legacy) max_dil = l.dil > max_dil ? l.dil : max_dil;
-    if (last_block_fused_supported(ctx->head.c, max_dil)) {  // fused units ping-pong between x and the scratch buffer
-        float* cur = x;
-        float* alt = ws.a;
-        for (const LegacyW& l : ctx->legacy) {
-            L3AC_TRY(launch_legacy_unit_fused(s, l, cur, alt, batch, frames, ctx->gemm_split, ctx->unit_counter == 1 || ctx->unit_counter == 3 ? ctx->wide_counters + 4 : nullptr));
-            float* t = cur;
-            cur = alt;
-            alt = t;
-        }
-        return launch_head_fused(s, ctx->head, cur, batch, frames, audio, ctx->head_pretanh);
+    return last_block_fused_supported(ctx->head.c, max_dil);
+}
+
+// One LegacyUnit (modules.py:47-64), x -> y.  The fused kernel reads x while it writes y (x != y); the unfused form may run in
+// place; only the unfused form uses ws.a / ws.h.
+int run_legacy_unit(l3ac_ctx* ctx, hipStream_t s, const LegacyW& l, const float* x, float* y, int batch, int frames) {
+    if (last_block_fused(ctx))
+        return launch_legacy_unit_fused(s, l, x, y, batch, frames, ctx->gemm_split, ctx->unit_counter == 1 || ctx->unit_counter == 3 ? ctx->wide_counters + 4 : nullptr);
+    Workspace& ws = ctx->ws;
+    const int64_t rows = (int64_t)batch * frames;
+    L3AC_TRY(launch_snake(s, x, ws.a, rows, l.c, l.a0, l.ia0));
+    GemmArgs g{};
+    g.a = ws.a; g.lda = l.c; g.taps = 7; g.dil = l.dil; g.cin = l.c; g.frames = frames;
+    g.w = l.w1; g.w_img = ctx->img(l.w1); g.ldw = 7 * l.c; g.c = ws.h; g.ldc = l.c; g.m = rows; g.n = l.c; g.k = 7 * l.c;
+    g.bias = l.b1; g.epi = EPI_SNAKE; g.alpha = l.a1; g.inv_alpha = l.ia1;
+    L3AC_TRY(launch_gemm(s, g));
+    GemmArgs g2{};
+    g2.a = ws.h; g2.lda = l.c; g2.w = l.w2; g2.w_img = ctx->img(l.w2); g2.ldw = l.c; g2.c = y; g2.ldc = l.c; g2.m = rows; g2.n = l.c; g2.k = l.c;
+    g2.bias = l.b2; g2.epi = EPI_BIAS_RES; g2.res = x; g2.ldres = l.c;
+    return launch_gemm(s, g2);
+}
+
+// Snake1d -> Conv1d(c -> 1, k7) -> Tanh (modules.py:192-194); tanh is left out while the context's head_pretanh switch is on.
+// x is only read; the unfused form uses ws.a.
+int run_head(l3ac_ctx* ctx, hipStream_t s, const float* x, float* audio, int batch, int frames) {
+    const HeadW& hd = ctx->head;
+    if (last_block_fused(ctx)) return launch_head_fused(s, hd, x, batch, frames, audio, ctx->head_pretanh);
+    L3AC_TRY(launch_snake(s, x, ctx->ws.a, (int64_t)batch * frames, hd.c, hd.alpha, hd.inv_alpha));
+    return launch_head(s, ctx->ws.a, batch, frames, hd.c, hd.w, hd.b, audio, ctx->head_pretanh);
+}
+
+int run_last_block(l3ac_ctx* ctx, hipStream_t s, float* x, float* audio, int batch, int frames) {
+    // fused units ping-pong between x and the scratch buffer; unfused ones run in place (they use the scratch buffer themselves)
+    float* cur = x;
+    float* alt = last_block_fused(ctx) ? ctx->ws.a : x;
+    for (const LegacyW& l : ctx->legacy) {
+        L3AC_TRY(run_legacy_unit(ctx, s, l, cur, alt, batch, frames));
+        float* t = cur;
+        cur = alt;
+        alt = t;
     }
-    for (const LegacyW& l : ctx->legacy) {  // modules.py:47-64
-        L3AC_TRY(launch_snake(s, x, ws.a, rows, l.c, l.a0, l.ia0));
-        GemmArgs g{};
-        g.a = ws.a; g.lda = l.c; g.taps = 7; g.dil = l.dil; g.cin = l.c; g.frames = frames;
-        g.w = l.w1; g.w_img = ctx->img(l.w1); g.ldw = 7 * l.c; g.c = ws.h; g.ldc = l.c; g.m = rows; g.n = l.c; g.k = 7 * l.c;
-        g.bias = l.b1; g.epi = EPI_SNAKE; g.alpha = l.a1; g.inv_alpha = l.ia1;
-        L3AC_TRY(launch_gemm(s, g));
-        GemmArgs g2{};
-        g2.a = ws.h; g2.lda = l.c; g2.w = l.w2; g2.w_img = ctx->img(l.w2); g2.ldw = l.c; g2.c = x; g2.ldc = l.c; g2.m = rows; g2.n = l.c; g2.k = l.c;
-        g2.bias = l.b2; g2.epi = EPI_BIAS_RES; g2.res = x; g2.ldres = l.c;
-        L3AC_TRY(launch_gemm(s, g2));
-    }
-    const HeadW& hd = ctx->head;  // Snake1d -> Conv1d(c -> 1, k7) -> Tanh (modules.py:192-194)
-    L3AC_TRY(launch_snake(s, x, ws.a, rows, hd.c, hd.alpha, hd.inv_alpha));
-    return launch_head(s, ws.a, batch, frames, hd.c, hd.w, hd.b, audio, ctx->head_pretanh);
+    return run_head(ctx, s, cur, audio, batch, frames);
 }
 
 // the fused stack kernel computes on the bf16 matrix cores only (bf16x3): it belongs to the split route

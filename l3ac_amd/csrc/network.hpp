@@ -227,6 +227,8 @@ int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, flo
 int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tmp, float* y, int batch, int frames);
 int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, float* x, float* tmp, float* y, int batch, int frames);
 int run_last_block(l3ac_ctx* ctx, hipStream_t s, float* x, float* audio, int batch, int frames);  // x is clobbered
+int run_legacy_unit(l3ac_ctx* ctx, hipStream_t s, const LegacyW& l, const float* x, float* y, int batch, int frames);  // fused form: x != y
+int run_head(l3ac_ctx* ctx, hipStream_t s, const float* x, float* audio, int batch, int frames);
 int run_local_trans(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames);  // in place
 
 // sub-modules; `cur`/`alt` are the ping-pong activation buffers, on return *cur holds the result

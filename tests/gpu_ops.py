@@ -45,6 +45,20 @@ def op_plain(ctx, fn_name, x, d1, d2, out_shape, out_dtype=torch.float32):
     return y
 
 
+def legacy_unit(ctx, unit, x_btc, out=None):
+    """l3ac_op_legacy_unit: LegacyUnit `unit` (0, 1, 2 = dilation 1, 3, 9) on x [B][T][C] -> [B][T][C]."""
+    y = torch.empty_like(x_btc) if out is None else out
+    b, frames = x_btc.shape[0], x_btc.shape[1]
+    _capi.check(ctx.lib.l3ac_op_legacy_unit(ctx.handle, unit, x_btc.data_ptr(), b, frames, y.data_ptr(), _stream(x_btc.device)))
+    torch.cuda.synchronize()
+    return y
+
+
+def head(ctx, x_btc):
+    """l3ac_op_head: snake -> Conv1d(C -> 1, k7) -> tanh (unless the context's head_pretanh is on), x [B][T][C] -> [B][T]."""
+    return op_plain(ctx, "l3ac_op_head", x_btc, x_btc.shape[0], x_btc.shape[1], (x_btc.shape[0], x_btc.shape[1]))
+
+
 def fsq_forward(x, levels, w_in, b_in, w_out, b_out, latents_in=None, want_latents=False):
     lib = _capi.load_library()
     dev = w_out.device
