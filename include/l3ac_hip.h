@@ -291,49 +291,59 @@ int l3ac_gemm_f32(const float* a, int64_t lda, const float* w, const float* bias
  * product is the six plane products of order <= 2, accumulated in fp32: error vs fp64 no larger than the fp32 fmaf
  * chain's (tests/test_gpu_blocks.py::test_gemm_split_accuracy), at 2.67x fewer matrix-core cycles.  The network's large
  * channel contractions use it by default.  The route is a property of the CONTEXT: l3ac_ctx_set_gemm_split(ctx, 0)
- * routes every later product of that context through the exact v_mfma_f32_32x32x2_f32 kernel instead (a context starts on
- * the split route unless L3AC_GEMM_SPLIT=0 is in the environment when it is created); other contexts, and graphs already
- * captured from this one, are not affected.
+ * routes every later product of that context through the exact v_mfma_f32_32x32x2_f32 kernel instead (option "gemm_split"
+ * below: a context starts on the split route unless L3AC_GEMM_SPLIT=0 is in the environment when it is created); other contexts,
+ * and graphs already captured from this one, are not affected.
  * (reference counterpart: none — torch.nn.functional.linear / conv1d on fp32 tensors.) */
 /* The split itself, on the HOST (no GPU needed; this is what builds the weight images): planes [3][n] bf16 bit patterns with
  * x[i] == bf16(planes[0][i]) + bf16(planes[1][i]) + bf16(planes[2][i]) exactly for every finite fp32 x[i]
  * (tests/test_host.py::test_bf16x3_split_is_exact). */
 void l3ac_split3_host(const float* x, int64_t n, uint16_t* planes);
 int l3ac_ctx_set_gemm_split(l3ac_ctx* ctx, int32_t enable);
-/* Route options of ONE context by name (same rules as the setters above): "gemm_split", "head_pretanh", and "narrow_ring" — which
+/* Route options of ONE context by name.  Every option has a default; where an environment variable is named, its value (read with
+ * atoi when the context is CREATED) replaces the default.  Both the environment and l3ac_ctx_set_option go through one rule: a 0/1
+ * switch takes value != 0, any other option is clamped into its range; a retired value is refused with L3AC_EINVAL.
+ * "gemm_split" (default 1, L3AC_GEMM_SPLIT) and "head_pretanh" (default 0): the setters above.  "narrow_ring" (0..2) — which
  * fused kernel takes the ConvUnits with C <= 48 on the split route: 0 = conv_unit_split_kernel (32 frames per wave) everywhere,
  * 1 (default) = conv_unit_ring_kernel (16 frames per wave, weights resident in / streamed through LDS) at the width where it is the
  * faster one (C = 48), 2 = wherever it exists (C = 24 too).  Both evaluate the same operations; their results agree to rounding.
- * "trans_coop" (default 1): batches of at most 32 clips — a streaming chunk is one — run every LocalTrans stack in the cooperative
- * form of trans_stack_kernel (six co-resident workgroups per clip exchanging partial tiles through global memory); 0 keeps one
+ * "trans_coop" (default 1, L3AC_TRANS_COOP): batches of at most 32 clips — a streaming chunk is one — run every LocalTrans stack in the
+ * cooperative form of trans_stack_kernel (six co-resident workgroups per clip exchanging partial tiles through global memory); 0 keeps one
  * workgroup per clip.  Both forms return the same bits.  The cooperative form's six workgroups per clip wait for each other: they need
  * six CUs per clip (claimed per context in a process-wide registry; a launch that does not fit runs in the one-workgroup form);
- * failure reporting: l3ac_coop_timeout_count above.  "coop_timeout_ms" (default 250): the time limit of an arrival poll.
+ * failure reporting: l3ac_coop_timeout_count above.  "coop_timeout_ms" (default 250, 1..20000): the time limit of an arrival poll.
  * "coop_release_claim" (any value): returns the CUs this context has claimed for cooperative launches to the per-device registry (a claim
  * otherwise only grows until the context is destroyed); not while a graph captured from the context may still replay a cooperative launch.
  * "coop_test_fault" (test hook, default 0): j + 1 makes workgroup j of every clip withhold its first arrival.
- * "down_fused" (default 2): the encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm) in one kernel instead of an
- * fp32-MFMA GEMM + row kernel.  2: down_exact_kernel — the arithmetic of those two kernels bit for bit, on both GEMM routes; 1: the bf16x3
- * form of round 4 — faster, equally accurate, a DIFFERENT rounding of those layers (one token of the stress weights changes sides); 0: the
- * two kernels.
- * "wide_sliced" (default 1): the wide ConvUnits (C = 96 .. 256) of few frames — up to 256 tiles of 16, a streaming chunk — as two
+ * "down_fused" (default 2, L3AC_DOWN_FUSED, 0..2): the encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm) in one
+ * kernel instead of an fp32-MFMA GEMM + row kernel.  2: down_exact_kernel — the arithmetic of those two kernels bit for bit, on both GEMM
+ * routes; 0: the two kernels.  1 was retired and is refused.
+ * "gemm_w256" (default 1, L3AC_GEMM_W256, 0..2): which bf16x3 batch products take the 256-column kernel gemm_split_kernel_w256: 0 none,
+ * 1 the long-K light-epilogue ones, 2 every eligible shape.  The same bits either way.
+ * "unit_chunk_mb" (default 192, L3AC_UNIT_CHUNK_MB, 0..65536): the C = 512 ConvUnits (GEMM form) run over groups of clips whose hidden
+ * tensor is about this many MB (0: the whole batch at once).  The same bits either way.
+ * "wide_sliced" (default 1, 0..2): the wide ConvUnits (C = 96 .. 256) of few frames — up to 256 tiles of 16, a streaming chunk — as two
  * launches over frame tiles x channel slices instead of the fused kernel whose waves own their frames end to end; 0 never, 2 wherever
  * the form exists.  The same bits either way.
- * "unit_counter" (default 1; its initial value can be set with the environment variable L3AC_UNIT_COUNTER): batch kernels that keep two
- * workgroups per CU resident (the C = 96 ConvUnits, the LegacyUnits) hand their units of work out by a device counter instead of equal
- * static shares (the workgroup dispatched first is served first by every SIMD and would finish its share early); 0: static shares;
- * 2 / 3 (measurement): only the ConvUnits / only the LegacyUnits.  Which workgroup computes a tile does not enter its arithmetic: the
- * same bits either way.
- * Unknown names return L3AC_EINVAL. */
+ * "unit_counter" (default 1, L3AC_UNIT_COUNTER, 0..3): batch kernels that keep two workgroups per CU resident (the C = 96 ConvUnits,
+ * the LegacyUnits) hand their units of work out by a device counter instead of equal static shares (the workgroup dispatched first is
+ * served first by every SIMD and would finish its share early); 0: static shares; 2 / 3 (measurement): only the ConvUnits / only the
+ * LegacyUnits.  Which workgroup computes a tile does not enter its arithmetic: the same bits either way.
+ * Unknown names return L3AC_EINVAL.  l3ac_ctx_get_option writes the value an option holds now (all but coop_release_claim and
+ * coop_test_fault). */
 int l3ac_ctx_set_option(l3ac_ctx* ctx, const char* name, int32_t value);
+int l3ac_ctx_get_option(const l3ac_ctx* ctx, const char* name, int32_t* out);
 int32_t l3ac_ctx_get_gemm_split(const l3ac_ctx* ctx);
 /* Weight image for l3ac_gemm_split_f32: w [n][k] fp32 -> `image` (device, l3ac_gemm_split_image_bytes(n, k) bytes;
  * 0 = shape not eligible: needs n >= 192, k >= 32, k % 8 == 0). */
 int64_t l3ac_gemm_split_image_bytes(int32_t n, int32_t k);
 int l3ac_gemm_split_image(const float* w, int32_t n, int32_t k, void* image, void* stream);
-/* c[m][n] = a[m][:] . w[n][:] + bias[n] with w given as its split image (a [m][k] fp32, row stride lda). */
+/* c[m][n] = a[m][:] . w[n][:] + bias[n] with w given as its split image (a [m][k] fp32, row stride lda); the 256-column kernel takes
+ * the products option "gemm_w256" of a new context would send there.  _at: that choice given as w256 (0..2; test entry). */
 int l3ac_gemm_split_f32(const float* a, int64_t lda, const void* image, const float* bias, float* c, int64_t ldc,
                         int64_t m, int32_t n, int32_t k, void* stream);
+int l3ac_gemm_split_f32_at(const float* a, int64_t lda, const void* image, const float* bias, float* c, int64_t ldc,
+                           int64_t m, int32_t n, int32_t k, int32_t w256, void* stream);
 
 #ifdef __cplusplus
 }

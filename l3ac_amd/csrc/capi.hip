@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -149,6 +150,60 @@ auto lookup(const Map& m, const char* name, const char* kind) -> decltype(m.begi
     return it->second;
 }
 
+// ---- context options --------------------------------------------------------------------------------
+// Every switch of a context, by name.  l3ac_create starts each at its default, or at the value of its environment variable where
+// it has one and that is set; l3ac_ctx_set_option changes it later.  Both go through set_checked: a flag stores value != 0, any
+// other option is clamped into [lo, hi].
+struct Option {
+    const char* name;
+    int& (*field)(l3ac_ctx&);
+    bool flag;
+    int lo, hi, def;
+    const char* env;  // sets the initial value (null: none)
+};
+#define L3AC_FIELD(member) [](l3ac_ctx& c) -> int& { return c.member; }
+const Option kOptions[] = {
+    {"gemm_split", L3AC_FIELD(gemm_split), true, 0, 1, 1, "L3AC_GEMM_SPLIT"},
+    {"head_pretanh", L3AC_FIELD(head_pretanh), true, 0, 1, 0, nullptr},
+    {"narrow_ring", L3AC_FIELD(narrow_ring), false, 0, 2, 1, nullptr},
+    {"wide_sliced", L3AC_FIELD(wide_sliced), false, 0, 2, 1, nullptr},
+    {"unit_counter", L3AC_FIELD(unit_counter), false, 0, 3, 1, "L3AC_UNIT_COUNTER"},
+    {"trans_coop", L3AC_FIELD(coop.enabled), true, 0, 1, 1, "L3AC_TRANS_COOP"},
+    {"coop_timeout_ms", L3AC_FIELD(coop.timeout_ms), false, 1, 20000, 250, nullptr},
+    {"down_fused", L3AC_FIELD(down_fused), false, 0, 2, 2, "L3AC_DOWN_FUSED"},
+    {"gemm_w256", L3AC_FIELD(gemm_w256), false, 0, 2, 1, "L3AC_GEMM_W256"},
+    {"unit_chunk_mb", L3AC_FIELD(unit_chunk_mb), false, 0, 65536, 192, "L3AC_UNIT_CHUNK_MB"},
+};
+#undef L3AC_FIELD
+
+const Option* find_option(const char* name) {
+    for (const Option& o : kOptions)
+        if (std::strcmp(o.name, name) == 0) return &o;
+    return nullptr;
+}
+
+int unknown_option(const char* who, const char* name) {
+    std::string names;
+    for (const Option& o : kOptions) names += std::string(names.empty() ? "" : ", ") + o.name;
+    l3ac_set_error("%s: unknown option '%s' (%s; to set only: coop_release_claim, coop_test_fault)", who, name, names.c_str());
+    return L3AC_EINVAL;
+}
+
+int initial_value(const Option& o) {  // (std::atoi: l3ac_amd/__init__.py::_env_atoi_flag reads L3AC_GEMM_SPLIT the same way)
+    const char* e = o.env ? std::getenv(o.env) : nullptr;
+    return e ? std::atoi(e) : o.def;
+}
+
+int checked_value(const Option& o, int value) { return o.flag ? value != 0 : std::min(std::max(value, o.lo), o.hi); }
+
+int set_checked(l3ac_ctx* ctx, const Option& o, int value, const char* who) {
+    L3AC_REQUIRE(!(std::strcmp(o.name, "down_fused") == 0 && value == 1),
+                 "%s: down_fused = 1 (the bf16x3 one-kernel down layers) was retired, DESIGN.md section 4; 2 (the default) is the one-kernel "
+                 "form with the bits of 0, the GEMM + row kernel", who);
+    o.field(*ctx) = checked_value(o, value);
+    return L3AC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -170,15 +225,11 @@ int l3ac_create(const l3ac_config* cfg, const l3ac_tensor* tensors, int32_t n_te
     L3AC_REQUIRE(ctx, "out of host memory");
     ctx->cfg = *cfg;
     ctx->device = device;
-    ctx->gemm_split = gemm_split_default();
-    {
-        const char* e = std::getenv("L3AC_DOWN_FUSED");
-        if (e) ctx->down_fused = std::atoi(e);
-        e = std::getenv("L3AC_UNIT_COUNTER");  // the initial value of option "unit_counter" (A/B runs of bench.py)
-        if (e) ctx->unit_counter = std::atoi(e);  // 0: static shares; 1: all; 2: conv_unit_wide only; 3: legacy units only (measurement)
-    }
+    int rc = L3AC_OK;
+    for (const Option& o : kOptions)
+        if (rc == L3AC_OK) rc = set_checked(ctx, o, initial_value(o), o.env ? o.env : "l3ac_create");
     DeviceGuard guard(device);
-    int rc = guard.ok ? network_build(ctx, tensors, n_tensors) : L3AC_EHIP;
+    if (rc == L3AC_OK) rc = guard.ok ? network_build(ctx, tensors, n_tensors) : L3AC_EHIP;
     if (rc == L3AC_OK && hipEventCreateWithFlags(&ctx->ws_done, hipEventDisableTiming) != hipSuccess) {
         l3ac_set_error("hipEventCreate failed");
         rc = L3AC_EHIP;
@@ -626,11 +677,7 @@ void l3ac_split3_host(const float* x, int64_t n, uint16_t* planes) {
     }
 }
 
-int l3ac_ctx_set_head_pretanh(l3ac_ctx* ctx, int32_t enable) {
-    L3AC_REQUIRE(ctx != nullptr, "null context");
-    ctx->head_pretanh = enable != 0;
-    return L3AC_OK;
-}
+int l3ac_ctx_set_head_pretanh(l3ac_ctx* ctx, int32_t enable) { return l3ac_ctx_set_option(ctx, "head_pretanh", enable); }
 
 int l3ac_op_snake(const float* x, float* y, int64_t rows, int32_t c, const float* alpha, int32_t mode, void* stream) {
     L3AC_REQUIRE(x && y && alpha && rows >= 0 && c > 0 && c % 4 == 0 && c <= 4096 && mode >= 0 && mode <= 4, "op_snake: bad arguments");
@@ -654,35 +701,31 @@ int l3ac_op_snake(const float* x, float* y, int64_t rows, int32_t c, const float
 
 int l3ac_ctx_set_option(l3ac_ctx* ctx, const char* name, int32_t value) {
     L3AC_REQUIRE(ctx != nullptr && name != nullptr, "set_option: null argument");
-    const std::string n(name);
-    if (n == "gemm_split") ctx->gemm_split = value != 0;
-    else if (n == "head_pretanh") ctx->head_pretanh = value != 0;
-    else if (n == "wide_sliced") ctx->wide_sliced = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (n == "unit_counter") ctx->unit_counter = value < 0 ? 0 : (value > 3 ? 3 : value);
-    else if (n == "narrow_ring") ctx->narrow_ring = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (n == "trans_coop") ctx->coop.enabled = value != 0;
-    else if (n == "coop_timeout_ms") ctx->coop.timeout_ms = value < 1 ? 1 : (value > 20000 ? 20000 : value);
-    else if (n == "coop_release_claim") {  // (any value) give this context's CUs back to the per-device registry: the next cooperative launch
-        // claims what IT needs.  A claim only grows otherwise — a context that once ran 32 clips keeps 192 CUs and pushes other contexts'
-        // small batches into the one-workgroup form (a speed matter, never a correctness one).  Not while a graph captured from this
-        // context may still replay a cooperative launch: the registry would no longer cover it.
+    if (std::strcmp(name, "coop_release_claim") == 0) {  // (any value) give this context's CUs back to the per-device registry: the next
+        // cooperative launch claims what IT needs.  A claim only grows otherwise — a context that once ran 32 clips keeps 192 CUs and pushes
+        // other contexts' small batches into the one-workgroup form (a speed matter, never a correctness one).  Not while a graph captured
+        // from this context may still replay a cooperative launch: the registry would no longer cover it.
         trans_coop_release(ctx->coop);
+        return L3AC_OK;
     }
-    else if (n == "coop_test_fault") ctx->coop.fault_part = value - 1;  // 0 = off, j + 1 = workgroup j of every clip withholds its first arrival
-    else if (n == "down_fused") ctx->down_fused = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else {
-        l3ac_set_error("set_option: unknown option '%s' (gemm_split, head_pretanh, narrow_ring, wide_sliced, unit_counter, trans_coop, coop_timeout_ms, coop_release_claim, coop_test_fault, down_fused)", name);
-        return L3AC_EINVAL;
+    if (std::strcmp(name, "coop_test_fault") == 0) {  // 0 = off, j + 1 = workgroup j of every clip withholds its first arrival
+        ctx->coop.fault_part = value - 1;
+        return L3AC_OK;
     }
+    const Option* o = find_option(name);
+    return o ? set_checked(ctx, *o, value, "set_option") : unknown_option("set_option", name);
+}
+
+int l3ac_ctx_get_option(const l3ac_ctx* ctx, const char* name, int32_t* out) {
+    L3AC_REQUIRE(ctx != nullptr && name != nullptr && out != nullptr, "get_option: null argument");
+    const Option* o = find_option(name);
+    if (!o) return unknown_option("get_option", name);
+    *out = o->field(const_cast<l3ac_ctx&>(*ctx));
     return L3AC_OK;
 }
 
-int l3ac_ctx_set_gemm_split(l3ac_ctx* ctx, int32_t enable) {
-    L3AC_REQUIRE(ctx != nullptr, "null context");
-    ctx->gemm_split = enable != 0;
-    return L3AC_OK;
-}
-int32_t l3ac_ctx_get_gemm_split(const l3ac_ctx* ctx) { return ctx && ctx->gemm_split ? 1 : 0; }
+int l3ac_ctx_set_gemm_split(l3ac_ctx* ctx, int32_t enable) { return l3ac_ctx_set_option(ctx, "gemm_split", enable); }
+int32_t l3ac_ctx_get_gemm_split(const l3ac_ctx* ctx) { int32_t v = 0; return l3ac_ctx_get_option(ctx, "gemm_split", &v) == L3AC_OK ? v : 0; }
 
 int64_t l3ac_gemm_split_image_bytes(int32_t n, int32_t k) {
     return (n > 0 && k > 0 && gemm_split_eligible(n, k)) ? gemm_split_image_bytes(n, k) : 0;
@@ -693,12 +736,18 @@ int l3ac_gemm_split_image(const float* w, int32_t n, int32_t k, void* image, voi
     return launch_gemm_split_image((hipStream_t)stream, w, k, n, k, (unsigned char*)image);
 }
 
-int l3ac_gemm_split_f32(const float* a, int64_t lda, const void* image, const float* bias, float* c, int64_t ldc, int64_t m,
-                        int32_t n, int32_t k, void* stream) {
+int l3ac_gemm_split_f32_at(const float* a, int64_t lda, const void* image, const float* bias, float* c, int64_t ldc, int64_t m,
+                           int32_t n, int32_t k, int32_t w256, void* stream) {
+    L3AC_REQUIRE(w256 >= 0 && w256 <= 2, "split gemm: w256 = %d, not 0, 1 or 2", w256);
     GemmArgs g{};
     g.a = a; g.lda = lda; g.w_img = (const unsigned char*)image; g.c = c; g.ldc = ldc; g.m = m; g.n = n; g.k = k; g.bias = bias;
-    g.epi = EPI_BIAS;
+    g.epi = EPI_BIAS; g.w256 = w256;
     return launch_gemm_split((hipStream_t)stream, g);
+}
+int l3ac_gemm_split_f32(const float* a, int64_t lda, const void* image, const float* bias, float* c, int64_t ldc, int64_t m,
+                        int32_t n, int32_t k, void* stream) {  // (no context: option gemm_w256 as a new context would start)
+    const Option& o = *find_option("gemm_w256");
+    return l3ac_gemm_split_f32_at(a, lda, image, bias, c, ldc, m, n, k, checked_value(o, initial_value(o)), stream);
 }
 
 }  // extern "C"

@@ -34,6 +34,8 @@ struct GemmArgs {
     int n = 0, k = 0;
     // epilogue
     int epi = EPI_BIAS;
+    int w256 = 1;  // split route, batch rows (option "gemm_w256"): 0 no product, 1 the long-K light-epilogue ones, 2 every eligible
+                   // shape on gemm_split_kernel_w256 (the same bits either way; in what was padding: the kernels' arguments keep their layout)
     const float* bias = nullptr;
     const float* res = nullptr;
     int64_t ldres = 0;
@@ -56,9 +58,7 @@ int launch_gemm(hipStream_t s, const GemmArgs& g);
 
 // bf16x3 split-operand GEMM (kernels/gemm_split.hip)
 #define L3AC_SPLIT_TILE_BYTES 24576  // one k tile (32) of one column block (128): 3 planes x 128 rows x 64 B
-bool gemm_split_default();                 // L3AC_GEMM_SPLIT (default 1): the route a new context starts on; the route of a
-                                           // launch is its GemmArgs::w_img (null = exact fp32 MFMA kernel)
-bool gemm_split_eligible(int n, int k);
+bool gemm_split_eligible(int n, int k);  // the route of a launch is its GemmArgs::w_img (null = exact fp32 MFMA kernel)
 bool gemm_split_conv_ok(const struct GemmArgs& g);  // taps > 1 on the split route: cin % 32 == 0, plain frame-major rows
 int64_t gemm_split_image_bytes(int n, int k);
 void gemm_split_image_host(const float* w, int64_t ldw, int n, int k, unsigned char* img);  // img: host buffer

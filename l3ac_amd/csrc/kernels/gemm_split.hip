@@ -29,7 +29,6 @@
 
 #include <atomic>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -672,28 +671,12 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel_few_blocks(const
 
 }  // namespace
 
-// the route a new context starts on (l3ac_ctx::gemm_split; l3ac_ctx_set_gemm_split changes it per context)
-bool gemm_split_default() {
-    const char* e = std::getenv("L3AC_GEMM_SPLIT");
-    return e ? (std::atoi(e) != 0) : true;
-}
-
 // n < 192 would be a single 128-column block per row panel: too few workgroups at the transformer's row counts, where
 // the exact kernel's narrower tiles win (measured: 128 x 344 and 128 x 192 weights, 26 vs 45 TFLOP/s at 15360 rows)
 bool gemm_split_eligible(int n, int k) { return n >= 192 && k >= 32 && k % 8 == 0; }
 // implicit-conv A operand (taps > 1): whole k tiles inside a tap, 32-bit row arithmetic
 bool gemm_split_conv_ok(const GemmArgs& g) {
     return g.cin > 0 && g.cin % BK == 0 && g.k == g.taps * g.cin && g.frames > 0 && g.m % g.frames == 0 && g.m < ((int64_t)1 << 31) && g.lda == g.cin;
-}
-
-// L3AC_GEMM_W256 (A/B measurements — same bits either way): 0 the batch products of 256-column weights stay on gemm_split_kernel |
-// 1 (default) the light-epilogue long-K products on gemm_split_kernel_w256 | 2 every eligible shape there
-static int w256_enabled() {
-    static const int on = [] {
-        const char* e = std::getenv("L3AC_GEMM_W256");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on;
 }
 
 int64_t gemm_split_image_bytes(int n, int k) { return (int64_t)((n + BN - 1) / BN) * ((k + BK - 1) / BK) * W_TILE; }
@@ -744,8 +727,8 @@ int launch_gemm_split(hipStream_t s, const GemmArgs& g) {
     // workgroup (gemm_split_w256.hip).  Measured inside the 256-clip step (profiles/r06/gemm_w256.md): 24480 x 512 x 2048 0.242 -> 0.221 ms;
     // the first product (K = 512, snake + GRN epilogue: four tiles per CU, each with an exposed 38 k-cycle epilogue) 0.246 -> 0.258 — and
     // 0.265 in a persistent form that runs a tile's epilogue inside the next tile's k loop (tools/patches/gemm_split_w256d.patch) —,
-    // 46080 x 256 x 512 0.063 -> 0.066: those stay on gemm_split_kernel (L3AC_GEMM_W256=2 sends them here too: same bits)
-    const int w256 = conv ? 0 : w256_enabled();  // 1: the light-epilogue long-K products | 2: every eligible shape
+    // 46080 x 256 x 512 0.063 -> 0.066: those stay on gemm_split_kernel (GemmArgs::w256 = 2 sends them here too: same bits)
+    const int w256 = conv ? 0 : g.w256;  // 1: the light-epilogue long-K products | 2: every eligible shape
     const bool use_w256 = w256 && gemm_split_w256_ok(g) && blocks > cus && (w256 >= 2 || (g.k >= 1024 && (g.epi == EPI_BIAS || g.epi == EPI_BIAS_RES)));
     char name[64];
     std::snprintf(name, sizeof(name), "%s %lldx%dx%d e%d", conv ? "gemm_split_conv_kernel" : use_w256 ? "gemm_split_kernel_w256" : "gemm_split_kernel",

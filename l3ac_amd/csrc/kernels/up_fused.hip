@@ -69,16 +69,12 @@ __device__ __forceinline__ float row_next(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, false));  // row_shl:1
 }
 
-// DOWN (round 4): the same kernel as an encoder DOWN layer (reference l3ac/modules.py:96-99): Conv1d(k = stride) — a frame-major patch of
-// `stride` frames is one contiguous row of CIN = stride x cin values — followed by ChannelNorm; no gate, no upsample, no halo (a wave stores
-// all 16 frames of its tile).  It replaces a small-N fp32-MFMA GEMM, the tensor it wrote and row_kernel<PLAIN,CN>.
 // WAVES: waves per workgroup — 16 (one workgroup per CU fills it), or 4 for grids of a few tiles (a single clip: 900 frames at 256 -> 96
 // are 65 tiles = five 16-wave workgroups on five CUs, each filling 144 KB of LDS first: 31 us; as 17 workgroups of four waves ~ a third).
 // A tile's arithmetic does not depend on it: the same bits.
-template <int CIN, int COUT, bool DOWN, int WAVES>
+template <int CIN, int COUT, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const UpFusedArgs p, const int tiles_per_clip, const int n_tiles, const int tickets) {
     using G = UfGeo<CIN, COUT>;
-    constexpr int CORE = DOWN ? 16 : UF_CORE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_uf[];
     float* const par = reinterpret_cast<float*>(smem_uf + G::OFF_PAR);
     float* const gws = reinterpret_cast<float*>(smem_uf + G::OFF_GW);
@@ -96,12 +92,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
         par[G::CP + i] = i < COUT ? p.nw[i] : 0.f;
         par[2 * G::CP + i] = i < COUT ? p.nb[i] : 0.f;
     }
-    if constexpr (!DOWN) {
-        for (int i = tid; i < G::CINP; i += 64 * WAVES) {
-            const float4 w4 = i < CIN ? *reinterpret_cast<const float4*>(p.gate_w + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(gws + 4 * i) = w4;
-            gbs[i] = i < CIN ? p.gate_b[i] : 0.f;
-        }
+    for (int i = tid; i < G::CINP; i += 64 * WAVES) {
+        const float4 w4 = i < CIN ? *reinterpret_cast<const float4*>(p.gate_w + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(gws + 4 * i) = w4;
+        gbs[i] = i < CIN ? p.gate_b[i] : 0.f;
     }
     int* const ticket_s = reinterpret_cast<int*>(smem_uf + G::OFF_TICKET);
     if (tid == 0) *ticket_s = 0;
@@ -113,12 +107,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
     const int fl = lane & 15, lg = lane >> 4;
     const int T = p.frames, S = p.scale;
     const float rscale = (float)(1.0 / (double)S);
-    float4 iw = make_float4(0.f, 0.f, 0.f, 0.f), ib = iw;
-    if constexpr (!DOWN) {
-        iw = *reinterpret_cast<const float4*>(p.in_w);
-        ib = *reinterpret_cast<const float4*>(p.in_b);
-    }
-    const unsigned char* const wl = smem_uf + 16 * lane;
+    const float4 iw = *reinterpret_cast<const float4*>(p.in_w);
+    const float4 ib = *reinterpret_cast<const float4*>(p.in_b);
     // PRE (the narrow forms: at most three k steps = 24 registers): the NEXT tile's input rows and gate signals are requested before the
     // current tile's products — a wave's tile is otherwise load -> wait -> products -> s output frames with nothing of its own in flight
     // behind the loads (wait_any 0.6 of the wave cycles, 3.6-4.1 TB/s).  The same values reach the same operations: the same bits.
@@ -132,7 +122,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
         if constexpr (PRE) {
             const int b = tile / tiles_per_clip;
             const int k = tile - b * tiles_per_clip;
-            const int f = CORE * k - (DOWN ? 0 : 1) + fl;
+            const int f = UF_CORE * k - 1 + fl;
             const bool valid = tile < n_tiles && f >= 0 && f < T;
             const int64_t r = valid ? (int64_t)b * T + f : 0;
             const float* const row = p.x + r * CIN;
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
                 xpre[s][0] = *reinterpret_cast<const f32x4_t*>(row + 32 * s + 4 * lg);
                 xpre[s][1] = 32 * s + 16 < CIN ? *reinterpret_cast<const f32x4_t*>(row + 32 * s + 16 + 4 * lg) : f32x4_t{0.f, 0.f, 0.f, 0.f};
             }
-            if constexpr (!DOWN) ypre = *reinterpret_cast<const float4*>(p.yi + r * 4);
+            ypre = *reinterpret_cast<const float4*>(p.yi + r * 4);
         }
     };
     const int tile_first = tickets ? take_tile<WAVES>(ticket_s, lane, n_tiles) : (int)blockIdx.x * WAVES + wave;
@@ -161,7 +151,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
         const unsigned char* const wl = smem_uf + 16 * lane_t;
         const int b = tile / tiles_per_clip;
         const int k = tile - b * tiles_per_clip;
-        const int f = CORE * k - (DOWN ? 0 : 1) + fl;  // this lane's input frame
+        const int f = UF_CORE * k - 1 + fl;  // this lane's input frame
         const bool valid = f >= 0 && f < T;
         const int fv = valid ? f : 0;
         const float* const row = p.x + ((int64_t)b * T + fv) * CIN;
@@ -173,22 +163,18 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
             prefetch(tile_next);
         }
         // ---- gate input: z = InstanceNorm(branch signals) of this frame (rows.hip, SRC_GATE) ----------------------------------------
-        float z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
-        if constexpr (!DOWN) {
-            const float4 yraw = PRE ? ycur : *reinterpret_cast<const float4*>(p.yi + ((int64_t)b * T + fv) * 4);
-            const float4 mean = *reinterpret_cast<const float4*>(p.stats + (int64_t)b * 8);
-            const float4 istd = *reinterpret_cast<const float4*>(p.stats + (int64_t)b * 8 + 4);
-            z0 = (yraw.x - mean.x) * istd.x * iw.x + ib.x;
-            z1 = (yraw.y - mean.y) * istd.y * iw.y + ib.y;
-            z2 = (yraw.z - mean.z) * istd.z * iw.z + ib.z;
-            z3 = (yraw.w - mean.w) * istd.w * iw.w + ib.w;
-        }
+        const float4 yraw = PRE ? ycur : *reinterpret_cast<const float4*>(p.yi + ((int64_t)b * T + fv) * 4);
+        const float4 mean = *reinterpret_cast<const float4*>(p.stats + (int64_t)b * 8);
+        const float4 istd = *reinterpret_cast<const float4*>(p.stats + (int64_t)b * 8 + 4);
+        const float z0 = (yraw.x - mean.x) * istd.x * iw.x + ib.x;
+        const float z1 = (yraw.y - mean.y) * istd.y * iw.y + ib.y;
+        const float z2 = (yraw.z - mean.z) * istd.z * iw.z + ib.z;
+        const float z3 = (yraw.w - mean.w) * istd.w * iw.w + ib.w;
         // ---- c^T = W . x'^T + bias ---------------------------------------------------------------------------------------------------
         f32x4_t acc[G::RT];
 #pragma unroll
         for (int rt = 0; rt < G::RT; ++rt) acc[rt] = *reinterpret_cast<const f32x4_t*>(par + 16 * rt + 4 * lg);
         auto gated = [&](const f32x4_t xv, const int c0) __attribute__((always_inline)) -> f32x4_t {  // x + (gate_b + gate_w . z) * x
-            if constexpr (DOWN) return xv;
             f32x4_t o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
                 acc[rt] = mfma6(wf, bp, acc[rt]);
             }
         }
-        const bool core = DOWN ? f < T : fl >= 1 && fl <= UF_CORE && f < T;  // (f >= 0 for fl >= 1)
+        const bool core = fl >= 1 && fl <= UF_CORE && f < T;  // (f >= 0 for fl >= 1)
         float* const yclip = p.y + (int64_t)b * T * S * COUT;
         // ---- s output frames per input frame: lerp (ATen upsample_linear1d, rows.hip SRC_LERP), ChannelNorm, store -----------------
 #pragma unroll 1
@@ -254,13 +240,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
                     // the two shifted copies of the accumulators cost the 256 -> 96 kernel 46 spilled registers)
                     // the shifts themselves run in EVERY lane, outside any lane-dependent control flow: a DPP read from a lane the EXEC mask has
                     // switched off returns 0, not that lane's register (the first build selected by branching and lost frame 0 at clip starts)
-                    float u = acc[rt][i];
-                    if constexpr (!DOWN) {
-                        const float pv = row_prev(acc[rt][i]), nx = row_next(acc[rt][i]);
-                        const float x0 = p0 ? pv : acc[rt][i];
-                        const float x1 = n1 ? nx : acc[rt][i];
-                        u = __fadd_rn(__fmul_rn(l0, x0), __fmul_rn(l1, x1));
-                    }
+                    const float pv = row_prev(acc[rt][i]), nx = row_next(acc[rt][i]);
+                    const float x0 = p0 ? pv : acc[rt][i];
+                    const float x1 = n1 ? nx : acc[rt][i];
+                    const float u = __fadd_rn(__fmul_rn(l0, x0), __fmul_rn(l1, x1));
                     v[rt][i] = (16 * rt + 4 * lg + i < COUT) ? u : 0.f;
                 }
                 s1 += (v[rt][0] + v[rt][1]) + (v[rt][2] + v[rt][3]);
@@ -294,12 +277,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
     }
 }
 
-template <int CIN, int COUT, bool DOWN, int WAVES>
+template <int CIN, int COUT, int WAVES>
 int launch_uf_waves(hipStream_t s, const UpFusedArgs& a, int tiles_per_clip, int64_t tiles) {
     using G = UfGeo<CIN, COUT>;
     static PerDeviceOnce configured;
     if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(up_fused_kernel<CIN, COUT, DOWN, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
+        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(up_fused_kernel<CIN, COUT, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         configured.done();
     }
     int64_t blocks = ceil_div64(tiles, WAVES);
@@ -308,31 +291,30 @@ int launch_uf_waves(hipStream_t s, const UpFusedArgs& a, int tiles_per_clip, int
     // tiles by ticket (take_tile) where a wave has at least four of them (measured, profiles/r06/tickets_ab.txt: 48 -> 24 0.214 -> 0.193 ms,
     // 96 -> 48 and 256 -> 96 - 2 %; with two tiles per wave — the 48 -> 96 down layer — the tickets cost 5 %)
     const int tickets = tiles >= 4 * blocks * WAVES;
-    hipLaunchKernelGGL((up_fused_kernel<CIN, COUT, DOWN, WAVES>), dim3((unsigned)blocks), dim3(64 * WAVES), G::LDS, s, a, tiles_per_clip, (int)tiles, tickets);
+    hipLaunchKernelGGL((up_fused_kernel<CIN, COUT, WAVES>), dim3((unsigned)blocks), dim3(64 * WAVES), G::LDS, s, a, tiles_per_clip, (int)tiles, tickets);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
 
-template <int CIN, int COUT, bool DOWN = false>
+template <int CIN, int COUT>
 int launch_uf(hipStream_t s, const UpFusedArgs& a) {
-    constexpr int CORE = DOWN ? 16 : UF_CORE;
-    const int tiles_per_clip = (a.frames + CORE - 1) / CORE;
+    const int tiles_per_clip = (a.frames + UF_CORE - 1) / UF_CORE;
     const int64_t tiles = (int64_t)a.batch * tiles_per_clip;
     L3AC_REQUIRE(tiles < ((int64_t)1 << 31) - 65536 && (int64_t)a.frames * a.scale < ((int64_t)1 << 30), "up_fused: too many tiles");
     const double rows = (double)a.batch * a.frames;
     char name[64];
-    std::snprintf(name, sizeof(name), DOWN ? "down_fused_kernel<%d,%d>" : "up_fused_kernel<%d,%d>", CIN, COUT);
-    ProfScope prof(s, name, rows * 2.0 * CIN * COUT, rows * 4.0 * (CIN + (DOWN ? 0 : 4) + (double)a.scale * COUT));
+    std::snprintf(name, sizeof(name), "up_fused_kernel<%d,%d>", CIN, COUT);
+    ProfScope prof(s, name, rows * 2.0 * CIN * COUT, rows * 4.0 * (CIN + 4 + (double)a.scale * COUT));
     // fewer 16-wave workgroups than half the CUs: four-wave workgroups spread the tiles over four times as many CUs (same bits)
-    if (2 * ceil_div64(tiles, UF_WAVES) <= l3ac_device_cu_count()) return launch_uf_waves<CIN, COUT, DOWN, 4>(s, a, tiles_per_clip, tiles);
-    return launch_uf_waves<CIN, COUT, DOWN, UF_WAVES>(s, a, tiles_per_clip, tiles);
+    if (2 * ceil_div64(tiles, UF_WAVES) <= l3ac_device_cu_count()) return launch_uf_waves<CIN, COUT, 4>(s, a, tiles_per_clip, tiles);
+    return launch_uf_waves<CIN, COUT, UF_WAVES>(s, a, tiles_per_clip, tiles);
 }
 
 
 // ---- encoder down layers 24 -> 48 and 48 -> 96, EXACT form (round 6): Conv1d(k = stride) + bias + ChannelNorm in one kernel with the
 // arithmetic of the two kernels it replaces — gemm_f32_kernel (v_mfma_f32_32x32x2_f32, bias epilogue) and row_kernel<PLAIN,CN> — bit for
-// bit, so that it can be the DEFAULT (the bf16x3 DOWN form above is an equally accurate but different rounding: one token of the stress
-// weights changes sides with it).  What makes the bits equal:
+// bit, so that it can be the DEFAULT (the bf16x3 DOWN form of up_fused_kernel it followed, retired since, was an equally accurate but
+// different rounding: one token of the stress weights changed sides with it).  What makes the bits equal:
 //   * products: v_mfma_f32_16x16x4_f32 is, per output element, the k-ordered chain of fused multiply-adds in lane-group order
 //     (tools/probes/mfma_f32_order_probe.hip), as 32x32x2 is in lane-half order.  gemm_f32_kernel feeds k in the order 0, 4, 1, 5, 2, 6, 3, 7
 //     inside every group of 8 (its lanes read 16 B and instruction r takes element r of both halves); here lane group g of instruction j
@@ -419,7 +401,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void down_exact_kernel(const UpFused
         // differently per instantiation — in the compiled row kernels a chunk's squared deviations are (dx dx + dy dy) + (dz dz + dw dw) with
         // separate multiplies at one chunk per lane (C = 48) and fma(dx, dx, dy dy) + fma(dz, dz, dw dw) at two (C = 96); the affine is
         // fma(w, rstd d, b) in both (ISA of rows.hip, hipcc 7.2) — and this kernel must not be reshaped on its own.
-        // tests/test_gpu_blocks.py::test_down_and_k3_layers asserts the equality with the two-kernel route bit for bit.
+        // tests/test_gpu_blocks.py::test_down_layer_forms_and_k3_layers asserts the equality with the two-kernel route bit for bit.
         float4 v[G::RT];
 #pragma unroll
         for (int rt = 0; rt < G::RT; ++rt) {
@@ -527,25 +509,11 @@ int launch_up_fused(hipStream_t s, const EnhW& e, const UpW& w, const float* x, 
     return L3AC_EINVAL;
 }
 
-// ---- encoder down layers: Conv1d(k = stride) + ChannelNorm (up_fused_kernel<K, Cout, DOWN>) ---------------------------------------------
-bool down_fused_supported(int cin, int stride, int cout) {
+// ---- encoder down layers: Conv1d(k = stride) + ChannelNorm in one kernel (down_exact_kernel): fp32 weights in fragment order ------------
+bool down_exact_supported(int cin, int stride, int cout) {
     const int k = cin * stride;
     return (k == 144 && cout == 48) || (k == 240 && cout == 96) || (k == 192 && cout == 96);
 }
-// x [batch][frames_out * stride][cin] -> y [batch][frames_out][cout]; w.fused_img = up_fused_image(w.w, stride * cin, cout)
-int launch_down_fused(hipStream_t s, const DownW& w, const float* x, float* y, int batch, int frames_out) {
-    L3AC_REQUIRE(w.fused_img && w.nw && w.nb && x && y && x != y && batch > 0 && frames_out > 0, "down_fused: bad arguments");
-    UpFusedArgs a{};
-    a.x = x; a.y = y; a.batch = batch; a.frames = frames_out; a.scale = 1; a.img = w.fused_img; a.bias = w.b; a.nw = w.nw; a.nb = w.nb; a.eps = 1e-8f;
-    const int k = w.cin * w.stride;
-    if (k == 144 && w.cout == 48) return launch_uf<144, 48, true>(s, a);
-    if (k == 240 && w.cout == 96) return launch_uf<240, 96, true>(s, a);
-    if (k == 192 && w.cout == 96) return launch_uf<192, 96, true>(s, a);
-    l3ac_set_error("down_fused: %d x %d -> %d not supported", w.cin, w.stride, w.cout);
-    return L3AC_EINVAL;
-}
-
-// ---- the EXACT one-kernel form of the same down layers (down_exact_kernel): fp32 weights in fragment order ------------------------------
 // block (rt, q) = 64 lanes x 8 B: lane (r = lane & 15, g = lane >> 4) holds w[16 rt + r][8 q + 4 (g & 1) + (g >> 1)] and the same + 2
 std::vector<unsigned char> down_exact_image(const float* w, int k, int cout) {
     const int nq = k / 8, rt_n = cout / 16;

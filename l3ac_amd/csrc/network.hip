@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -411,11 +410,8 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
             for (UpW& u : ctx->dec_up)
                 if (up_fused_supported(u.cin, u.cout)) b.extra_imgs.push_back({up_fused_image(b.host_of(u.w), u.cin, u.cout), &u.fused_img});
             for (DownW& d : ctx->enc_down)  // (sized before the loops above as well)
-                if (d.nw && down_fused_supported(d.cin, d.stride, d.cout))
-                {
-                    b.extra_imgs.push_back({up_fused_image(b.host_of(d.w), d.cin * d.stride, d.cout), &d.fused_img});
+                if (d.nw && down_exact_supported(d.cin, d.stride, d.cout))
                     b.extra_imgs.push_back({down_exact_image(b.host_of(d.w), d.cin * d.stride, d.cout), &d.exact_img});
-                }
         }
         if (b.err.empty() && last_block_fused_supported(cl, 9)) {  // (ctx->legacy no longer reallocates: the targets stay valid)
             for (LegacyW& l : ctx->legacy) {
@@ -478,8 +474,6 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
             *ctx->coop.fail_host = 0;
             L3AC_HIP_CHECK(hipHostGetDevicePointer((void**)&ctx->coop.fail_dev, ctx->coop.fail_host, 0));
         }
-        const char* e = std::getenv("L3AC_TRANS_COOP");
-        if (e) ctx->coop.enabled = std::atoi(e);
     }
     {  // GRN guard: starts at +inf
         const float inf = INFINITY;
@@ -651,6 +645,14 @@ int conv_unit_step(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, float** cur
     return run_conv_unit(ctx, s, w, *cur, *cur, batch, frames);
 }
 
+// a product with one of the context's weights (g.w) on the context's route: its split image — null on the exact route, which then takes
+// the fp32 MFMA kernel — and its choice of batch products for gemm_split_kernel_w256
+static int gemm_on_route(const l3ac_ctx* ctx, hipStream_t s, GemmArgs g) {
+    g.w_img = ctx->img(g.w);
+    g.w256 = ctx->gemm_w256;
+    return launch_gemm(s, g);
+}
+
 static int run_conv_unit_rows(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames) {
     const int64_t rows = (int64_t)batch * frames;
     Workspace& ws = ctx->ws;
@@ -659,18 +661,18 @@ static int run_conv_unit_rows(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, 
     r.src = SRC_DWCONV7; r.norm = NORM_LN; r.dw_w = w.dw_w; r.dw_b = w.dw_b; r.nw = w.ln_w; r.nb = w.ln_b; r.eps = 1e-8f;
     L3AC_TRY(launch_rows(s, r));
     GemmArgs g{};  // pw_conv1 -> snake -> GRN (modules.py:36-38)
-    g.a = ws.a; g.lda = w.c; g.w = w.w1; g.w_img = ctx->img(w.w1); g.ldw = w.c; g.c = ws.h; g.ldc = 4 * w.c; g.m = rows; g.n = 4 * w.c; g.k = w.c;
+    g.a = ws.a; g.lda = w.c; g.w = w.w1; g.ldw = w.c; g.c = ws.h; g.ldc = 4 * w.c; g.m = rows; g.n = 4 * w.c; g.k = w.c;
     g.bias = w.b1; g.alpha = w.alpha; g.inv_alpha = w.inv_alpha; g.gamma = w.gamma; g.beta = w.beta;
     g.epi = ctx->cfg.grn_exact ? EPI_SNAKE : EPI_SNAKE_GRN;
-    L3AC_TRY(launch_gemm(s, g));
+    L3AC_TRY(gemm_on_route(ctx, s, g));
     if (ctx->cfg.grn_exact) {
         L3AC_TRY(launch_grn_sumsq(s, ws.h, batch, (int64_t)frames * 4 * w.c, ws.sumsq));
         L3AC_TRY(launch_grn_apply(s, ws.h, batch, frames, 4 * w.c, ws.sumsq, w.gamma, w.beta, ctx->grn_min_sumsq));
     }
     GemmArgs g2{};  // pw_conv2 + residual (modules.py:39, xtract/nn/layers.py:59-62)
-    g2.a = ws.h; g2.lda = 4 * w.c; g2.w = w.w2; g2.w_img = ctx->img(w.w2); g2.ldw = 4 * w.c; g2.c = y; g2.ldc = w.c; g2.m = rows; g2.n = w.c; g2.k = 4 * w.c;
+    g2.a = ws.h; g2.lda = 4 * w.c; g2.w = w.w2; g2.ldw = 4 * w.c; g2.c = y; g2.ldc = w.c; g2.m = rows; g2.n = w.c; g2.k = 4 * w.c;
     g2.bias = w.b2; g2.epi = EPI_BIAS_RES; g2.res = x; g2.ldres = w.c;
-    return launch_gemm(s, g2);
+    return gemm_on_route(ctx, s, g2);
 }
 
 static int conv_unit_group(const l3ac_ctx* ctx, const ConvUnitW& w, int batch, int frames);
@@ -710,32 +712,26 @@ int run_conv_unit(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, const float*
 static int conv_unit_group(const l3ac_ctx* ctx, const ConvUnitW& w, int batch, int frames) {
     // Clips are independent, so the unit can run over groups of clips whose hidden tensor (4C floats per frame) stays in the
     // 256 MB Infinity Cache between the two products instead of making an HBM round trip (measured, 1kbps x 256: 19.15 ->
-    // 18.65 ms per step at 192 MB; 96 MB and below lose more to the smaller launches than they save).  L3AC_UNIT_CHUNK_MB
-    // overrides the target size of that tensor per group (0 = whole batch in one go).
-    static const int64_t chunk_mb = [] {
-        const char* e = std::getenv("L3AC_UNIT_CHUNK_MB");
-        return e ? (int64_t)std::atoi(e) : (int64_t)192;
-    }();
+    // 18.65 ms per step at 192 MB; 96 MB and below lose more to the smaller launches than they save).  Option "unit_chunk_mb"
+    // sets the target size of that tensor per group (0 = whole batch in one go).
+    const int64_t chunk_mb = ctx->unit_chunk_mb;
     const int64_t per_clip = (int64_t)frames * 4 * w.c * sizeof(float);
     int group = batch;
     if (chunk_mb > 0 && !ctx->cfg.grn_exact) group = (int)std::max<int64_t>(1, std::min<int64_t>(batch, (chunk_mb << 20) / per_clip));
     return group;
 }
 
-// the one-kernel form of a down layer (up_fused_kernel<K, Cout, DOWN>): bf16x3 route, the narrow encoder stages' widths
-static bool use_down_fused(const l3ac_ctx* ctx, const DownW& w) { return ctx->down_fused == 1 && ctx->gemm_split && w.fused_img && w.nw; }
-// the exact one-kernel form (down_exact_kernel): the bits of the GEMM + row kernel it replaces, on either route
+// the one-kernel form of a down layer (down_exact_kernel): the bits of the GEMM + row kernel it replaces, on either route
 static bool use_down_exact(const l3ac_ctx* ctx, const DownW& w) { return ctx->down_fused == 2 && w.exact_img && w.nw; }
 
 int run_down(l3ac_ctx* ctx, hipStream_t s, const DownW& w, const float* x, float* y, int batch, int frames) {
     L3AC_REQUIRE(frames % w.stride == 0, "down layer: frames=%d not a multiple of stride %d", frames, w.stride);
-    if (use_down_fused(ctx, w) && x != y) return launch_down_fused(s, w, x, y, batch, frames / w.stride);
     if (use_down_exact(ctx, w) && x != y) return launch_down_exact(s, w, x, y, batch, frames / w.stride);
     const int64_t rows_out = (int64_t)batch * (frames / w.stride);
     GemmArgs g{};  // Conv1d(k = stride): non-overlapping patches are contiguous in the frame-major layout
-    g.a = x; g.lda = (int64_t)w.stride * w.cin; g.w = w.w; g.w_img = ctx->img(w.w); g.ldw = (int64_t)w.stride * w.cin; g.c = y; g.ldc = w.cout;
+    g.a = x; g.lda = (int64_t)w.stride * w.cin; g.w = w.w; g.ldw = (int64_t)w.stride * w.cin; g.c = y; g.ldc = w.cout;
     g.m = rows_out; g.n = w.cout; g.k = w.stride * w.cin; g.bias = w.b; g.epi = EPI_BIAS;
-    L3AC_TRY(launch_gemm(s, g));
+    L3AC_TRY(gemm_on_route(ctx, s, g));
     if (w.nw) {  // ChannelNorm channels_first (modules.py:98), in place
         RowArgs r{};
         r.x = y; r.y = y; r.batch = batch; r.frames_in = frames / w.stride; r.frames_out = frames / w.stride; r.c = w.cout;
@@ -749,10 +745,10 @@ int run_down(l3ac_ctx* ctx, hipStream_t s, const DownW& w, const float* x, float
 int run_conv_k3(l3ac_ctx* ctx, hipStream_t s, const ConvK3W& w, const float* x, float* y, int batch, int frames) {
     GemmArgs g{};
     g.a = x; g.lda = w.cin; g.taps = 3; g.dil = 1; g.cin = w.cin; g.frames = frames;
-    g.w = w.w; g.w_img = ctx->img(w.w); g.ldw = 3 * w.cin; g.c = y; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = 3 * w.cin;
+    g.w = w.w; g.ldw = 3 * w.cin; g.c = y; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = 3 * w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
     (void)ctx;
-    return launch_gemm(s, g);
+    return gemm_on_route(ctx, s, g);
 }
 
 int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, float* y, int batch, int frames) {
@@ -768,9 +764,9 @@ int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, flo
 
 int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tmp, float* y, int batch, int frames) {
     GemmArgs g{};  // 1x1 conv (modules.py:161)
-    g.a = x; g.lda = w.cin; g.w = w.w; g.w_img = ctx->img(w.w); g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
+    g.a = x; g.lda = w.cin; g.w = w.w; g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
-    L3AC_TRY(launch_gemm(s, g));
+    L3AC_TRY(gemm_on_route(ctx, s, g));
     RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
     r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
     r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
@@ -812,7 +808,7 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     g.bias = w.b; g.epi = EPI_BIAS;
     g.gate_yi = ws.yi; g.gate_stats = ws.stats; g.gate_in_w = e.in_w; g.gate_in_b = e.in_b; g.gate_w = e.gate_w; g.gate_b = e.gate_b;
     g.gate_frames = frames;
-    L3AC_TRY(launch_gemm(s, g));
+    L3AC_TRY(launch_gemm(s, g));  // (not gemm_on_route: the gated A operand exists in the fp32 kernel only)
     RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
     r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
     r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
@@ -837,13 +833,13 @@ int run_legacy_unit(l3ac_ctx* ctx, hipStream_t s, const LegacyW& l, const float*
     L3AC_TRY(launch_snake(s, x, ws.a, rows, l.c, l.a0, l.ia0));
     GemmArgs g{};
     g.a = ws.a; g.lda = l.c; g.taps = 7; g.dil = l.dil; g.cin = l.c; g.frames = frames;
-    g.w = l.w1; g.w_img = ctx->img(l.w1); g.ldw = 7 * l.c; g.c = ws.h; g.ldc = l.c; g.m = rows; g.n = l.c; g.k = 7 * l.c;
+    g.w = l.w1; g.ldw = 7 * l.c; g.c = ws.h; g.ldc = l.c; g.m = rows; g.n = l.c; g.k = 7 * l.c;
     g.bias = l.b1; g.epi = EPI_SNAKE; g.alpha = l.a1; g.inv_alpha = l.ia1;
-    L3AC_TRY(launch_gemm(s, g));
+    L3AC_TRY(gemm_on_route(ctx, s, g));
     GemmArgs g2{};
-    g2.a = ws.h; g2.lda = l.c; g2.w = l.w2; g2.w_img = ctx->img(l.w2); g2.ldw = l.c; g2.c = y; g2.ldc = l.c; g2.m = rows; g2.n = l.c; g2.k = l.c;
+    g2.a = ws.h; g2.lda = l.c; g2.w = l.w2; g2.ldw = l.c; g2.c = y; g2.ldc = l.c; g2.m = rows; g2.n = l.c; g2.k = l.c;
     g2.bias = l.b2; g2.epi = EPI_BIAS_RES; g2.res = x; g2.ldres = l.c;
-    return launch_gemm(s, g2);
+    return gemm_on_route(ctx, s, g2);
 }
 
 // Snake1d -> Conv1d(c -> 1, k7) -> Tanh (modules.py:192-194); tanh is left out while the context's head_pretanh switch is on.
@@ -886,24 +882,24 @@ int run_local_trans(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x
         r.src = SRC_PLAIN; r.norm = NORM_LN; r.nw = l.ln1w; r.nb = l.ln1b; r.eps = 1e-5f;
         L3AC_TRY(launch_rows(s, r));
         GemmArgs g{};  // to_qkv (no bias)
-        g.a = ws.a; g.lda = dim; g.w = l.wqkv; g.w_img = ctx->img(l.wqkv); g.ldw = dim; g.c = ws.h; g.ldc = 3 * ctx->inner; g.m = rows; g.n = 3 * ctx->inner; g.k = dim;
+        g.a = ws.a; g.lda = dim; g.w = l.wqkv; g.ldw = dim; g.c = ws.h; g.ldc = 3 * ctx->inner; g.m = rows; g.n = 3 * ctx->inner; g.k = dim;
         g.epi = EPI_BIAS;
-        L3AC_TRY(launch_gemm(s, g));
+        L3AC_TRY(gemm_on_route(ctx, s, g));
         L3AC_TRY(launch_attention(s, ws.h, ws.a, w.bias_table, batch, frames, HEADS, ctx->dim_head, w.window));
         GemmArgs go{};  // to_out + residual (local_trans.py:45)
-        go.a = ws.a; go.lda = ctx->inner; go.w = l.wout; go.w_img = ctx->img(l.wout); go.ldw = ctx->inner; go.c = x; go.ldc = dim; go.m = rows; go.n = dim; go.k = ctx->inner;
+        go.a = ws.a; go.lda = ctx->inner; go.w = l.wout; go.ldw = ctx->inner; go.c = x; go.ldc = dim; go.m = rows; go.n = dim; go.k = ctx->inner;
         go.epi = EPI_BIAS_RES; go.res = x; go.ldres = dim;
-        L3AC_TRY(launch_gemm(s, go));
+        L3AC_TRY(gemm_on_route(ctx, s, go));
         r.nw = l.ln2w; r.nb = l.ln2b;  // FeedForward LayerNorm
         L3AC_TRY(launch_rows(s, r));
         GemmArgs f1{};  // Linear(dim, 2*inner) + GEGLU, value/gate tiles interleaved at upload
-        f1.a = ws.a; f1.lda = dim; f1.w = l.wff1; f1.w_img = ctx->img(l.wff1); f1.ldw = dim; f1.c = ws.h; f1.ldc = ctx->ff_pad; f1.m = rows; f1.n = ctx->ff_n; f1.k = dim;
+        f1.a = ws.a; f1.lda = dim; f1.w = l.wff1; f1.ldw = dim; f1.c = ws.h; f1.ldc = ctx->ff_pad; f1.m = rows; f1.n = ctx->ff_n; f1.k = dim;
         f1.epi = EPI_GEGLU; f1.n_out = ctx->ff_inner;
-        L3AC_TRY(launch_gemm(s, f1));
+        L3AC_TRY(gemm_on_route(ctx, s, f1));
         GemmArgs f2{};  // Linear(inner, dim) + residual (local_trans.py:46)
-        f2.a = ws.h; f2.lda = ctx->ff_pad; f2.w = l.wff2; f2.w_img = ctx->img(l.wff2); f2.ldw = ctx->ff_pad; f2.c = x; f2.ldc = dim; f2.m = rows; f2.n = dim; f2.k = ctx->ff_pad;
+        f2.a = ws.h; f2.lda = ctx->ff_pad; f2.w = l.wff2; f2.ldw = ctx->ff_pad; f2.c = x; f2.ldc = dim; f2.m = rows; f2.n = dim; f2.k = ctx->ff_pad;
         f2.epi = EPI_BIAS_RES; f2.res = x; f2.ldres = dim;
-        L3AC_TRY(launch_gemm(s, f2));
+        L3AC_TRY(gemm_on_route(ctx, s, f2));
     }
     return L3AC_OK;
 }

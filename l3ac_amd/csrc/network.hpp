@@ -22,9 +22,8 @@ struct ConvUnitW {  // modules.py:10-41
 struct DownW {  // modules.py:96-99 and local_trans.py:136: Conv1d(k = stride) [+ ChannelNorm]
     int cin = 0, cout = 0, stride = 1;
     const float *w, *b, *nw = nullptr, *nb = nullptr;
-    // the conv's weight [cout][stride * cin] as bf16x3 pieces for the DOWN form of up_fused_kernel, null when the geometry is not the kernel's
-    const unsigned char* fused_img = nullptr;
-    // ... and as fp32 in fragment order for down_exact_kernel (the default one-kernel form: the unfused route's bits)
+    // the conv's weight [cout][stride * cin] as fp32 in fragment order for down_exact_kernel (the one-kernel form: the unfused route's bits),
+    // null when the geometry is not the kernel's
     const unsigned char* exact_img = nullptr;
 };
 struct ConvK3W {  // modules.py:110, :150
@@ -70,9 +69,9 @@ struct TransCoopState {
     void* scratch = nullptr;        // device: partial slabs, private residual streams, arrival counters (trans_stack_coop_bytes())
     unsigned* fail_host = nullptr;  // pinned, device-visible host word: arrival polls that expired (cumulative); the kernel adds to it
     unsigned* fail_dev = nullptr;   // its device address
-    int enabled = 1;                // option "trans_coop"; cleared for good once a timeout has been seen
+    int enabled;                    // option "trans_coop"; cleared for good once a timeout has been seen
     int claim = 0, claim_slot = -1; // CUs of the device this context's cooperative launches may occupy (process-wide registry)
-    int timeout_ms = 250;           // option "coop_timeout_ms": how long an arrival poll waits
+    int timeout_ms;                 // option "coop_timeout_ms": how long an arrival poll waits
     int fault_part = -1;            // option "coop_test_fault" (test hook): workgroup that withholds its first arrival, -1 = none
     unsigned seen = 0;              // value of *fail_host the host has already acted on (fallback + report)
     unsigned count_base = 0;        // value of *fail_host at the last l3ac_coop_timeout_count(reset = 1)
@@ -96,26 +95,26 @@ struct l3ac_ctx {
     unsigned char* img_arena = nullptr;
     size_t img_bytes = 0;
     std::unordered_map<const float*, const unsigned char*> split_img;
-    // Route switches are PER CONTEXT (a flip never reaches another context's calls or captured graphs).  gemm_split: the large
-    // channel contractions on the bf16 matrix cores through exact bf16x3 operand splits (default) or everything on the fp32 MFMA
-    // instruction; head_pretanh (validation): the output head stores its value before the final tanh.
-    bool gemm_split = true, head_pretanh = false;
-    // which fused kernel takes the narrow ConvUnits (C <= 48) on the split route: conv_unit_ring_kernel (16 frames per wave, LDS-DMA
-    // weight ring) or conv_unit_split_kernel (32 frames per wave, chunk barriers); l3ac_ctx_set_option(ctx, "narrow_ring", 0 / 1)
+    // Route switches are PER CONTEXT (a flip never reaches another context's calls or captured graphs): the options of capi.hip's table
+    // (l3ac_ctx_set_option), which also holds their defaults: l3ac_create sets every one from it.
+    // gemm_split: the large channel contractions on the bf16 matrix cores through exact bf16x3 operand splits or everything on the fp32
+    // MFMA instruction; head_pretanh (validation): the output head stores its value before the final tanh.
+    int gemm_split, head_pretanh;
+    // batch kernels that keep two workgroups per CU resident (conv_unit_wide_kernel<96>, the LegacyUnits) hand their units out by a counter
+    // instead of equal static shares: the workgroup dispatched first is served first by every SIMD and finishes its share early
+    int unit_counter;
     // the wide ConvUnits (C = 96 .. 256) of FEW frames — a streaming chunk — as two launches over (frame tiles x channel slices) instead of
     // the fused kernel, whose waves own their frames end to end (conv_unit_wide.hip, 'the SLICED form'; the same bits)
-    // batch kernels that keep two workgroups per CU resident (conv_unit_wide_kernel<96>) hand their units out by a counter instead of equal
-    // static shares: the workgroup dispatched first is served first by every SIMD and finishes its share early (option "unit_counter")
-    int unit_counter = 1;
-    int wide_sliced = 1;  // 0: never, 1: where it is faster (up to 256 frame tiles of 16: measured), 2: wherever the form exists (the same today; tests)
-    int narrow_ring = 1;  // 0: conv_unit_split_kernel everywhere, 1: the ring kernel where it is faster (C = 48), 2: wherever it exists (C = 24 too)
-    // encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm) in one kernel on the bf16x3 route (the DOWN form of
-    // up_fused_kernel) instead of a small-N fp32-MFMA GEMM + row kernel: option "down_fused" / env L3AC_DOWN_FUSED.  Default 0: it is
-    // 0.12 ms faster at 256 clips and as accurate, but a different rounding of the encoder's first layers, and of the tokens compared
-    // with the oracle so far one (stress weights, 1.9e-6 of a rounding boundary) changes sides with it — DESIGN.md section 4.
-    // Round 6: value 2 (the DEFAULT) = down_exact_kernel, the same fusion with the unfused route's arithmetic bit for bit (exact fp32 MFMA
-    // chain in gemm_f32_kernel's k order, row_kernel's ChannelNorm tree) on BOTH GEMM routes; 1 = the bf16x3 form; 0 = GEMM + row kernel.
-    int down_fused = 2;
+    int wide_sliced;  // 0: never, 1: where it is faster (up to 256 frame tiles of 16: measured), 2: wherever the form exists (the same today; tests)
+    // which fused kernel takes the narrow ConvUnits (C <= 48) on the split route: conv_unit_ring_kernel (16 frames per wave, LDS-DMA
+    // weight ring) or conv_unit_split_kernel (32 frames per wave, chunk barriers)
+    int narrow_ring;  // 0: conv_unit_split_kernel everywhere, 1: the ring kernel where it is faster (C = 48), 2: wherever it exists (C = 24 too)
+    // encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm): 2 = down_exact_kernel, one kernel with the arithmetic of
+    // the two it replaces bit for bit (exact fp32 MFMA chain in gemm_f32_kernel's k order, row_kernel's ChannelNorm tree), on both GEMM
+    // routes; 0 = fp32-MFMA GEMM + row kernel.  (1, the bf16x3 form of round 4, was retired: DESIGN.md section 4.)
+    int down_fused;
+    int gemm_w256;      // GemmArgs::w256 of this context's products
+    int unit_chunk_mb;  // unfused C = 512 ConvUnits: target size of the hidden tensor per clip group (0 = the whole batch)
     const unsigned char* img(const float* w) const {  // null on the exact route: launch_gemm then takes the fp32 kernel
         if (!gemm_split) return nullptr;
         auto it = split_img.find(w);
@@ -202,9 +201,8 @@ int trans_coop_claimed_on_device(int device);  // -1: bad ordinal
 bool up_fused_supported(int cin, int cout);
 std::vector<unsigned char> up_fused_image(const float* w, int cin, int cout);  // w [cout][cin]
 int launch_up_fused(hipStream_t s, const EnhW& e, const UpW& w, const float* x, const float* yi, const float* stats, float* y, int batch, int frames);
-// encoder down layer (Conv1d(k = stride) + ChannelNorm) in the same kernel's DOWN form
-bool down_fused_supported(int cin, int stride, int cout);
-int launch_down_fused(hipStream_t s, const DownW& w, const float* x, float* y, int batch, int frames_out);
+// encoder down layer (Conv1d(k = stride) + ChannelNorm) in one kernel, x [batch][frames_out * stride][cin] -> y [batch][frames_out][cout]
+bool down_exact_supported(int cin, int stride, int cout);
 std::vector<unsigned char> down_exact_image(const float* w, int k, int cout);
 int launch_down_exact(hipStream_t s, const DownW& w, const float* x, float* y, int batch, int frames_out);
 // fused LegacyUnit / head (kernels/last_block.hip); x must not alias y

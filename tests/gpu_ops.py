@@ -141,8 +141,9 @@ def gemm(a, w, bias):
     return c
 
 
-def gemm_split(a, w, bias):
-    """bf16x3 split-operand GEMM through the C ABI: builds the weight image on the device, then multiplies."""
+def gemm_split(a, w, bias, w256=None):
+    """bf16x3 split-operand GEMM through the C ABI: builds the weight image on the device, then multiplies.  w256: which batch products
+    take gemm_split_kernel_w256 (0 / 1 / 2, l3ac_gemm_split_f32_at); None: as a new context's option "gemm_w256" would."""
     lib = _capi.load_library()
     m, k = a.shape
     n = w.shape[0]
@@ -151,8 +152,11 @@ def gemm_split(a, w, bias):
     img = torch.empty((nbytes,), dtype=torch.uint8, device=a.device)
     c = torch.empty((m, n), dtype=torch.float32, device=a.device)
     _capi.check(lib.l3ac_gemm_split_image(w.data_ptr(), n, k, img.data_ptr(), _stream(a.device)))
-    _capi.check(lib.l3ac_gemm_split_f32(a.data_ptr(), a.stride(0), img.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                        c.data_ptr(), n, m, n, k, _stream(a.device)))
+    args = (a.data_ptr(), a.stride(0), img.data_ptr(), bias.data_ptr() if bias is not None else None, c.data_ptr(), n, m, n, k)
+    if w256 is None:
+        _capi.check(lib.l3ac_gemm_split_f32(*args, _stream(a.device)))
+    else:
+        _capi.check(lib.l3ac_gemm_split_f32_at(*args, w256, _stream(a.device)))
     torch.cuda.synchronize()
     return c
 

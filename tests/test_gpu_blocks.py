@@ -108,21 +108,42 @@ def test_gemm_split_forms_return_the_same_bits():
 
 def test_gemm_split_w256_returns_the_same_bits():
     """Round 6: gemm_split_kernel_w256 (one wave per SIMD, 192 x 256 per workgroup) takes the long-K light-epilogue batch products by default
-    (L3AC_GEMM_W256=1) and every eligible shape with =2 — among them the snake + GRN epilogue of the C = 512 stage's first product, which the
-    default never sends there.  The switch is read once per process: one subprocess per value, and every digest (ragged row counts, both
-    weight shapes, a 256-column weight, the whole C = 512 ConvUnit) must equal the old kernel's (=0)."""
-    import json
-    import os
-    import subprocess
-    import sys
-    outs = {}
-    for mode in ("0", "1", "2"):
-        env = dict(os.environ, L3AC_GEMM_W256=mode)
-        r = subprocess.run([sys.executable, str(Path(__file__).resolve().parent / "w256_digest.py")], capture_output=True, text=True, env=env, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[mode] = json.loads(r.stdout.strip().splitlines()[-1])
-    print(f"[gemm_split_w256] digests: {outs['0']}")
-    assert outs["1"] == outs["0"] and outs["2"] == outs["0"], {k: (outs["0"][k], outs["1"][k], outs["2"][k]) for k in outs["0"] if len({outs[m][k] for m in outs}) > 1}
+    (option "gemm_w256" = 1) and every eligible shape with 2 — among them the snake + GRN epilogue of the C = 512 stage's first product, which
+    the default never sends there.  Every digest under 1 and 2 must equal the old kernel's (0): raw products with row counts that are not
+    multiples of its 192-row panels, both weight shapes of the C = 512 stage and a 256-column weight (through l3ac_gemm_split_f32_at), and the
+    whole C = 512 ConvUnit (its first product carries the snake + GRN epilogue, its second the residual) on one context."""
+    import hashlib
+
+    def sha(t):
+        return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
+
+    outs = {mode: {} for mode in (0, 1, 2)}
+    g = torch.Generator().manual_seed(7)
+    for m, n, k in ((24480 + 77, 512, 2048), (21600, 512, 1024), (46080 + 5, 256, 512), (33000, 2048, 512), (193 * 150, 768, 64)):
+        a = torch.randn(m, k, generator=g) * torch.pow(10.0, torch.randint(-2, 2, (m, 1), generator=g).float())
+        w = torch.randn(n, k, generator=g) * 0.1
+        b = torch.randn(n, generator=g)
+        a, w, b = a.cuda(), w.cuda(), b.cuda()
+        for mode in outs:
+            outs[mode][f"gemm {m}x{n}x{k}"] = sha(G.gemm_split(a, w, b, w256=mode))
+    codec = l3ac_amd.get_model("1kbps", synthetic_seed=0)
+    codec.network.to(device="cuda").eval()
+    ctx = codec.network.context()
+    ctx.reserve(256, 16000)
+    s = torch.cuda.current_stream().cuda_stream
+    for batch, frames in ((136, 180), (131, 97)):
+        x = torch.randn(batch, frames, 512, generator=g).cuda()
+        for mode in outs:
+            y = torch.empty_like(x)
+            ctx.set_option("gemm_w256", mode)
+            try:
+                _capi.check(ctx.lib.l3ac_op_conv_unit(ctx.handle, b"decoder.blocks.1.2.module", x.data_ptr(), batch, frames, y.data_ptr(), s))
+                torch.cuda.synchronize()
+            finally:
+                ctx.set_option("gemm_w256", 1)
+            outs[mode][f"unit512 {batch}x{frames}"] = sha(y)
+    print(f"[gemm_split_w256] digests: {outs[0]}")
+    assert outs[1] == outs[0] and outs[2] == outs[0], {k: (outs[0][k], outs[1][k], outs[2][k]) for k in outs[0] if len({outs[m][k] for m in outs}) > 1}
 
 
 def test_gemm_f32_forms_return_the_same_bits():
@@ -499,12 +520,12 @@ def test_conv_units_wide_scratch_on_a_fresh_context():
     assert float((wave.cpu() - wave_ref).abs().max()) < 2e-3
 
 
-def test_down_and_k3_layers(tiny, full):
+def test_down_layer_forms_and_k3_layers(tiny, full):
     import torch.nn.functional as F
     for (codec, mc, w), cases in ((tiny, [("encoder.blocks.2", 8, 16, 2, 66), ("encoder.blocks.4", 16, 24, 3, 66)]),
                                   (full, [("encoder.blocks.2", 24, 48, 6, 600), ("encoder.blocks.6", 96, 192, 3, 90),
-                                          # the DOWN form of up_fused_kernel (conv + ChannelNorm in one kernel): both widths it takes at
-                                          # 1kbps, output lengths around its 16-frame tiles (1, 15, 16, 17, 33) and whole clips
+                                          # down_exact_kernel (conv + ChannelNorm in one kernel): both widths it takes at 1kbps, output
+                                          # lengths around its 16-frame tiles (1, 15, 16, 17, 33) and whole clips
                                           ("encoder.blocks.4", 48, 96, 5, 5 * 33), ("encoder.blocks.4", 48, 96, 5, 2700),
                                           ("encoder.blocks.2", 24, 48, 6, 6), ("encoder.blocks.2", 24, 48, 6, 6 * 15),
                                           ("encoder.blocks.2", 24, 48, 6, 6 * 16), ("encoder.blocks.2", 24, 48, 6, 6 * 17),
@@ -514,10 +535,10 @@ def test_down_and_k3_layers(tiny, full):
             ref = F.conv1d(x, w[f"{block}.0.weight"], w[f"{block}.0.bias"], stride=s)
             ref = O.channel_norm_first(ref, w[f"{block}.1.weight"], w[f"{block}.1.bias"])
             ctx = codec.network.context()
-            # option "down_fused": 0 = the GEMM + row kernel, 1 = the bf16x3 one-kernel form, 2 (default, round 6) = down_exact_kernel, whose
-            # results must be those of 0 BIT FOR BIT (the exact fp32 MFMA chain in gemm_f32_kernel's k order, row_kernel's ChannelNorm tree)
+            # option "down_fused": 0 = the GEMM + row kernel, 2 (default, round 6) = down_exact_kernel, whose results must be those of 0
+            # BIT FOR BIT (the exact fp32 MFMA chain in gemm_f32_kernel's k order, row_kernel's ChannelNorm tree)
             outs = {}
-            for fused in (0, 1, 2):
+            for fused in (0, 2):
                 ctx.set_option("down_fused", fused)
                 try:
                     got = G.op_block(ctx, "l3ac_op_down_layer", block, G.to_frames(x), (2, t // s, co))
@@ -1050,29 +1071,92 @@ def test_vq_argmin_graph_capture():
             assert torch.equal(out, eager[i]), f"n={n} set {i}"
 
 
+# every option of the context's table (capi.hip): (name, lowest, highest, default); flags (gemm_split, head_pretanh, trans_coop) store value != 0
+RANGED_OPTIONS = [("narrow_ring", 0, 2, 1), ("wide_sliced", 0, 2, 1), ("unit_counter", 0, 3, 1), ("coop_timeout_ms", 1, 20000, 250),
+                  ("down_fused", 0, 2, 2), ("gemm_w256", 0, 2, 1), ("unit_chunk_mb", 0, 65536, 192)]
+FLAG_OPTIONS = [("gemm_split", 1), ("head_pretanh", 0), ("trans_coop", 1)]
+
+
 def test_context_options_by_name(full):
-    """l3ac_ctx_set_option: the route switches by name belong to ONE context, unknown names are refused (L3AC_EINVAL with a
-    message naming the options) — among them the options retired in round 5 — and out-of-range values of `narrow_ring` are clamped."""
+    """l3ac_ctx_set_option / _get_option: the route switches by name belong to ONE context, unknown names are refused (L3AC_EINVAL with a
+    message naming the options) — among them the options retired in round 5, and the retired value 1 of `down_fused` — every option reads
+    back what was stored, and out-of-range values are clamped at both ends."""
     codec, mc, w = full
     ctx = codec.network.context()
     for name in ("no_such_option", "wide_narrow", "ring_geometry"):
-        with pytest.raises(RuntimeError, match="unknown option"):
+        with pytest.raises(RuntimeError, match="unknown option.*narrow_ring.*unit_chunk_mb"):
             ctx.set_option(name, 1)
+        with pytest.raises(RuntimeError, match="unknown option"):
+            ctx.get_option(name)
+    with pytest.raises(RuntimeError, match="retired.*DESIGN.md section 4"):
+        ctx.set_option("down_fused", 1)
+    assert ctx.get_option("down_fused") == 2
+    for name, _ in FLAG_OPTIONS:
+        before = ctx.get_option(name)
+        try:
+            for value, stored in ((0, 0), (1, 1), (7, 1), (-3, 1), (0, 0)):
+                ctx.set_option(name, value)
+                assert ctx.get_option(name) == stored, (name, value)
+        finally:
+            ctx.set_option(name, before)
+    for name, lo, hi, _ in RANGED_OPTIONS:
+        before = ctx.get_option(name)
+        try:
+            for value, stored in ((lo, lo), (hi, hi), (hi + 97, hi), (lo - 1, lo), (-(1 << 31), lo), ((1 << 31) - 1, hi)):
+                ctx.set_option(name, value)
+                assert ctx.get_option(name) == stored, (name, value)
+        finally:
+            ctx.set_option(name, before)
+    for name in ("coop_release_claim", "coop_test_fault"):  # (actions of set_option, not values)
+        with pytest.raises(RuntimeError, match="unknown option"):
+            ctx.get_option(name)
     other = l3ac_amd.get_model("1kbps", synthetic_seed=0)
     other.network.cuda().eval()
     octx = other.network.context()
     try:
         ctx.set_option("gemm_split", 0)
+        ctx.set_option("gemm_w256", 2)
+        ctx.set_option("unit_chunk_mb", 0)
         assert ctx.get_gemm_split() is False and octx.get_gemm_split() is True  # another context is untouched
+        assert (ctx.get_option("gemm_w256"), ctx.get_option("unit_chunk_mb")) == (2, 0)
+        assert (octx.get_option("gemm_w256"), octx.get_option("unit_chunk_mb")) == (1, 192)
     finally:
         ctx.set_option("gemm_split", 1)
+        ctx.set_option("gemm_w256", 1)
+        ctx.set_option("unit_chunk_mb", 192)
     block, c, b, t = "decoder.blocks.10.0.module", 48, 3, 333
     x = _rand((b, c, t), 77)
     ctx.set_option("narrow_ring", 2)
     try:
         ref = G.from_frames(G.op_block(ctx, "l3ac_op_conv_unit", block, G.to_frames(x), (b, t, c)))
         ctx.set_option("narrow_ring", 99)     # clamped to 2: still the ring kernel at this width
+        assert ctx.get_option("narrow_ring") == 2
         got = G.from_frames(G.op_block(ctx, "l3ac_op_conv_unit", block, G.to_frames(x), (b, t, c)))
     finally:
         ctx.set_option("narrow_ring", 1)
     assert torch.equal(got, ref)
+
+
+def test_context_options_start_from_the_environment(monkeypatch):
+    """An option's environment variable is read when a context is CREATED, as its initial value, under the rule of l3ac_ctx_set_option:
+    out-of-range values are clamped, the retired value 1 of `down_fused` makes the creation fail."""
+    def created(**env):
+        for k in ("L3AC_GEMM_SPLIT", "L3AC_TRANS_COOP", "L3AC_DOWN_FUSED", "L3AC_UNIT_COUNTER", "L3AC_GEMM_W256", "L3AC_UNIT_CHUNK_MB"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        codec = l3ac_amd.get_model(GOLDEN / "tiny.toml", synthetic_seed=3)
+        codec.network.to(device="cuda").eval()
+        return codec.network.context()
+
+    ctx = created()
+    for name, *_, default in RANGED_OPTIONS + FLAG_OPTIONS:
+        assert ctx.get_option(name) == default, name
+    for env, name, expected in (("L3AC_DOWN_FUSED", "down_fused", {"7": 2, "0": 0, "-2": 0}),
+                                ("L3AC_UNIT_COUNTER", "unit_counter", {"4": 3, "-1": 0, "2": 2}),
+                                ("L3AC_GEMM_W256", "gemm_w256", {"5": 2, "0": 0}),
+                                ("L3AC_UNIT_CHUNK_MB", "unit_chunk_mb", {"0": 0, "96": 96, "1000000": 65536})):
+        for value, stored in expected.items():
+            assert created(**{env: value}).get_option(name) == stored, (env, value)
+    with pytest.raises(RuntimeError, match="L3AC_DOWN_FUSED.*down_fused = 1.*retired.*DESIGN.md section 4"):
+        created(L3AC_DOWN_FUSED="1")

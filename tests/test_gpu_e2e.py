@@ -320,7 +320,8 @@ def test_parity_under_trained_weight_statistics(tag):
             print(f"[index agreement {tag} {name}] {rep}")
             assert rep["single_step"] and rep["max_margin_of_mismatches"] < TAU
             # strict since round 6 (the arithmetic is deterministic on this hardware: the count is a property of the build): the bf16x3 down
-            # layers (L3AC_DOWN_FUSED=1), which move ONE stress_3kbps token across its boundary, fail here — profiles/r06/strict_gates.txt
+            # layers of round 4 (down_fused = 1, retired since), which moved ONE stress_3kbps token across its boundary, failed here —
+            # profiles/r06/strict_gates.txt
             assert rep["mismatches"] == OBSERVED_STRESS_MISMATCHES.get((tag, name), 0)
             wave = codec.decode_audio(indices=idx_ref.cuda()).cpu()
             err = (wave - wave_ref).abs()
@@ -340,20 +341,12 @@ def test_parity_under_trained_weight_statistics(tag):
     assert g_min >= 0.25 and torch.equal(ind_x["indices"], ind_f["indices"])
 
 
-# (round 5 needed this test to run after the stress test, which had to be the one to fill the session cache; round 6: the stress test
-# bypasses the cache for its hooked evaluation, so the order no longer matters)
-# option "down_fused": observed mismatches with the narrow encoder down layers in their one-kernel bf16x3 form (value 1)
-OBSERVED_DOWN_FUSED_MISMATCHES = {"1kbps": 0, "stress_3kbps": 1}
-
-
 @pytest.mark.parametrize("tag", ["1kbps", "stress_3kbps"])
-def test_index_agreement_with_fused_down_layers(tag):
-    """The encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm) have two one-kernel forms (context option
-    "down_fused").  Value 2, the DEFAULT since round 6 (down_exact_kernel), evaluates the arithmetic of the GEMM + row kernel it replaces
-    bit for bit: tokens AND q_feature of a whole encode equal those of value 0.  Value 1 (the bf16x3 form, round 4) is a different —
-    equally accurate — rounding of the encoder's first layers: the index contract holds with it (single-level flips within TAU of a
-    rounding boundary only) and what it costs is printed: on the stress weights the one decision that lies 1.9e-6 level units from its
-    boundary falls on the other side — which is why it never became the default, and what a strict gate must catch (profiles/r06/strict_gates.txt)."""
+def test_fused_down_layers_keep_the_encoder_bits(tag):
+    """The encoder down layers 24 -> 48 and 48 -> 96 (Conv1d(k = stride) + ChannelNorm) run in one kernel (context option "down_fused" = 2,
+    the DEFAULT since round 6: down_exact_kernel), which evaluates the arithmetic of the GEMM + row kernel it replaces (value 0) bit for
+    bit: tokens AND q_feature of a whole encode equal those of value 0, and the tokens keep the index contract against the oracle.
+    (Value 1, the bf16x3 form of round 4, moved one stress-weight token across its rounding boundary and was retired: DESIGN.md section 4.)"""
     from tests.helpers import structured_audio
     codec = _codec(tag, 0)
     mc = codec.network.mc
@@ -366,16 +359,13 @@ def test_index_agreement_with_fused_down_layers(tag):
     try:
         ctx.set_option("down_fused", 0)
         q_plain, plain = codec.encode_audio(audio.cuda())
-        ctx.set_option("down_fused", 1)
-        _, ind = codec.encode_audio(audio.cuda())
     finally:
         ctx.set_option("down_fused", 2)
     assert torch.equal(default["indices"], plain["indices"]) and torch.equal(q_default, q_plain), "down_exact_kernel changed the encoder's bits"
-    rep = index_agreement(ind["indices"].cpu().numpy(), idx_ref.numpy(), lat_ref.numpy(), mc.levels)
-    differ = int((ind["indices"] != plain["indices"]).sum())
-    print(f"[index agreement {tag} down_fused=1] {rep}; tokens that differ from the default form's: {differ}")
+    rep = index_agreement(default["indices"].cpu().numpy(), idx_ref.numpy(), lat_ref.numpy(), mc.levels)
+    print(f"[index agreement {tag} down_fused=2] {rep}")
     assert rep["single_step"] and rep["max_margin_of_mismatches"] < TAU
-    assert rep["mismatches"] <= OBSERVED_DOWN_FUSED_MISMATCHES[tag] + 1
+    assert rep["mismatches"] == 0
 
 
 # mismatches observed on the MI355X per (config, input set), both GEMM routes (round 3; every one a +-1 flip within TAU).  The one entry
