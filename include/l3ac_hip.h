@@ -148,6 +148,26 @@ int l3ac_encode(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t sample
 int l3ac_decode(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, int32_t batch, int32_t n_tok,
                 float* audio_out, void* stream);
 
+/* Ragged batches: clips of different lengths in one call.  Clip i's outputs are bit-identical to the
+ * same call on that clip alone, and zero after its own tokens / samples; what lies after its own length in the inputs is never
+ * read into its results, whatever it holds.  The per-clip lengths are HOST arrays of `batch` entries, read during the call (they
+ * pick launch forms) and handed to the device as kernel arguments: the caller may overwrite them as soon as the call returns,
+ * and a captured graph replays the lengths it was captured with.  No allocation once l3ac_reserve(batch, max_samples) has run.
+ * Refused (L3AC_EINVAL) on a context created with grn_exact = 1: its per-clip GRN norm would include the padding.
+ *
+ * l3ac_encode_ragged: audio [batch][max_samples] (row stride audio_stride); samples[i] in [1, max_samples].
+ *   q_feature / indices / level_indices as l3ac_encode with n_tok = ceil(max_samples / hop); clip i's first
+ *   ceil(samples[i] / hop) tokens are those of l3ac_encode on its samples[i] samples alone, the rest are zero. */
+int l3ac_encode_ragged(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t max_samples, int64_t audio_stride,
+                       const int32_t* samples, float* q_feature, int32_t* indices, float* level_indices, void* stream);
+
+/* l3ac_decode_ragged: q_feature [batch][max_tok][feature_dim] or (q_feature NULL) indices [batch][max_tok]; n_tok[i] in
+ *   [1, max_tok] with n_tok[i] * en_coder_compress_rate >= 2.  audio_out [batch][max_tok * hop]: clip i's first n_tok[i] * hop
+ *   samples are l3ac_decode of its first n_tok[i] tokens alone, the rest are zero.  Tokens after a clip's own never reach
+ *   l3ac_bad_index_count. */
+int l3ac_decode_ragged(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, int32_t batch, int32_t max_tok,
+                       const int32_t* n_tok, float* audio_out, void* stream);
+
 /* ---- quantiser kernels, context-free --------------------------------------------------------------- */
 
 /* Fused FSQ (vq/__init__.py:25-30 + vq/fsq.py:30-68, eval): x [n][feat] -> q_feature [n][feat], indices [n],

@@ -23,6 +23,7 @@ without the built extension, raises.
 """
 from __future__ import annotations
 
+import ctypes
 import logging
 import math
 import os
@@ -38,7 +39,7 @@ from .chunking import ChunkData, plan as _chunk_plan
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
-           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length"]
+           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -239,7 +240,7 @@ class L3AC:
         return int(sample_rate)
 
     @torch.no_grad()
-    def encode_audio(self, audio_data: torch.Tensor, validate: bool = False, sample_rate: Optional[int] = None):
+    def encode_audio(self, audio_data: torch.Tensor, validate: bool = False, sample_rate: Optional[int] = None, lengths=None):
         """audio (B, T) fp32 -> (q_feature (B, T_tok, C) fp32, {"indices": int32 (B, T_tok),
         "level_indices": fp32 (B, T_tok, D)}); the zero right-padding to a hop multiple happens in-kernel.
         ``sample_rate``: the rate of ``audio_data`` when it is not ``config.sample_rate``: the audio is first converted on the GPU,
@@ -247,11 +248,23 @@ class L3AC:
         ``validate=True`` synchronises before and after the call: it raises — without running anything — if an EARLIER, unvalidated
         call on the context lost a cooperative transformer launch to its time limit, and raises if a launch of THIS call did.  Without
         it a later call on the context returns L3AC_ECOOP once, after the fact and possibly several calls late (the entry check does
-        not synchronise: include/l3ac_hip.h, L3AC_ECOOP / l3ac_coop_timeout_pending)."""
+        not synchronise: include/l3ac_hip.h, L3AC_ECOOP / l3ac_coop_timeout_pending).
+        ``lengths``: B ints in 1..T, clips of different lengths in one call.  Samples at or after
+        ``lengths[i]`` in row i are ignored, whatever they hold; clip i's first ``ceil(lengths[i] / hop)`` tokens are bit-identical
+        to ``encode_audio(audio_data[i:i+1, :lengths[i]])``, the rest are zero, and the dict gains ``"lengths"``: those token counts
+        (int32, on the CPU).  With ``sample_rate`` the lengths count samples at that rate."""
+        if lengths is not None and audio_data.dim() != 2:
+            raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
+        lens = None if lengths is None else ragged_lengths(lengths, audio_data.shape[0], audio_data.shape[1], "lengths")
         ctx = self._check_input(audio_data, "audio_data")
         if audio_data.dim() != 2:
             raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
         rate = self._rate(sample_rate)
+        if rate is not None and lens is not None:
+            # each clip is converted as it would be alone: its zero padding, not its neighbour's samples, after its end
+            keep = torch.arange(audio_data.shape[1], device=audio_data.device)[None, :] < torch.tensor(lens, device=audio_data.device)[:, None]
+            audio_data = torch.where(keep, audio_data.to(torch.float32), 0.0)
+            lens = [resample_length(rate, self.config.sample_rate, n) for n in lens]
         if rate is not None:
             audio_data = resample(audio_data, rate, self.config.sample_rate)
         audio = audio_data.to(torch.float32)
@@ -270,21 +283,33 @@ class L3AC:
             stream = torch.cuda.current_stream(dev).cuda_stream
             if validate:
                 self._coop_check_before(ctx, "encode_audio")
-            _capi.check(ctx.lib.l3ac_encode(ctx.handle, audio.data_ptr(), b, t, audio.stride(0) if b > 1 else t,
-                                            q_feature.data_ptr(), indices.data_ptr(), level_indices.data_ptr(), stream))
+            if lens is None:
+                _capi.check(ctx.lib.l3ac_encode(ctx.handle, audio.data_ptr(), b, t, audio.stride(0) if b > 1 else t,
+                                                q_feature.data_ptr(), indices.data_ptr(), level_indices.data_ptr(), stream))
+            else:
+                host = (ctypes.c_int32 * b)(*lens)
+                _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, audio.data_ptr(), b, t, audio.stride(0) if b > 1 else t, host,
+                                                       q_feature.data_ptr(), indices.data_ptr(), level_indices.data_ptr(), stream))
             if validate:
                 self._raise_on_coop_timeout(ctx, "encode_audio")
+        if lens is not None:
+            tok = torch.tensor([math.ceil(n / mc.hop_length) for n in lens], dtype=torch.int32)
+            return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": tok}
         return q_feature, {"indices": indices, "level_indices": level_indices}
 
     @torch.no_grad()
     def decode_audio(self, audio_feature: torch.Tensor = None, indices: torch.Tensor = None, validate: bool = False,
-                     sample_rate: Optional[int] = None) -> torch.Tensor:
+                     sample_rate: Optional[int] = None, lengths=None) -> torch.Tensor:
         """(B, T_tok, C) features, or int indices (B, T_tok) -> audio (B, T_tok * hop), not trimmed.
         ``sample_rate``: return the audio at this rate instead, exactly ``resample(decode_audio(...), config.sample_rate,
         sample_rate)``: (B, resample_length(config.sample_rate, sample_rate, T_tok * hop)), not trimmed either.
         Indices outside [0, codebook_size) — a corrupted or truncated token stream — are clamped into range and counted on
         the device (``codec.network.context().bad_index_count()``); with ``validate=True`` the call synchronises and raises
-        if this call met any — or if a cooperative transformer launch of this call timed out (as encode_audio)."""
+        if this call met any — or if a cooperative transformer launch of this call timed out (as encode_audio).
+        ``lengths``: B token counts in 1..T_tok (``encode_audio(..., lengths=...)[1]["lengths"]``): clip i's first
+        ``lengths[i] * hop`` samples are bit-identical to decoding its first ``lengths[i]`` tokens alone, the rest are zero; tokens
+        after a clip's own are ignored (never counted as bad indices).  With ``sample_rate`` each clip is converted as it would be
+        alone and is zero after ``resample_length(config.sample_rate, sample_rate, lengths[i] * hop)``."""
         src = audio_feature if audio_feature is not None else indices
         if src is None:
             raise ValueError("decode_audio needs audio_feature or indices")
@@ -303,7 +328,8 @@ class L3AC:
             idx = indices.to(torch.int32).contiguous()
             b, n_tok = idx.shape
             f_ptr, i_ptr, keep = None, idx.data_ptr(), idx
-        if n_tok * mc.en_coder_compress_rate < 2:
+        lens = None if lengths is None else ragged_lengths(lengths, b, n_tok, "lengths (tokens)")
+        if min(lens or [n_tok]) * mc.en_coder_compress_rate < 2:
             # reference behaviour: the first EnhanceBlock's InstanceNorm1d (tconv/__init__.py:36) raises on a single frame
             raise ValueError(f"Expected more than 1 spatial element when training, got input size torch.Size([{b}, 4, 1])")
         audio = torch.empty((b, n_tok * mc.hop_length), dtype=torch.float32, device=src.device)
@@ -312,7 +338,11 @@ class L3AC:
             before = ctx.bad_index_count() if validate and i_ptr is not None else 0  # cumulative counter: read, never reset here
             if validate:
                 self._coop_check_before(ctx, "decode_audio")
-            _capi.check(ctx.lib.l3ac_decode(ctx.handle, f_ptr, i_ptr, b, n_tok, audio.data_ptr(), stream))
+            if lens is None:
+                _capi.check(ctx.lib.l3ac_decode(ctx.handle, f_ptr, i_ptr, b, n_tok, audio.data_ptr(), stream))
+            else:
+                host = (ctypes.c_int32 * b)(*lens)
+                _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, b, n_tok, host, audio.data_ptr(), stream))
             if validate:
                 self._raise_on_coop_timeout(ctx, "decode_audio")
             if validate and i_ptr is not None:
@@ -320,7 +350,14 @@ class L3AC:
                 if bad:
                     raise ValueError(f"{bad} of {b * n_tok} indices lie outside [0, {mc.codebook_size}): corrupted token stream")
         del keep
-        return audio if rate is None else resample(audio, self.config.sample_rate, rate)
+        if rate is None:
+            return audio
+        audio = resample(audio, self.config.sample_rate, rate)
+        if lens is not None:  # each clip ends where its own converted samples end
+            ends = [resample_length(self.config.sample_rate, rate, n * mc.hop_length) for n in lens]
+            keep = torch.arange(audio.shape[1], device=audio.device)[None, :] < torch.tensor(ends, device=audio.device)[:, None]
+            audio = torch.where(keep, audio, 0.0)
+        return audio
 
 
     # ---- long audio (reference l3ac/codec.py:124-156, corrected: see l3ac_amd/chunking.py) ---------------------------
@@ -452,6 +489,26 @@ def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int) -> torch.Tensor:
         _capi.check(lib.l3ac_unpack_indices(src.data_ptr(), packed.shape[0], n_tok, bits, words, out.data_ptr(),
                                             torch.cuda.current_stream(packed.device).cuda_stream))
     return out
+
+
+def ragged_lengths(lengths, batch: int, limit: int, what: str = "lengths") -> list:
+    """``lengths=`` of encode_audio / decode_audio as B Python ints in 1..limit; raises ValueError (before any device work)
+    otherwise.  Accepts a sequence, a NumPy array or a tensor (a CUDA tensor is copied to the host)."""
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().reshape(-1).tolist()
+    try:
+        seq = list(lengths)
+        vals = [int(v) for v in seq]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a sequence of {batch} ints") from None
+    if any(float(v) != int(v) for v in seq):
+        raise ValueError(f"{what} must be integers")
+    if len(vals) != batch:
+        raise ValueError(f"{what}: {len(vals)} entries for a batch of {batch}")
+    bad = [v for v in vals if not 1 <= v <= limit]
+    if bad:
+        raise ValueError(f"{what}: {bad[0]} outside [1, {limit}]")
+    return vals
 
 
 def resample_length(orig_sr: int, target_sr: int, n_in: int) -> int:

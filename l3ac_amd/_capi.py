@@ -60,6 +60,8 @@ SIGNATURES = {
     "l3ac_hop_length": (_I32, [_P]),
     "l3ac_encode": (C.c_int, [_P, _P, _I32, _I32, _I64, _P, _P, _P, _P]),
     "l3ac_decode": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
+    "l3ac_encode_ragged": (C.c_int, [_P, _P, _I32, _I32, _I64, C.POINTER(_I32), _P, _P, _P, _P]),
+    "l3ac_decode_ragged": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(_I32), _P, _P]),
     "l3ac_fsq_forward": (C.c_int, [_P, _I64, _I32, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "l3ac_fsq_quantize_act": (C.c_int, [_P, _I64, _I32, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, _P]),
     "l3ac_fsq_decode": (C.c_int, [_P, _I64, _I32, C.POINTER(_I32), _I32, _P, _P, _P, _P]),

@@ -41,6 +41,7 @@ SOURCES = [
     "kernels/last_block.hip",
     "kernels/bitpack.hip",
     "kernels/up_fused.hip",
+    "kernels/ragged.hip",
     "kernels/resample.hip",
 ]
 

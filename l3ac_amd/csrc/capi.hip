@@ -204,6 +204,37 @@ int set_checked(l3ac_ctx* ctx, const Option& o, int value, const char* who) {
     return L3AC_OK;
 }
 
+// ---- ragged batches -------------------------------------------------------------
+// The host's per-clip counts into the workspace's plan array, as kernel arguments (never through a staging buffer the next call could
+// overwrite while a copy is in flight: the caller may reuse its array at once, and a captured graph replays these values), and the
+// context's RaggedPlan pointing at them.  `samples` null: decode (n_tok * hop).
+int ragged_plan(l3ac_ctx* ctx, hipStream_t s, RaggedPlan& p, int batch, int max_tok, const int32_t* n_tok, const int32_t* samples) {
+    p.max_tok = max_tok;
+    p.n_tok.assign(n_tok, n_tok + batch);
+    p.order.resize(batch);
+    for (int i = 0; i < batch; ++i) p.order[i] = i;
+    std::stable_sort(p.order.begin(), p.order.end(), [&](int a, int b) { return p.n_tok[a] < p.n_tok[b]; });
+    std::vector<int> host((size_t)batch * RaggedPlan::plan_ints());
+    for (int i = 0; i < batch; ++i) {
+        host[i] = p.n_tok[i];
+        host[batch + i] = samples ? samples[i] : p.n_tok[i] * ctx->hop;
+        host[2 * batch + i] = p.order[i];
+    }
+    int* dev = ctx->ws.plan;
+    L3AC_TRY(launch_ragged_upload(s, dev, host.data(), (int)host.size()));
+    p.n_dev = dev;
+    p.samples_dev = dev + batch;
+    p.order_dev = dev + 2 * batch;
+    return L3AC_OK;
+}
+
+// sets ctx->rag for the scope of one call
+struct RaggedScope {
+    l3ac_ctx* ctx;
+    RaggedScope(l3ac_ctx* c, const RaggedPlan* p) : ctx(c) { ctx->rag = p; }
+    ~RaggedScope() { ctx->rag = nullptr; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -359,6 +390,87 @@ int l3ac_decode(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, i
     }
     int frames = 0;
     L3AC_TRY(run_en_decoder(ctx, s, batch, n_tok, &cur, &alt, &frames));
+    return run_decoder(ctx, s, batch, frames, &cur, &alt, audio_out);
+}
+
+// ragged batches: clip i of the batch gets the bits of clip i alone
+int l3ac_encode_ragged(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t max_samples, int64_t audio_stride,
+                       const int32_t* samples, float* q_feature, int32_t* indices, float* level_indices, void* stream) {
+    L3AC_ENTER_WS(ctx, stream);
+    L3AC_REQUIRE(audio && q_feature && indices, "l3ac_encode_ragged: null buffer");
+    L3AC_REQUIRE(samples, "l3ac_encode_ragged: null samples (a HOST array of batch lengths)");
+    L3AC_REQUIRE(batch > 0 && batch <= 65535 && max_samples > 0 && audio_stride >= max_samples, "l3ac_encode_ragged: bad shape");
+    L3AC_REQUIRE(!ctx->cfg.grn_exact, "l3ac_encode_ragged: this context evaluates the GRN normaliser per clip (grn_exact = 1), over "
+                 "all of a clip's frames: a ragged batch would include its padding; encode such clips one length at a time");
+    for (int i = 0; i < batch; ++i)
+        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "l3ac_encode_ragged: samples[%d] = %d outside [1, %d]", i, samples[i],
+                     max_samples);
+    hipStream_t s = (hipStream_t)stream;
+    L3AC_TRY(workspace_ensure_clip(ctx, batch, max_samples, s));
+    const int max_tok = (int)ceil_div64(max_samples, ctx->hop);
+    std::vector<int32_t> n_tok(batch);
+    for (int i = 0; i < batch; ++i) n_tok[i] = (int32_t)ceil_div64(samples[i], ctx->hop);
+    RaggedPlan plan;
+    L3AC_TRY(ragged_plan(ctx, s, plan, batch, max_tok, n_tok.data(), samples));
+    RaggedScope scope(ctx, &plan);
+    const int frames = max_tok * ctx->hop;
+    float* cur = ctx->ws.x0;
+    float* alt = ctx->ws.x1;
+    L3AC_TRY(run_encoder(ctx, s, audio, audio_stride, batch, max_samples, frames, &cur, &alt));
+    int n = 0;
+    L3AC_TRY(run_en_encoder(ctx, s, batch, frames / ctx->enc_rate, &cur, &alt, &n));
+    FsqArgs f{};
+    f.x = cur; f.n = (int64_t)batch * n; f.feat = ctx->cfg.feature_dim; f.n_levels = ctx->cfg.n_levels;
+    for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
+    f.w_in = ctx->q_win; f.b_in = ctx->q_bin; f.w_out = ctx->q_wout; f.b_out = ctx->q_bout;
+    f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices;
+    L3AC_TRY(launch_fsq(s, f));
+    // tokens after a clip's own are zero (int32 0 and fp32 0 share their bits)
+    L3AC_TRY(launch_ragged_mask(s, q_feature, batch, n, ctx->cfg.feature_dim, plan.n_dev, 1, n));
+    L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(indices), batch, n, 1, plan.n_dev, 1, n));
+    if (level_indices) L3AC_TRY(launch_ragged_mask(s, level_indices, batch, n, ctx->cfg.n_levels, plan.n_dev, 1, n));
+    return L3AC_OK;
+}
+
+int l3ac_decode_ragged(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, int32_t batch, int32_t max_tok,
+                       const int32_t* n_tok, float* audio_out, void* stream) {
+    L3AC_ENTER_WS(ctx, stream);
+    L3AC_REQUIRE((q_feature || indices) && audio_out, "l3ac_decode_ragged: null buffer");
+    L3AC_REQUIRE(n_tok, "l3ac_decode_ragged: null n_tok (a HOST array of batch token counts)");
+    L3AC_REQUIRE(batch > 0 && batch <= 65535 && max_tok > 0, "l3ac_decode_ragged: bad shape");
+    L3AC_REQUIRE(!ctx->cfg.grn_exact, "l3ac_decode_ragged: this context evaluates the GRN normaliser per clip (grn_exact = 1), over "
+                 "all of a clip's frames: a ragged batch would include its padding; decode such clips one length at a time");
+    const int rate = ctx->cfg.en_coder_compress_rate;
+    for (int i = 0; i < batch; ++i) {
+        L3AC_REQUIRE(n_tok[i] >= 1 && n_tok[i] <= max_tok, "l3ac_decode_ragged: n_tok[%d] = %d outside [1, %d]", i, n_tok[i], max_tok);
+        L3AC_REQUIRE((int64_t)n_tok[i] * rate >= 2, "l3ac_decode_ragged: n_tok[%d] = %d: a clip needs n_tok * en_coder_compress_rate "
+                     ">= 2 frames (the first EnhanceBlock's InstanceNorm)", i, n_tok[i]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    L3AC_TRY(workspace_ensure_clip(ctx, batch, max_tok * ctx->hop, s));
+    RaggedPlan plan;
+    L3AC_TRY(ragged_plan(ctx, s, plan, batch, max_tok, n_tok, nullptr));
+    RaggedScope scope(ctx, &plan);
+    float* cur = ctx->ws.x0;
+    float* alt = ctx->ws.x1;
+    const int64_t n = (int64_t)batch * max_tok;
+    const int feat = ctx->cfg.feature_dim;
+    if (q_feature) {
+        L3AC_HIP_CHECK(hipMemcpyAsync(cur, q_feature, (size_t)n * feat * sizeof(float), hipMemcpyDeviceToDevice, s));
+        L3AC_TRY(launch_ragged_mask(s, cur, batch, max_tok, feat, plan.n_dev, 1, max_tok));
+    } else {  // tokens after a clip's own become index 0 first: they never reach bad_index_count
+        int32_t* idx = reinterpret_cast<int32_t*>(ctx->ws.a);
+        L3AC_HIP_CHECK(hipMemcpyAsync(idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(idx), batch, max_tok, 1, plan.n_dev, 1, max_tok));
+        FsqArgs f{};
+        f.idx_in = idx; f.n = n; f.feat = feat; f.n_levels = ctx->cfg.n_levels;
+        for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
+        f.w_out = ctx->q_wout; f.b_out = ctx->q_bout; f.q_feature = cur;
+        f.bad_count = ctx->bad_index_count;
+        L3AC_TRY(launch_fsq(s, f));
+    }
+    int frames = 0;
+    L3AC_TRY(run_en_decoder(ctx, s, batch, max_tok, &cur, &alt, &frames));
     return run_decoder(ctx, s, batch, frames, &cur, &alt, audio_out);
 }
 

@@ -120,16 +120,24 @@ struct FirstBlockW {
     const float* b2;   // [d0]
     int d0;
 };
+// Per-clip bounds of a ragged batch (kernels/ragged.hip), device arrays: clip b has n[b] * mult of the
+// launch's `frames` (and, for the first block, samples[b] of its `samples`); null = every clip has them all (the plain kernels)
+struct RaggedClips {
+    const int* n = nullptr;
+    int mult = 1;
+    const int* samples = nullptr;
+};
 int launch_first_block(hipStream_t s, const FirstBlockW& w, const float* audio, int64_t audio_stride, int batch,
-                       int samples, int frames, float* y);
+                       int samples, int frames, float* y, const RaggedClips* rc = nullptr);
 
 // EnhanceBlock helpers (tconv/__init__.py:30-44)
 struct EnhanceW {
     const float* tw;  // trend convs [4][7]
     const float* tb;  // [4]
 };
-int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi);
-int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats);
+int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi,
+                            const RaggedClips* rc = nullptr);
+int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats, const RaggedClips* rc = nullptr);
 
 // output head (modules.py:190-195 after the Snake1d): conv 24 -> 1 k7 pad 3, tanh
 // pretanh (validation, l3ac_ctx_set_head_pretanh): store the conv result BEFORE the final tanh
@@ -176,6 +184,20 @@ int64_t resample_bank_floats(const ResamplePlan& p);                     // 0 wh
 void resample_fill_bank(const ResamplePlan& p, float* bank);             // host: [up][2][KE] fp32, each tap rounded once from fp64
 int launch_resample(hipStream_t s, const float* x, int batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
                     const float* bank, float* y, int64_t y_stride);
+// ragged batches (kernels/ragged.hip): per-clip counts reach the device as kernel arguments, CAP values per launch
+struct RaggedUpload {
+    static constexpr int CAP = 248;
+    int offset, n;
+    int vals[CAP];
+};
+int launch_ragged_upload(hipStream_t s, int* dst, const int* host, int n);
+// zero rows [n[b] * mult, n[b] * mult + width) of each clip of x [batch][frames][c] (clipped to frames)
+int launch_ragged_mask(hipStream_t s, float* x, int batch, int frames, int c, const int* n, int mult, int width);
+// row n[b] * mult of each clip = row n[b] * mult - 1 (where it is inside the clip's frames)
+int launch_ragged_dup(hipStream_t s, float* x, int batch, int frames, int c, const int* n, int mult);
+// compact clip k <-> batch clip perm[k0 + k] for k < count: `rows` rows of c floats; clip strides in floats
+int launch_ragged_gather(hipStream_t s, const float* src, float* dst, const int* perm, int k0, int count, int rows, int c,
+                         int64_t batch_clip, int64_t compact_clip, bool scatter);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

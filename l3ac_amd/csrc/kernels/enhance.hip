@@ -17,8 +17,12 @@ namespace {
 constexpr int TILE = 256;
 constexpr int XH = 23;  // 3*5 (conv reach at dilation 5) + 4 (avg 9) + 4 (max 9)
 
+// RAGGED (a ragged batch): clip b's pools and convs end at its own last frame rn[b] * rmult — x at and after
+// it reads as 0, as do the pooled values there: the zero padding of the clip alone.  `frames` stays the batch's row count.
+template <bool RAGGED>
 __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w, const float* __restrict__ x,
-                                                               int frames, int c, float* __restrict__ yi) {
+                                                               int frames, int c, float* __restrict__ yi,
+                                                               const int* __restrict__ rn, int rmult) {
     __shared__ float xs[TILE + 2 * XH];
     __shared__ float mbuf[TILE + 30 + 8];
     __shared__ float pbuf[TILE + 30];
@@ -28,7 +32,7 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
     const float* clip = x + (int64_t)b * frames * c;
     for (int i = tid; i < TILE + 2 * XH; i += TILE) {
         const int u = t0 - XH + i;
-        xs[i] = (u >= 0 && u < frames) ? clip[(int64_t)u * c] : 0.f;
+        xs[i] = (u >= 0 && u < (RAGGED ? rn[b] * rmult : frames)) ? clip[(int64_t)u * c] : 0.f;
     }
     __syncthreads();
 
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
         for (int i = tid; i < m_len; i += TILE) {
             const int v = t0 - reach - hk + i;
             float m = 0.f;
-            if (v >= 0 && v < frames) {
+            if (v >= 0 && v < (RAGGED ? rn[b] * rmult : frames)) {
                 const int base = v - hk - (t0 - XH);
                 for (int s = 0; s < k; ++s) m = fmaxf(m, fabsf(xs[base + s]));
             }
@@ -60,11 +64,11 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
         for (int i = tid; i < TILE + 2 * reach; i += TILE) {
             const int u = t0 - reach + i;
             float pv = 0.f;
-            if (u >= 0 && u < frames) {
+            if (u >= 0 && u < (RAGGED ? rn[b] * rmult : frames)) {
                 float sum = 0.f;
                 for (int s = 0; s < k; ++s) {
                     const int v = u - hk + s;
-                    if (v >= 0 && v < frames) sum += mbuf[i + s];
+                    if (v >= 0 && v < (RAGGED ? rn[b] * rmult : frames)) sum += mbuf[i + s];
                 }
                 pv = sum / (float)k;
             }
@@ -82,13 +86,16 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
         *reinterpret_cast<float4*>(yi + ((int64_t)b * frames + t) * 4) = make_float4(out[0], out[1], out[2], out[3]);
 }
 
-// one block per clip: two-pass mean / biased variance over frames for the 4 branch channels
-__global__ __launch_bounds__(1024) void enhance_stats_kernel(const float* __restrict__ yi, int frames,
-                                                            float* __restrict__ stats) {
+// one block per clip: two-pass mean / biased variance over frames for the 4 branch channels (RAGGED: over the clip's own rn[b] * rmult
+// frames, summed in the order of the clip alone; `batch_frames` is the batch's row count)
+template <bool RAGGED>
+__global__ __launch_bounds__(1024) void enhance_stats_kernel(const float* __restrict__ yi, int batch_frames,
+                                                            float* __restrict__ stats, const int* __restrict__ rn, int rmult) {
     __shared__ float4 part[16];
     __shared__ float4 bc;
     const int b = blockIdx.x;
-    const float4* src = reinterpret_cast<const float4*>(yi) + (int64_t)b * frames;
+    const float4* src = reinterpret_cast<const float4*>(yi) + (int64_t)b * batch_frames;
+    const int frames = RAGGED ? rn[b] * rmult : batch_frames;
     auto block_sum = [&](float4 v) -> float4 {
         v = make_float4(wave_sum(v.x), wave_sum(v.y), wave_sum(v.z), wave_sum(v.w));
         __syncthreads();
@@ -155,18 +162,21 @@ __global__ __launch_bounds__(TILE) void head_kernel(const float* __restrict__ x,
 
 }  // namespace
 
-int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi) {
+int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi, const RaggedClips* rc) {
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && frames > 0, "enhance: bad shape");
-    ProfScope prof(s, "enhance_branches_kernel", 2.0 * (28.0 + 34.0) * batch * frames, 4.0 * 5.0 * batch * frames);
-    hipLaunchKernelGGL(enhance_branches_kernel, dim3((unsigned)ceil_div64(frames, TILE), (unsigned)batch), dim3(TILE), 0, s,
-                       w, x, frames, c, yi);
+    ProfScope prof(s, rc ? "enhance_branches_kernel<RAGGED>" : "enhance_branches_kernel", 2.0 * (28.0 + 34.0) * batch * frames,
+                   4.0 * 5.0 * batch * frames);
+    const dim3 grid((unsigned)ceil_div64(frames, TILE), (unsigned)batch);
+    if (rc) hipLaunchKernelGGL(enhance_branches_kernel<true>, grid, dim3(TILE), 0, s, w, x, frames, c, yi, rc->n, rc->mult);
+    else hipLaunchKernelGGL(enhance_branches_kernel<false>, grid, dim3(TILE), 0, s, w, x, frames, c, yi, nullptr, 1);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
 
-int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats) {
-    ProfScope prof(s, "enhance_stats_kernel", 16.0 * batch * frames, 32.0 * batch * frames);
-    hipLaunchKernelGGL(enhance_stats_kernel, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats);
+int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats, const RaggedClips* rc) {
+    ProfScope prof(s, rc ? "enhance_stats_kernel<RAGGED>" : "enhance_stats_kernel", 16.0 * batch * frames, 32.0 * batch * frames);
+    if (rc) hipLaunchKernelGGL(enhance_stats_kernel<true>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, rc->n, rc->mult);
+    else hipLaunchKernelGGL(enhance_stats_kernel<false>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, nullptr, 1);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }

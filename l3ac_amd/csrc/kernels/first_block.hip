@@ -84,10 +84,13 @@ __device__ __forceinline__ void first_block_trends(const FirstBlockW& w, const f
 
 // UNR: unroll of the 80-channel loop (1 for a batch: with 8 waves per SIMD the scalar weight loads are covered, and more registers
 // cost a wave of occupancy).
-template <int D0, int UNR>
+// RAGGED (a ragged batch): clip b's trends end at its own samples rs[b] and frames rn[b] * rmult, as in the
+// clip alone; `frames` stays the batch's row count.  (Both kernels.)
+template <int D0, int UNR, bool RAGGED>
 __global__ __launch_bounds__(TILE) void first_block_kernel(const FirstBlockW w, const float* __restrict__ audio,
                                                           int64_t audio_stride, int samples, int frames,
-                                                          float* __restrict__ y) {
+                                                          float* __restrict__ y, const int* __restrict__ rn, int rmult,
+                                                          const int* __restrict__ rs) {
     __shared__ float xs[TILE + 2 * HALO];
     __shared__ float mbuf[TILE + 6 + 44];
     __shared__ float pbuf[TILE + 6];
@@ -96,7 +99,8 @@ __global__ __launch_bounds__(TILE) void first_block_kernel(const FirstBlockW w, 
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * TILE;
     float h[20];
-    first_block_trends<TILE, TILE>(w, audio + (int64_t)b * audio_stride, t0, samples, frames, tid, tid, xs, mbuf, pbuf, h);
+    first_block_trends<TILE, TILE>(w, audio + (int64_t)b * audio_stride, t0, RAGGED ? rs[b] : samples, RAGGED ? rn[b] * rmult : frames,
+                                   tid, tid, xs, mbuf, pbuf, h);
 
     const int t = t0 + tid;
     if (t >= frames) return;
@@ -127,9 +131,10 @@ __global__ __launch_bounds__(TILE) void first_block_kernel(const FirstBlockW w, 
 // the hidden channels 20 j .. 20 j + 19 of the workgroup's frames (the GELU is the expensive part) into LDS, then every wave
 // accumulates ITS quarter of the output channels over all 80 hidden channels in the same order as the kernel above: per output the
 // same fused multiply-adds in the same order, the same bits.  The trend branches are computed by all four waves (2 % of the work).
-template <int D0>
+template <int D0, bool RAGGED>
 __global__ __launch_bounds__(256) void first_block_split_kernel(const FirstBlockW w, const float* __restrict__ audio, int64_t audio_stride, int samples,
-                                                                int frames, float* __restrict__ y) {
+                                                                int frames, float* __restrict__ y, const int* __restrict__ rn, int rmult,
+                                                                const int* __restrict__ rs) {
     constexpr int FT = 64, DP = D0 / 4;
     static_assert(D0 % 8 == 0, "two floats per store");
     __shared__ float xs[FT + 2 * HALO];
@@ -142,7 +147,8 @@ __global__ __launch_bounds__(256) void first_block_split_kernel(const FirstBlock
     const int b = blockIdx.y;
     const int t0 = blockIdx.x * FT;
     float h[20];
-    first_block_trends<FT, 256>(w, audio + (int64_t)b * audio_stride, t0, samples, frames, tid, f, xs, mbuf, pbuf, h);
+    first_block_trends<FT, 256>(w, audio + (int64_t)b * audio_stride, t0, RAGGED ? rs[b] : samples, RAGGED ? rn[b] * rmult : frames, tid, f,
+                                xs, mbuf, pbuf, h);
 #pragma unroll 4
     for (int oo = 0; oo < 20; ++oo) {
         const int o = 20 * part + oo;
@@ -175,10 +181,13 @@ __global__ __launch_bounds__(256) void first_block_split_kernel(const FirstBlock
 
 // w.w2 is expected TRANSPOSED: [81][d0] (done once at weight upload).
 int launch_first_block(hipStream_t s, const FirstBlockW& w, const float* audio, int64_t audio_stride, int batch,
-                       int samples, int frames, float* y) {
+                       int samples, int frames, float* y, const RaggedClips* rc) {
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && frames >= samples && samples > 0, "first_block: bad shape");
     const dim3 grid((unsigned)ceil_div64(frames, TILE), (unsigned)batch);
-    ProfScope prof(s, "first_block_kernel", 2.0 * (140.0 + 1600.0 + 81.0 * w.d0 + 164.0) * batch * frames,
+    const int* rn = rc ? rc->n : nullptr;
+    const int* rs = rc ? rc->samples : nullptr;
+    const int rmult = rc ? rc->mult : 1;
+    ProfScope prof(s, rc ? "first_block_kernel<RAGGED>" : "first_block_kernel", 2.0 * (140.0 + 1600.0 + 81.0 * w.d0 + 164.0) * batch * frames,
                    4.0 * ((double)batch * samples + (double)batch * frames * w.d0));
     // few clips: four threads per frame (first_block_split_kernel), up to four 64-frame workgroups per CU
     const dim3 grid_split((unsigned)ceil_div64(frames, 64), (unsigned)batch);
@@ -186,8 +195,18 @@ int launch_first_block(hipStream_t s, const FirstBlockW& w, const float* audio, 
     switch (w.d0) {
 #define L3AC_FB_CASE(D)                                                                                                       \
     case D:                                                                                                                   \
-        if (few) hipLaunchKernelGGL((first_block_split_kernel<D>), grid_split, dim3(256), 0, s, w, audio, audio_stride, samples, frames, y); \
-        else hipLaunchKernelGGL((first_block_kernel<D, 1>), grid, dim3(TILE), 0, s, w, audio, audio_stride, samples, frames, y);    \
+        if (rc && few)                                                                                                        \
+            hipLaunchKernelGGL((first_block_split_kernel<D, true>), grid_split, dim3(256), 0, s, w, audio, audio_stride, samples,   \
+                               frames, y, rn, rmult, rs);                                                                     \
+        else if (rc)                                                                                                          \
+            hipLaunchKernelGGL((first_block_kernel<D, 1, true>), grid, dim3(TILE), 0, s, w, audio, audio_stride, samples, frames, y, \
+                               rn, rmult, rs);                                                                                \
+        else if (few)                                                                                                         \
+            hipLaunchKernelGGL((first_block_split_kernel<D, false>), grid_split, dim3(256), 0, s, w, audio, audio_stride, samples,  \
+                               frames, y, rn, rmult, rs);                                                                     \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((first_block_kernel<D, 1, false>), grid, dim3(TILE), 0, s, w, audio, audio_stride, samples, frames, y, \
+                               rn, rmult, rs);                                                                                \
         break
         L3AC_FB_CASE(8);
         L3AC_FB_CASE(16);

@@ -533,6 +533,8 @@ void network_free(l3ac_ctx* ctx) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (w.plan) (void)hipFree(w.plan);
+    w.plan = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -573,9 +575,12 @@ int workspace_ensure(l3ac_ctx* ctx, size_t x_floats, size_t a_floats, size_t h_f
     if (batch > w.b_cap) {
         L3AC_TRY(free_buf(w.stats));
         L3AC_TRY(free_buf(w.sumsq));
+        if (w.plan) L3AC_HIP_CHECK(hipFree(w.plan));
+        w.plan = nullptr;
         w.b_cap = 0;
         L3AC_HIP_CHECK(hipMalloc((void**)&w.stats, (batch * 8 + 64) * sizeof(float)));
         L3AC_HIP_CHECK(hipMalloc((void**)&w.sumsq, (batch + 64) * sizeof(float)));
+        L3AC_HIP_CHECK(hipMalloc((void**)&w.plan, (batch * RaggedPlan::plan_ints() + 64) * sizeof(int)));
         w.b_cap = batch;
     }
     return L3AC_OK;
@@ -653,6 +658,18 @@ static int gemm_on_route(const l3ac_ctx* ctx, hipStream_t s, GemmArgs g) {
     return launch_gemm(s, g);
 }
 
+// A ragged call (ctx->rag): zero `width` rows after each clip's last frame of x [batch][frames][c] — the zero
+// padding the next op, which reads up to `width` frames ahead, sees in the clip alone; duplicate each clip's last frame into the row
+// after it ahead of a linear upsampling.  Neither launches anything on the plain path.
+static int rag_mask(const l3ac_ctx* ctx, hipStream_t s, float* x, int batch, int frames, int c, int width) {
+    const RaggedPlan* r = ctx->rag;
+    return r ? launch_ragged_mask(s, x, batch, frames, c, r->n_dev, frames / r->max_tok, width) : L3AC_OK;
+}
+static int rag_dup(const l3ac_ctx* ctx, hipStream_t s, float* x, int batch, int frames, int c) {
+    const RaggedPlan* r = ctx->rag;
+    return r ? launch_ragged_dup(s, x, batch, frames, c, r->n_dev, frames / r->max_tok) : L3AC_OK;
+}
+
 static int run_conv_unit_rows(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames) {
     const int64_t rows = (int64_t)batch * frames;
     Workspace& ws = ctx->ws;
@@ -683,8 +700,11 @@ int run_conv_units(l3ac_ctx* ctx, hipStream_t s, const std::vector<ConvUnitW>& u
                    int frames) {
     if (units.empty()) return L3AC_OK;
     const bool fused = (!ctx->cfg.grn_exact && conv_unit_fused_supported(units[0].c)) || use_wide(ctx, units[0]);
-    if (fused || units.size() == 1) {
-        for (const ConvUnitW& u : units) L3AC_TRY(conv_unit_step(ctx, s, u, cur, alt, batch, frames));
+    if (fused || units.size() == 1 || ctx->rag) {
+        for (const ConvUnitW& u : units) {
+            L3AC_TRY(rag_mask(ctx, s, *cur, batch, frames, u.c, 3));  // dw_conv k7
+            L3AC_TRY(conv_unit_step(ctx, s, u, cur, alt, batch, frames));
+        }
         return L3AC_OK;
     }
     const int group = conv_unit_group(ctx, units[0], batch, frames);
@@ -753,8 +773,9 @@ int run_conv_k3(l3ac_ctx* ctx, hipStream_t s, const ConvK3W& w, const float* x, 
 
 int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, float* y, int batch, int frames) {
     Workspace& ws = ctx->ws;
-    L3AC_TRY(launch_enhance_branches(s, w.t, x, batch, frames, w.c, ws.yi));
-    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats));
+    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
+    L3AC_TRY(launch_enhance_branches(s, w.t, x, batch, frames, w.c, ws.yi, ctx->rag ? &rc : nullptr));
+    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr));
     RowArgs r{};
     r.x = x; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = frames; r.c = w.c;
     r.src = SRC_GATE; r.norm = NORM_NONE; r.yi = ws.yi; r.stats = ws.stats; r.in_w = w.in_w; r.in_b = w.in_b;
@@ -767,6 +788,7 @@ int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tm
     g.a = x; g.lda = w.cin; g.w = w.w; g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
     L3AC_TRY(gemm_on_route(ctx, s, g));
+    L3AC_TRY(rag_dup(ctx, s, tmp, batch, frames, w.cout));
     RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
     r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
     r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
@@ -798,10 +820,16 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
         return run_up(ctx, s, w, gated, tmp, y, batch, frames);
     }
     Workspace& ws = ctx->ws;
-    L3AC_TRY(launch_enhance_branches(s, e.t, x, batch, frames, e.c, ws.yi));
-    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats));
-    if (use_up_fused(ctx, w) && x != y)  // gate, conv, upsample and ChannelNorm in one kernel; it reads x while it writes y
+    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
+    L3AC_TRY(launch_enhance_branches(s, e.t, x, batch, frames, e.c, ws.yi, ctx->rag ? &rc : nullptr));
+    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr));
+    if (use_up_fused(ctx, w) && x != y) {  // gate, conv, upsample and ChannelNorm in one kernel; it reads x while it writes y
+        // ragged: the kernel's upsampling clamps at the batch's last frame; with the frame after each clip's last a copy of it (x and yi:
+        // the gate and the 1x1 conv are per frame) its lerp gives the clamped form's l0 * x[n - 1] + l1 * x[n - 1]
+        L3AC_TRY(rag_dup(ctx, s, x, batch, frames, e.c));
+        L3AC_TRY(rag_dup(ctx, s, ws.yi, batch, frames, 4));
         return launch_up_fused(s, e, w, x, ws.yi, ws.stats, y, batch, frames);
+    }
     L3AC_REQUIRE(tmp != nullptr, "enhance_up: scratch missing");
     GemmArgs g{};  // gate (tconv/__init__.py:35-44) + 1x1 conv (modules.py:161)
     g.a = x; g.lda = w.cin; g.w = w.w; g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
@@ -809,6 +837,7 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     g.gate_yi = ws.yi; g.gate_stats = ws.stats; g.gate_in_w = e.in_w; g.gate_in_b = e.in_b; g.gate_w = e.gate_w; g.gate_b = e.gate_b;
     g.gate_frames = frames;
     L3AC_TRY(launch_gemm(s, g));  // (not gemm_on_route: the gated A operand exists in the fp32 kernel only)
+    L3AC_TRY(rag_dup(ctx, s, tmp, batch, frames, w.cout));
     RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
     r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
     r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
@@ -856,12 +885,15 @@ int run_last_block(l3ac_ctx* ctx, hipStream_t s, float* x, float* audio, int bat
     float* cur = x;
     float* alt = last_block_fused(ctx) ? ctx->ws.a : x;
     for (const LegacyW& l : ctx->legacy) {
+        L3AC_TRY(rag_mask(ctx, s, cur, batch, frames, l.c, 3 * l.dil));  // k7 at dilation dil
         L3AC_TRY(run_legacy_unit(ctx, s, l, cur, alt, batch, frames));
         float* t = cur;
         cur = alt;
         alt = t;
     }
-    return run_head(ctx, s, cur, audio, batch, frames);
+    L3AC_TRY(rag_mask(ctx, s, cur, batch, frames, ctx->head.c, 3));  // head k7
+    L3AC_TRY(run_head(ctx, s, cur, audio, batch, frames));
+    return rag_mask(ctx, s, audio, batch, frames, 1, frames);  // a clip's samples end with its tokens
 }
 
 // the fused stack kernel computes on the bf16 matrix cores only (bf16x3): it belongs to the split route
@@ -870,9 +902,48 @@ static bool use_trans_stack(const l3ac_ctx* ctx, const LocalTransW& w, int frame
            trans_stack_supported(ctx->cfg.feature_dim, ctx->dim_head, HEADS, ctx->ff_inner, frames, w.window, (int)w.layers.size());
 }
 
+static int run_local_trans_layers(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames);
+
 int run_local_trans(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames) {
     if (use_trans_stack(ctx, w, frames))  // one launch for the whole stack, one workgroup per clip
         return launch_trans_stack(s, w, x, batch, frames, (float)std::pow((double)ctx->dim_head, -0.5), &ctx->coop);
+    return run_local_trans_layers(ctx, s, w, x, batch, frames);
+}
+
+// A ragged batch's LocalTrans stack (ctx->rag), x in place, `spare` a free activation buffer.  The stack kernel and the layered route
+// do not give the same bits, and which one a clip gets alone depends on its own frame count: so do the clips that would take the stack
+// alone (a prefix of RaggedPlan::order: the count is monotone in n_tok) in that kernel, over the largest of their frame counts, and the
+// others on the layered route.  Attention is causal, so a clip's rows after its own frames — zero here — never reach its frames.
+static int run_local_trans_ragged(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, float* spare, int batch, int frames) {
+    const RaggedPlan& r = *ctx->rag;
+    const int mult = frames / r.max_tok, dim = ctx->cfg.feature_dim;
+    L3AC_TRY(launch_ragged_mask(s, x, batch, frames, dim, r.n_dev, mult, frames));
+    int nq = 0;
+    while (nq < batch && use_trans_stack(ctx, w, r.n_tok[r.order[nq]] * mult)) ++nq;
+    const int fq = nq ? r.n_tok[r.order[nq - 1]] * mult : 0;          // rows of the stack's clips
+    const int fl = nq < batch ? r.n_tok[r.order[batch - 1]] * mult : 0;  // rows of the layered route's clips
+    if (nq == batch && fq == frames) return run_local_trans(ctx, s, w, x, batch, frames);
+    if (nq == 0 && fl == frames) return run_local_trans_layers(ctx, s, w, x, batch, frames);
+    // compact copies in `spare`: the stack's clips [nq][fq][dim], then the layered route's [batch - nq][fl][dim]
+    const int64_t clip = (int64_t)frames * dim;
+    float* q = spare;
+    float* l = spare + (int64_t)nq * fq * dim;
+    if (nq) L3AC_TRY(launch_ragged_gather(s, x, q, r.order_dev, 0, nq, fq, dim, clip, (int64_t)fq * dim, false));
+    if (nq < batch) L3AC_TRY(launch_ragged_gather(s, x, l, r.order_dev, nq, batch - nq, fl, dim, clip, (int64_t)fl * dim, false));
+    if (nq) L3AC_TRY(launch_trans_stack(s, w, q, nq, fq, (float)std::pow((double)ctx->dim_head, -0.5), &ctx->coop));
+    if (nq < batch) L3AC_TRY(run_local_trans_layers(ctx, s, w, l, batch - nq, fl));
+    if (nq) L3AC_TRY(launch_ragged_gather(s, q, x, r.order_dev, 0, nq, fq, dim, clip, (int64_t)fq * dim, true));
+    if (nq < batch) L3AC_TRY(launch_ragged_gather(s, l, x, r.order_dev, nq, batch - nq, fl, dim, clip, (int64_t)fl * dim, true));
+    return L3AC_OK;
+}
+
+// one LocalTrans stack of the pipeline, x = *cur in place (*alt is free)
+static int local_trans_step(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float** cur, float** alt, int batch, int frames) {
+    if (ctx->rag) return run_local_trans_ragged(ctx, s, w, *cur, *alt, batch, frames);
+    return run_local_trans(ctx, s, w, *cur, batch, frames);
+}
+
+static int run_local_trans_layers(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames) {
     Workspace& ws = ctx->ws;
     const int dim = ctx->cfg.feature_dim;
     const int64_t rows = (int64_t)batch * frames;
@@ -916,7 +987,8 @@ static inline void swap_bufs(float** a, float** b) {
 int run_encoder(l3ac_ctx* ctx, hipStream_t s, const float* audio, int64_t audio_stride, int batch, int samples,
                 int frames, float** cur, float** alt) {
     const l3ac_config& c = ctx->cfg;
-    L3AC_TRY(launch_first_block(s, ctx->first, audio, audio_stride, batch, samples, frames, *cur));
+    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
+    L3AC_TRY(launch_first_block(s, ctx->first, audio, audio_stride, batch, samples, frames, *cur, ctx->rag ? &rc : nullptr));
     int f = frames;
     for (int i = 0; i < c.n_enc; ++i) {
         L3AC_TRY(run_conv_units(ctx, s, ctx->enc_units[i], cur, alt, batch, f));
@@ -926,6 +998,7 @@ int run_encoder(l3ac_ctx* ctx, hipStream_t s, const float* audio, int64_t audio_
             f /= c.compress_rates[i];
         }
     }
+    L3AC_TRY(rag_mask(ctx, s, *cur, batch, f, c.enc_dims[c.n_enc - 1], 1));  // k3
     L3AC_TRY(run_conv_k3(ctx, s, ctx->enc_out, *cur, *alt, batch, f));
     swap_bufs(cur, alt);
     return L3AC_OK;
@@ -934,30 +1007,31 @@ int run_encoder(l3ac_ctx* ctx, hipStream_t s, const float* audio, int64_t audio_
 int run_en_encoder(l3ac_ctx* ctx, hipStream_t s, int batch, int frames, float** cur, float** alt, int* n_tok) {
     // input (B, C, T) permuted to (B, T, C) by the reference (local_trans.py:162): already frame-major here
     if (ctx->en_enc.size() == 2) {
-        L3AC_TRY(run_local_trans(ctx, s, ctx->en_enc[0], *cur, batch, frames));
+        L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[0], cur, alt, batch, frames));
         L3AC_TRY(run_down(ctx, s, ctx->en_down, *cur, *alt, batch, frames));
         swap_bufs(cur, alt);
         frames /= ctx->en_down.stride;
-        L3AC_TRY(run_local_trans(ctx, s, ctx->en_enc[1], *cur, batch, frames));
+        L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[1], cur, alt, batch, frames));
     } else {
-        L3AC_TRY(run_local_trans(ctx, s, ctx->en_enc[0], *cur, batch, frames));
+        L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[0], cur, alt, batch, frames));
     }
     *n_tok = frames;
     return L3AC_OK;
 }
 
 int run_en_decoder(l3ac_ctx* ctx, hipStream_t s, int batch, int n_tok, float** cur, float** alt, int* frames) {
-    L3AC_TRY(run_local_trans(ctx, s, ctx->en_dec[0], *cur, batch, n_tok));
+    L3AC_TRY(local_trans_step(ctx, s, ctx->en_dec[0], cur, alt, batch, n_tok));
     int f = n_tok;
     if (ctx->en_dec.size() == 2) {
         const int r = ctx->cfg.en_coder_compress_rate;
+        L3AC_TRY(rag_dup(ctx, s, *cur, batch, f, ctx->cfg.feature_dim));  // linear upsampling
         RowArgs u{};  // UpTransV2.up_layer (local_trans.py:121-124)
         u.x = *cur; u.y = *alt; u.batch = batch; u.frames_in = f; u.frames_out = (int64_t)f * r; u.c = ctx->cfg.feature_dim;
         u.src = SRC_LERP; u.scale = r; u.norm = NORM_NONE;
         L3AC_TRY(launch_rows(s, u));
         swap_bufs(cur, alt);
         f *= r;
-        L3AC_TRY(run_local_trans(ctx, s, ctx->en_dec[1], *cur, batch, f));
+        L3AC_TRY(local_trans_step(ctx, s, ctx->en_dec[1], cur, alt, batch, f));
     }
     *frames = f;
     return L3AC_OK;
@@ -965,6 +1039,7 @@ int run_en_decoder(l3ac_ctx* ctx, hipStream_t s, int batch, int n_tok, float** c
 
 int run_decoder(l3ac_ctx* ctx, hipStream_t s, int batch, int frames, float** cur, float** alt, float* audio) {
     const l3ac_config& c = ctx->cfg;
+    L3AC_TRY(rag_mask(ctx, s, *cur, batch, frames, ctx->dec_in.cin, 1));  // k3
     L3AC_TRY(run_conv_k3(ctx, s, ctx->dec_in, *cur, *alt, batch, frames));
     swap_bufs(cur, alt);
     int f = frames;

@@ -81,8 +81,23 @@ struct TransCoopState {
 
 struct Workspace {
     float *x0 = nullptr, *x1 = nullptr, *a = nullptr, *h = nullptr, *yi = nullptr, *stats = nullptr, *sumsq = nullptr;
+    int* plan = nullptr;  // a ragged call's per-clip counts on the device: RaggedPlan::plan_ints() ints per clip
     size_t x_cap = 0, a_cap = 0, h_cap = 0, yi_cap = 0, b_cap = 0;  // capacities in floats
-    size_t bytes() const { return (2 * x_cap + a_cap + h_cap + yi_cap + 9 * b_cap) * sizeof(float); }
+    size_t bytes() const { return (2 * x_cap + a_cap + h_cap + yi_cap + 12 * b_cap) * sizeof(float); }
+};
+
+// A ragged batch (l3ac_encode_ragged / l3ac_decode_ragged), set on the context for the duration of the
+// call (null on every other path).  The batch runs on the frame grid of max_tok tokens; clip b has n_tok[b] of them, so n_tok[b] *
+// frames / max_tok of a stage's `frames` rows.
+struct RaggedPlan {
+    static constexpr int plan_ints() { return 3; }
+    int max_tok = 0;
+    std::vector<int> n_tok;    // host, per clip
+    std::vector<int> order;    // host: the clips by n_tok, ascending (stable)
+    const int* n_dev = nullptr;        // device copies (Workspace::plan): n_tok,
+    const int* samples_dev = nullptr;  // the clips' samples (encode; n_tok * hop on decode),
+    const int* order_dev = nullptr;    // order
+    RaggedClips clips(int frames) const { return RaggedClips{n_dev, frames / max_tok, samples_dev}; }
 };
 
 struct l3ac_ctx {
@@ -153,6 +168,7 @@ struct l3ac_ctx {
     int* bad_index_count = nullptr;  // device: indices outside [0, codebook size) seen by l3ac_decode since the last reset
     int* wide_counters = nullptr;    // device, 64 B, zeroed: conv_unit_wide_kernel's unit counters (every launch leaves them zeroed)
     float* grn_min_sumsq = nullptr;  // device: smallest per-clip sum of squares any GRN of this context has seen (grn_exact only)
+    const RaggedPlan* rag = nullptr;  // the ragged call in progress (network.hip bounds each clip by it), null otherwise
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;
     bool ws_done_valid = false;
