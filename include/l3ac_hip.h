@@ -243,6 +243,42 @@ int64_t l3ac_resample_bank(int32_t in_rate, int32_t out_rate, float* bank, int64
 int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
                   const float* bank, float* y, int64_t y_stride, void* stream);
 
+/* ---- long recordings as chunk rows (reference: ChunkData, l3ac/codec.py:159-188) ----------------------
+ * A recording of n frames is cut into chunks of chunk_len frames, each but the first preceded by the prefix_len frames before it:
+ * chunk j covers [j * chunk_len - (j ? prefix_len : 0), min(n, (j + 1) * chunk_len)).  The chunks of a batch of recordings are the rows of
+ * one ragged call (l3ac_encode_ragged / l3ac_decode_ragged); merging drops every chunk's prefix again.  Context-free, like
+ * l3ac_pack_indices.  Frames hold `c` 4-byte elements (fp32 or int32: moved bit for bit, no arithmetic).
+ *   l3ac_chunk_plan:  HOST only.  frames[i] >= 1 frames per recording, first rounded up to a multiple of round_to (audio: the hop, the
+ *                     zero padding of codec.py:79-84; 1 otherwise); chunk_len > prefix_len >= 0.  Returns the number of chunks N, rows
+ *                     numbered 0 .. N - 1 recording after recording, and fills desc_out when it is non-null (cap >= N); < 0
+ *                     (L3AC_EINVAL, nothing written) on bad arguments or a cap that is too small.  The one place the geometry is computed.
+ *   l3ac_chunk_cut:   src [recs][src_stride][c] -> dst [rows][dst_row_frames][c]: row desc.row gets frames [start, start + frames) of
+ *                     recording desc.rec, its last desc.pad frames (the rounding) as zeros, never read.  Frames of a row after the
+ *                     chunk's own are not written.
+ *   l3ac_chunk_merge: src [rows][src_row_frames][c] -> dst [recs][dst_stride][c]: frames [prefix, frames) of row desc.row go to
+ *                     [start + prefix, start + frames) of recording desc.rec; a recording's last chunk also zeroes its row from
+ *                     start + frames to out_frames (<= dst_stride).  Called with a whole plan it writes every frame below out_frames
+ *                     of every recording exactly once.
+ * `desc` is a HOST array of `count` descriptors (any slice of a plan, in any order), checked against the shapes given before
+ * anything is launched and handed to the device as kernel arguments, 112 per launch: the caller may change it as soon as the call
+ * returns, a captured graph replays what it captured.  16-byte accesses where source and destination of a span are congruent
+ * modulo 16 bytes (always for c % 4 == 0 with 16-byte aligned rows), dword accesses otherwise.  Enqueue only. */
+typedef struct l3ac_chunk_desc {
+    int32_t rec;     /* recording: row of the [recs][stride] layout */
+    int32_t row;     /* row of the chunk layout */
+    int64_t start;   /* the chunk's first frame in its recording, prefix included */
+    int32_t frames;  /* frames of the chunk, prefix included */
+    int32_t prefix;  /* of them, frames that belong to the previous chunk: prefix_len, 0 for a recording's first chunk */
+    int32_t pad;     /* of them, frames at the end that exist only through rounding: cut writes zeros */
+    int32_t last;    /* 1 for a recording's last chunk */
+} l3ac_chunk_desc;
+int64_t l3ac_chunk_plan(const int64_t* frames, int32_t batch, int64_t chunk_len, int64_t prefix_len, int32_t round_to,
+                        l3ac_chunk_desc* desc_out, int64_t cap);
+int l3ac_chunk_cut(const void* src, int32_t recs, int64_t src_stride, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
+                   void* dst, int32_t rows, int64_t dst_row_frames, void* stream);
+int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
+                     void* dst, int32_t recs, int64_t dst_stride, int64_t out_frames, void* stream);
+
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */

@@ -39,7 +39,7 @@ from .chunking import ChunkData, plan as _chunk_plan
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
-           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths"]
+           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -262,8 +262,7 @@ class L3AC:
         rate = self._rate(sample_rate)
         if rate is not None and lens is not None:
             # each clip is converted as it would be alone: its zero padding, not its neighbour's samples, after its end
-            keep = torch.arange(audio_data.shape[1], device=audio_data.device)[None, :] < torch.tensor(lens, device=audio_data.device)[:, None]
-            audio_data = torch.where(keep, audio_data.to(torch.float32), 0.0)
+            audio_data = _zero_after(audio_data.to(torch.float32), lens)
             lens = [resample_length(rate, self.config.sample_rate, n) for n in lens]
         if rate is not None:
             audio_data = resample(audio_data, rate, self.config.sample_rate)
@@ -355,8 +354,7 @@ class L3AC:
         audio = resample(audio, self.config.sample_rate, rate)
         if lens is not None:  # each clip ends where its own converted samples end
             ends = [resample_length(self.config.sample_rate, rate, n * mc.hop_length) for n in lens]
-            keep = torch.arange(audio.shape[1], device=audio.device)[None, :] < torch.tensor(ends, device=audio.device)[:, None]
-            audio = torch.where(keep, audio, 0.0)
+            audio = _zero_after(audio, ends)
         return audio
 
 
@@ -418,6 +416,160 @@ class L3AC:
             waves = self._batched(lambda b: list(self.decode_audio(indices=b)), src.chunk_data)
         merged = ChunkData(chunk_len=src.chunk_len * hop, prefix_len=src.prefix_len * hop, chunk_data=waves).data[None, :]
         return merged if audio_length is None else merged[:, :audio_length]
+
+
+    # ---- batches of long recordings through ragged chunk calls -------------------------------
+    def _long_plan(self, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int]):
+        mc = self.network.mc
+        prefix_tokens = mc.en_coder_window_size if prefix_tokens is None else int(prefix_tokens)
+        chunk_len, prefix_len = _chunk_plan(mc.hop_length, process_window, prefix_tokens)
+        if chunks_per_call is None:
+            chunks_per_call = max(1, (512 * self.config.sample_rate) // (chunk_len + prefix_len))
+        if int(chunks_per_call) < 1:
+            raise ValueError(f"chunks_per_call must be at least 1, got {chunks_per_call}")
+        return chunk_len, prefix_tokens, min(int(chunks_per_call), 65535)
+
+    @torch.no_grad()
+    def encode_long(self, audio_data: torch.Tensor, lengths=None, process_window: int = 5 * 16000, prefix_tokens: Optional[int] = None,
+                    sample_rate: Optional[int] = None, chunks_per_call: Optional[int] = None, validate: bool = False):
+        """A batch of recordings of any lengths, window by window: audio (B, T) fp32 with ``lengths`` (B sample counts in 1..T; absent:
+        every row is T long; samples at or after ``lengths[i]`` are ignored, whatever they hold) -> what
+        ``encode_audio(..., lengths=)`` returns, in the same shapes: (q_feature (B, T_tok, C), {"indices": int32 (B, T_tok),
+        "level_indices": fp32 (B, T_tok, D), "lengths": int32 CPU (B,)}), T_tok = ceil(T / hop), zero after a recording's own
+        ``ceil(lengths[i] / hop)`` tokens.
+
+        Row i equals ``extract_unit(audio_data[i:i+1, :lengths[i]], process_window, prefix_tokens)`` merged (``.data`` of the
+        index and of the feature ChunkData) bit for bit; ``process_window`` and ``prefix_tokens`` mean what they mean there.  The
+        chunks of the whole batch are cut on the device into the rows of ragged calls (``lengths=`` of encode_audio), at most
+        ``chunks_per_call`` rows per call (default: 512 s of rows); the result does not depend on it.  ``sample_rate``: as
+        encode_audio with ``lengths=`` (each recording converted as it would be alone, lengths counted at that rate).
+        ``validate``: as encode_audio.  Capturable into a graph after ``context().reserve(chunks_per_call, row_samples)`` and one
+        eager call: the plan and the lengths are host values fixed at capture."""
+        if audio_data.dim() != 2:
+            raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
+        if audio_data.shape[0] == 0 or audio_data.shape[1] == 0:
+            raise ValueError("empty audio")
+        lens = ragged_lengths([audio_data.shape[1]] * audio_data.shape[0] if lengths is None else lengths, audio_data.shape[0],
+                              audio_data.shape[1], "lengths")
+        chunk_len, prefix_tokens, per_call = self._long_plan(process_window, prefix_tokens, chunks_per_call)
+        rate = self._rate(sample_rate)
+        ctx = self._check_input(audio_data, "audio_data")
+        if self.network.grn_exact:
+            raise _capi.L3acError("encode_long: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
+                                  "would include their padding: use extract_unit per recording")
+        mc = self.network.mc
+        hop = mc.hop_length
+        audio = audio_data.to(torch.float32)
+        if rate is not None:
+            audio = resample(_zero_after(audio, lens), rate, self.config.sample_rate)
+            lens = [resample_length(rate, self.config.sample_rate, n) for n in lens]
+        if audio.stride(-1) != 1:
+            audio = audio.contiguous()
+        b, t = audio.shape
+        n_tok = math.ceil(t / hop)
+        tok = [math.ceil(n / hop) for n in lens]
+        cut = chunk_plan(lens, chunk_len, prefix_tokens * hop, hop)       # in samples, each recording padded to whole hops
+        merge = chunk_plan(tok, chunk_len // hop, prefix_tokens, 1)       # the same chunks in tokens
+        assert len(cut) == len(merge)
+        dev = audio.device
+        q_feature = torch.empty((b, n_tok, mc.feature_dim), dtype=torch.float32, device=dev)
+        indices = torch.empty((b, n_tok), dtype=torch.int32, device=dev)
+        level_indices = torch.empty((b, n_tok, len(mc.levels)), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if validate:
+                self._coop_check_before(ctx, "encode_long")
+            for group in _chunk_groups(cut, per_call):
+                g = len(group)
+                samples = [cut[j].frames for j in group]
+                longest = max(samples)
+                g_tok = longest // hop
+                rows = torch.empty((g, -(-longest // 4) * 4), dtype=torch.float32, device=dev)
+                q = torch.empty((g, g_tok, mc.feature_dim), dtype=torch.float32, device=dev)
+                idx = torch.empty((g, g_tok), dtype=torch.int32, device=dev)
+                li = torch.empty((g, g_tok, len(mc.levels)), dtype=torch.float32, device=dev)
+                _chunk_cut(audio, _group_desc(cut, group), rows, stream)
+                _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), (ctypes.c_int32 * g)(*samples),
+                                                       q.data_ptr(), idx.data_ptr(), li.data_ptr(), stream))
+                desc = _group_desc(merge, group)
+                _chunk_merge(q, desc, q_feature, stream)
+                _chunk_merge(idx, desc, indices, stream)
+                _chunk_merge(li, desc, level_indices, stream)
+            if validate:
+                self._raise_on_coop_timeout(ctx, "encode_long")
+        return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": torch.tensor(tok, dtype=torch.int32)}
+
+    @torch.no_grad()
+    def decode_long(self, audio_feature: torch.Tensor = None, indices: torch.Tensor = None, lengths=None, process_window: int = 5 * 16000,
+                    prefix_tokens: Optional[int] = None, sample_rate: Optional[int] = None, chunks_per_call: Optional[int] = None,
+                    validate: bool = False) -> torch.Tensor:
+        """The merged streams ``encode_long`` returns — (B, T_tok, C) features, or int indices (B, T_tok) — with ``lengths`` in tokens
+        (absent: T_tok each) -> audio (B, T_tok * hop), not trimmed, zero after ``lengths[i] * hop``.
+
+        Each recording's stream is cut the way ``ChunkData(cl, prefix_tokens, original_data=stream)`` cuts it
+        (``cl = process_window // hop``), the chunks of the whole batch are decoded as rows of ragged calls (at most
+        ``chunks_per_call`` per call; the result does not depend on it) and the waveforms merged, every chunk but a recording's
+        first dropping its first ``prefix_tokens * hop`` samples: row i equals
+        ``decode_unit(chunk_indices=ChunkData(cl, prefix_tokens, original_data=indices[i, :lengths[i]]))`` (or the
+        ``chunk_q_feature`` form) bit for bit.  A chunk too short for the first EnhanceBlock raises the ValueError decode_audio
+        raises, before any device work.  ``sample_rate``: as decode_audio with ``lengths=``.
+        Out-of-range indices are clamped and counted as in decode_audio; tokens after a recording's own are never counted.  A token
+        inside an overlap is decoded twice (as the last tokens of one chunk and as the prefix of the next) and is counted twice:
+        ``validate=True`` raises when the count is non-zero and reports index OCCURRENCES in chunk rows, not distinct tokens."""
+        src = audio_feature if audio_feature is not None else indices
+        if src is None:
+            raise ValueError("decode_long needs audio_feature or indices")
+        mc = self.network.mc
+        hop = mc.hop_length
+        if audio_feature is not None:
+            if audio_feature.dim() != 3 or audio_feature.shape[-1] != mc.feature_dim:
+                raise ValueError(f"audio_feature must be (batch, tokens, {mc.feature_dim})")
+        elif indices.dim() != 2:
+            raise ValueError("indices must be (batch, tokens)")
+        b, n_tok = src.shape[:2]
+        if b == 0 or n_tok == 0:
+            raise ValueError("empty token stream")
+        tok = ragged_lengths([n_tok] * b if lengths is None else lengths, b, n_tok, "lengths (tokens)")
+        chunk_len, prefix_tokens, per_call = self._long_plan(process_window, prefix_tokens, chunks_per_call)
+        rate = self._rate(sample_rate)
+        cut = chunk_plan(tok, chunk_len // hop, prefix_tokens, 1)
+        if min(d.frames for d in cut) * mc.en_coder_compress_rate < 2:
+            # reference behaviour, as decode_audio: the first EnhanceBlock's InstanceNorm1d raises on a single frame
+            raise ValueError(f"Expected more than 1 spatial element when training, got input size torch.Size([{b}, 4, 1])")
+        ctx = self._check_input(src, "decode input")
+        if self.network.grn_exact:
+            raise _capi.L3acError("decode_long: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
+                                  "would include their padding: use decode_unit per recording")
+        src = src.to(torch.float32 if audio_feature is not None else torch.int32).contiguous()
+        dev = src.device
+        audio = torch.empty((b, n_tok * hop), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            before = ctx.bad_index_count() if validate and audio_feature is None else 0
+            if validate:
+                self._coop_check_before(ctx, "decode_long")
+            for group in _chunk_groups(cut, per_call):
+                g = len(group)
+                toks = [cut[j].frames for j in group]
+                longest = max(toks)
+                rows = torch.empty((g, longest) + tuple(src.shape[2:]), dtype=src.dtype, device=dev)
+                wave = torch.empty((g, longest * hop), dtype=torch.float32, device=dev)
+                _chunk_cut(src, _group_desc(cut, group), rows, stream)
+                f_ptr, i_ptr = (rows.data_ptr(), None) if audio_feature is not None else (None, rows.data_ptr())
+                _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, g, longest, (ctypes.c_int32 * g)(*toks), wave.data_ptr(),
+                                                       stream))
+                _chunk_merge(wave, _group_desc(cut, group, hop), audio, stream)
+            if validate:
+                self._raise_on_coop_timeout(ctx, "decode_long")
+            if validate and audio_feature is None:
+                bad = ctx.bad_index_count() - before
+                if bad:
+                    raise ValueError(f"{bad} index occurrences in the chunk rows (a token in an overlap counts twice) lie outside "
+                                     f"[0, {mc.codebook_size}): corrupted token stream")
+        if rate is None:
+            return audio
+        audio = resample(audio, self.config.sample_rate, rate)
+        return _zero_after(audio, [resample_length(self.config.sample_rate, rate, n * hop) for n in tok])
 
 
 def set_gemm_split(enable: bool) -> None:
@@ -489,6 +641,59 @@ def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int) -> torch.Tensor:
         _capi.check(lib.l3ac_unpack_indices(src.data_ptr(), packed.shape[0], n_tok, bits, words, out.data_ptr(),
                                             torch.cuda.current_stream(packed.device).cuda_stream))
     return out
+
+
+def _zero_after(x: torch.Tensor, ends) -> torch.Tensor:
+    """(B, T) with row i zero from ends[i] on: each clip of a ragged batch masked to its own end (sample_rate= with lengths=)."""
+    keep = torch.arange(x.shape[1], device=x.device)[None, :] < torch.tensor(ends, device=x.device)[:, None]
+    return torch.where(keep, x, 0.0)
+
+
+def chunk_plan(frames, chunk_len: int, prefix_len: int, round_to: int = 1):
+    """The chunks of a batch of recordings of ``frames[i]`` frames each, as a ctypes array of ``_capi.ChunkDesc`` (rec, row, start,
+    frames, prefix, pad, last): ``ChunkData``'s geometry, computed by the library (l3ac_chunk_plan, host only; DESIGN.md section
+    3.8).  Rows are numbered recording after recording.  Raises ValueError on bad arguments."""
+    lib = _capi.load_library()
+    vals = [int(v) for v in frames]
+    host = (ctypes.c_int64 * max(len(vals), 1))(*vals)
+    n = lib.l3ac_chunk_plan(host, len(vals), int(chunk_len), int(prefix_len), int(round_to), None, 0)
+    if n < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    desc = (_capi.ChunkDesc * n)()
+    if lib.l3ac_chunk_plan(host, len(vals), int(chunk_len), int(prefix_len), int(round_to), desc, n) != n:
+        raise ValueError(lib.l3ac_last_error().decode())
+    return desc
+
+
+def _chunk_groups(desc, chunks_per_call: int):
+    """A plan's chunks as the groups of at most `chunks_per_call` chunk numbers that run in one ragged call each, shortest first: a
+    ragged call computes the grid of its longest row, so every recording's short chunks (its first has no prefix, its last is what is
+    left) share calls of their own size (3.5 % of a call).  The bits do not depend on the grouping."""
+    order = sorted(range(len(desc)), key=lambda k: desc[k].frames)  # (stable)
+    return [order[k0:k0 + chunks_per_call] for k0 in range(0, len(order), chunks_per_call)]
+
+
+def _group_desc(desc, group, scale: int = 1):
+    """The descriptors of one group with rows renumbered 0 .. len(group) - 1 (the rows of that group's call)."""
+    out = (_capi.ChunkDesc * len(group))()
+    for k, j in enumerate(group):
+        d = desc[j]
+        out[k] = _capi.ChunkDesc(d.rec, k, d.start * scale, d.frames * scale, d.prefix * scale, d.pad * scale, d.last)
+    return out
+
+
+def _chunk_cut(src: torch.Tensor, desc, rows: torch.Tensor, stream) -> None:
+    """src (B, stride[, c]) -> rows (N, row_frames[, c]) on the device (l3ac_chunk_cut)."""
+    c = src.shape[2] if src.dim() == 3 else 1
+    _capi.check(_capi.load_library().l3ac_chunk_cut(src.data_ptr(), src.shape[0], src.stride(0) // c if src.shape[0] > 1 else src.shape[1],
+                                                     c, desc, len(desc), rows.data_ptr(), rows.shape[0], rows.stride(0) // c, stream))
+
+
+def _chunk_merge(rows: torch.Tensor, desc, dst: torch.Tensor, stream) -> None:
+    """rows (N, row_frames[, c]) -> dst (B, out_frames[, c]), prefixes dropped, zeros after each recording (l3ac_chunk_merge)."""
+    c = dst.shape[2] if dst.dim() == 3 else 1
+    _capi.check(_capi.load_library().l3ac_chunk_merge(rows.data_ptr(), rows.shape[0], rows.stride(0) // c, c, desc, len(desc), dst.data_ptr(),
+                                                       dst.shape[0], dst.shape[1], dst.shape[1], stream))
 
 
 def ragged_lengths(lengths, batch: int, limit: int, what: str = "lengths") -> list:

@@ -39,6 +39,12 @@ class Config(C.Structure):
     ]
 
 
+class ChunkDesc(C.Structure):
+    """l3ac_chunk_desc: one chunk of one recording (include/l3ac_hip.h)."""
+    _fields_ = [("rec", C.c_int32), ("row", C.c_int32), ("start", C.c_int64), ("frames", C.c_int32), ("prefix", C.c_int32),
+                ("pad", C.c_int32), ("last", C.c_int32)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -101,6 +107,9 @@ SIGNATURES = {
     "l3ac_resample_length": (_I64, [_I32, _I32, _I64]),
     "l3ac_resample_bank": (_I64, [_I32, _I32, _P, _I64]),
     "l3ac_resample": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _P, _P, _I64, _P]),
+    "l3ac_chunk_plan": (_I64, [C.POINTER(_I64), _I32, _I64, _I64, _I32, C.POINTER(ChunkDesc), _I64]),
+    "l3ac_chunk_cut": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(ChunkDesc), _I32, _P, _I32, _I64, _P]),
+    "l3ac_chunk_merge": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(ChunkDesc), _I32, _P, _I32, _I64, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

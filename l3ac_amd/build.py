@@ -43,6 +43,7 @@ SOURCES = [
     "kernels/up_fused.hip",
     "kernels/ragged.hip",
     "kernels/resample.hip",
+    "kernels/chunk.hip",
 ]
 
 

@@ -727,6 +727,22 @@ int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride,
     return launch_resample((hipStream_t)stream, x, batch, n_in, x_stride, in_rate, out_rate, bank, y, y_stride);
 }
 
+// ---- long recordings as chunk rows ---------------------------------------------
+int64_t l3ac_chunk_plan(const int64_t* frames, int32_t batch, int64_t chunk_len, int64_t prefix_len, int32_t round_to,
+                        l3ac_chunk_desc* desc_out, int64_t cap) {
+    return chunk_plan(frames, batch, chunk_len, prefix_len, round_to, desc_out, cap);
+}
+
+int l3ac_chunk_cut(const void* src, int32_t recs, int64_t src_stride, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
+                   void* dst, int32_t rows, int64_t dst_row_frames, void* stream) {
+    return launch_chunk_cut((hipStream_t)stream, src, recs, src_stride, c, desc, count, dst, rows, dst_row_frames);
+}
+
+int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
+                     void* dst, int32_t recs, int64_t dst_stride, int64_t out_frames, void* stream) {
+    return launch_chunk_merge((hipStream_t)stream, src, rows, src_row_frames, c, desc, count, dst, recs, dst_stride, out_frames);
+}
+
 int l3ac_profile_begin(void) {
     L3AC_REQUIRE(g_profiler == nullptr, "profile already active on this thread");
     g_profiler = new (std::nothrow) Profiler();

@@ -198,6 +198,19 @@ int launch_ragged_dup(hipStream_t s, float* x, int batch, int frames, int c, con
 // compact clip k <-> batch clip perm[k0 + k] for k < count: `rows` rows of c floats; clip strides in floats
 int launch_ragged_gather(hipStream_t s, const float* src, float* dst, const int* perm, int k0, int count, int rows, int c,
                          int64_t batch_clip, int64_t compact_clip, bool scatter);
+// long recordings as chunk rows (kernels/chunk.hip): descriptors reach the device as kernel arguments, CAP per launch
+struct ChunkBlock {
+    static constexpr int CAP = 112;  // 3.5 KiB of the 4 KiB a launch's arguments may take
+    l3ac_chunk_desc desc[CAP];
+};
+// HOST: the chunks of `batch` recordings (ChunkData's geometry); the count, or L3AC_EINVAL.  Fills `out` when non-null (cap >= count)
+int64_t chunk_plan(const int64_t* frames, int batch, int64_t chunk_len, int64_t prefix_len, int round_to, l3ac_chunk_desc* out, int64_t cap);
+// recordings [recs][src_stride][c] -> chunk rows [rows][dst_row_frames][c], 4-byte elements; `desc` is a host array
+int launch_chunk_cut(hipStream_t s, const void* src, int recs, int64_t src_stride, int c, const l3ac_chunk_desc* desc, int count, void* dst,
+                     int rows, int64_t dst_row_frames);
+// chunk rows [rows][src_row_frames][c] -> recordings [recs][dst_stride][c], prefixes dropped, zeros from a recording's end to out_frames
+int launch_chunk_merge(hipStream_t s, const void* src, int rows, int64_t src_row_frames, int c, const l3ac_chunk_desc* desc, int count,
+                       void* dst, int recs, int64_t dst_stride, int64_t out_frames);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)
