@@ -283,6 +283,12 @@ int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int3
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */
 int l3ac_op_first_block(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t samples, float* y, void* stream);
+/* The stem as l3ac_encode runs it: audio [batch] rows of `samples` valid floats, `audio_stride` floats apart (>= samples; what lies
+ * between the rows is not read), -> y [batch][frames][d0] with frames >= samples > 0: frames samples .. frames - 1 are the zero
+ * right-padding of Codec.preprocess (codec.py:79-84), folded into the load.  Anything else is refused (L3AC_EINVAL) before a launch.
+ * l3ac_op_first_block(audio, batch, samples) = l3ac_op_first_block_at(audio, batch, samples, samples, samples). */
+int l3ac_op_first_block_at(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t samples, int64_t audio_stride, int32_t frames,
+                           float* y, void* stream);
 int l3ac_op_conv_unit(l3ac_ctx* ctx, const char* block, const float* x, int32_t batch, int32_t frames, float* y,
                       void* stream);
 int l3ac_op_down_layer(l3ac_ctx* ctx, const char* block, const float* x, int32_t batch, int32_t frames, float* y,

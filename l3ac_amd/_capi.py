@@ -76,6 +76,7 @@ SIGNATURES = {
     "l3ac_vq_argmin_scratch_bytes": (_I64, [_I64, _I32, _I32]),
     "l3ac_vq_argmin": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
     "l3ac_op_first_block": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
+    "l3ac_op_first_block_at": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, _P, _P]),
     "l3ac_op_conv_unit": (C.c_int, [_P, C.c_char_p, _P, _I32, _I32, _P, _P]),
     "l3ac_op_down_layer": (C.c_int, [_P, C.c_char_p, _P, _I32, _I32, _P, _P]),
     "l3ac_op_conv_k3": (C.c_int, [_P, C.c_char_p, _P, _I32, _I32, _P, _P]),

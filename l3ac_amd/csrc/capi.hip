@@ -537,6 +537,15 @@ int l3ac_op_first_block(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_
     return launch_first_block((hipStream_t)stream, ctx->first, audio, samples, batch, samples, samples, y);
 }
 
+int l3ac_op_first_block_at(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t samples, int64_t audio_stride, int32_t frames,
+                           float* y, void* stream) {
+    L3AC_ENTER_WS(ctx, stream);
+    L3AC_REQUIRE(audio && y && batch > 0, "op_first_block_at: bad arguments");
+    L3AC_REQUIRE(samples > 0 && frames >= samples, "op_first_block_at: frames %d < samples %d, or samples <= 0", frames, samples);
+    L3AC_REQUIRE(audio_stride >= samples, "op_first_block_at: stride %lld < samples %d", (long long)audio_stride, samples);
+    return launch_first_block((hipStream_t)stream, ctx->first, audio, audio_stride, batch, samples, frames, y);
+}
+
 // (h: 4C floats per row, or the wide ConvUnit front end's planes of whole 32-frame tiles when that is more)
 #define L3AC_OP_SCRATCH(c_max)                                                                                    \
     L3AC_TRY(workspace_ensure(ctx, (size_t)batch * frames * (c_max), (size_t)batch * frames * (c_max),           \

@@ -46,8 +46,8 @@ struct GemmArgs {
     int n_out = 0;                     // EPI_GEGLU: number of valid output columns (ff inner)
     // optional EnhanceBlock gate applied to the A operand while it is staged (tconv/__init__.py:35-44, same arithmetic as
     // the SRC_GATE row kernel): a'(m, k) = a + (gate_b[k] + gate_w[k][:] . instnorm(yi[m][:])) * a.  Plain A, k % 16 == 0.
-    const float* gate_yi = nullptr;     // raw branch signals [m][4]
-    const float* gate_stats = nullptr;  // [clip][8] = mean[4], 1/std[4]
+    const float* gate_yi = nullptr;     // branch signals [m][4], centred in place by enhance_stats_kernel
+    const float* gate_stats = nullptr;  // [clip][8] = mean[4] (0: yi arrives centred; the subtraction that is left is exact), 1/std[4]
     const float* gate_in_w = nullptr;   // InstanceNorm affine [4]
     const float* gate_in_b = nullptr;
     const float* gate_w = nullptr;      // merge conv [k][4]
@@ -90,8 +90,8 @@ struct RowArgs {
     const float* dw_w = nullptr;  // [7][c]
     const float* dw_b = nullptr;  // [c]
     int scale = 1;                // SRC_LERP
-    const float* yi = nullptr;    // SRC_GATE: raw branch signals [batch][frames][4]
-    const float* stats = nullptr; // [batch][8] = mean[4], invstd[4]
+    const float* yi = nullptr;    // SRC_GATE: branch signals [batch][frames][4], centred in place by enhance_stats_kernel
+    const float* stats = nullptr; // [batch][8] = mean[4] (0: yi arrives centred), invstd[4]
     const float* in_w = nullptr;  // InstanceNorm affine [4]
     const float* in_b = nullptr;
     const float* gate_w = nullptr;  // merge conv [c][4]
@@ -137,7 +137,8 @@ struct EnhanceW {
 };
 int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi,
                             const RaggedClips* rc = nullptr);
-int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats, const RaggedClips* rc = nullptr);
+// (centres yi in place: stats = 0[4], 1/std[4])
+int launch_enhance_stats(hipStream_t s, float* yi, int batch, int frames, float* stats, const RaggedClips* rc = nullptr);
 
 // output head (modules.py:190-195 after the Snake1d): conv 24 -> 1 k7 pad 3, tanh
 // pretanh (validation, l3ac_ctx_set_head_pretanh): store the conv result BEFORE the final tanh

@@ -4,13 +4,12 @@
 //   p_k = avg_pool(max_pool(|x0|, k), k), k in {1 (identity), 3, 5, 9}
 //   -> weight-normed Conv1d(1 -> 1, k7, dilation k//2 + 1 = {1, 2, 3, 5}, pad 3*dil)
 //   -> InstanceNorm1d(4, affine) over the frames of each clip -> plain Conv1d(4 -> C, 1) -> x + y * x.
-// Here: `enhance_branches` writes the four raw branch signals yi [batch][frames][4]; `enhance_stats` reduces
-// them to mean / 1/sqrt(var + 1e-5) per (clip, branch); the normalise + merge + gate is the SRC_GATE row kernel.
+// Here: `enhance_branches` writes the four raw branch signals yi [batch][frames][4]; `enhance_stats` centres them in place
+// (yi - mean) and reduces them to 1/sqrt(var + 1e-5) per (clip, branch); the normalise + merge + gate is the SRC_GATE row kernel.
 //
 // Output head (l3ac/modules.py:192-194): weight-normed Conv1d(c -> 1, k7, pad 3) -> tanh on the snake-activated
 // last feature map.
 #include "../kernels.hpp"
-#include "lane_sums.hpp"
 
 namespace {
 
@@ -37,11 +36,15 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
     __syncthreads();
 
     float out[4];
+    // The seven taps are summed in fp64 and rounded once.  An fp32 fma chain from the bias rounds seven times at the bias's magnitude;
+    // for a quiet channel 0 (1e-6: the taps are far below an ulp of the bias) that is most of what the InstanceNorm then multiplies
+    // by 1/std = 316, and it left the gate 1.6 - 1.9 x less accurate than the fp32 oracle, whose conv adds the bias last
+    // (tests/test_gpu_trend_front.py).  28 fp64 fmas per frame, next to a gather of channel 0 at a stride of c floats.
     {  // branch 0: identity pool, dilation 1
-        float acc = w.tb[0];
+        double acc = (double)w.tb[0];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) acc = fmaf(w.tw[j], xs[XH + tid + j - 3], acc);
-        out[0] = acc;
+        for (int j = 0; j < 7; ++j) acc = fma((double)w.tw[j], (double)xs[XH + tid + j - 3], acc);
+        out[0] = (float)acc;
     }
     const int pool_k[3] = {3, 5, 9};
 #pragma unroll
@@ -75,10 +78,10 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
             pbuf[i] = pv;
         }
         __syncthreads();
-        float acc = w.tb[br + 1];
+        double acc = (double)w.tb[br + 1];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) acc = fmaf(w.tw[(br + 1) * 7 + j], pbuf[tid + j * dil], acc);
-        out[br + 1] = acc;
+        for (int j = 0; j < 7; ++j) acc = fma((double)w.tw[(br + 1) * 7 + j], (double)pbuf[tid + j * dil], acc);
+        out[br + 1] = (float)acc;
         __syncthreads();
     }
     const int t = t0 + tid;
@@ -87,50 +90,59 @@ __global__ __launch_bounds__(TILE) void enhance_branches_kernel(const EnhanceW w
 }
 
 // one block per clip: two-pass mean / biased variance over frames for the 4 branch channels (RAGGED: over the clip's own rn[b] * rmult
-// frames, summed in the order of the clip alone; `batch_frames` is the batch's row count)
+// frames, summed in the order of the clip alone; `batch_frames` is the batch's row count).
+// The gate multiplies yi - mean by 1/std, up to 316 at a near-constant channel 0 (silence, DC, a square wave, a 1e-6 signal), so what
+// is wrong in the mean comes out 316 x larger.  With an fp32 mean (ceil(T / 1024) + 22 additions, a product by the rounded 1 / T) the
+// gate was 3 - 14 x less accurate there than the fp32 oracle, whose ATen instance_norm accumulates in fp64; and ANY mean stored in fp32
+// is up to half an ulp off, which is still 3 % of yi - mean for a 1e-6 signal.  So: the sums run in fp64, and the second pass writes
+// yi - mean back over yi, the difference taken in fp64 and rounded once; stats[0..3] (the mean the gate evaluators subtract) is 0.
+// tests/test_gpu_trend_front.py holds the result to 1.5 x the oracle's rms error per input kind.
+// The kernel is bound by its passes over yi (16 B per frame): the fp64 adds and the 2 x 24 shuffles are not on that path.
 template <bool RAGGED>
-__global__ __launch_bounds__(1024) void enhance_stats_kernel(const float* __restrict__ yi, int batch_frames,
+__global__ __launch_bounds__(1024) void enhance_stats_kernel(float* __restrict__ yi, int batch_frames,
                                                             float* __restrict__ stats, const int* __restrict__ rn, int rmult) {
-    __shared__ float4 part[16];
-    __shared__ float4 bc;
+    __shared__ double part[16][4];
+    __shared__ double bc[4];
     const int b = blockIdx.x;
-    const float4* src = reinterpret_cast<const float4*>(yi) + (int64_t)b * batch_frames;
-    const int frames = RAGGED ? rn[b] * rmult : batch_frames;
-    auto block_sum = [&](float4 v) -> float4 {
-        v = make_float4(wave_sum(v.x), wave_sum(v.y), wave_sum(v.z), wave_sum(v.w));
+    float4* src = reinterpret_cast<float4*>(yi) + (int64_t)b * batch_frames;
+    const int frames = RAGGED ? rn[b] * rmult : batch_frames;  // >= 1: l3ac_decode_ragged refuses a clip without a token
+    auto block_sum = [&](double (&v)[4]) {  // v <- the block's sums, the same bits in every thread; a fixed order of additions
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) v[j] += __shfl_xor(v[j], m);
         __syncthreads();
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+        if ((threadIdx.x & 63) == 0)
+            for (int j = 0; j < 4; ++j) part[threadIdx.x >> 6][j] = v[j];
         __syncthreads();
-        if (threadIdx.x == 0) {
-            float4 s = part[0];
-            for (int i = 1; i < 16; ++i) { s.x += part[i].x; s.y += part[i].y; s.z += part[i].z; s.w += part[i].w; }
-            bc = s;
+        if (threadIdx.x < 4) {
+            double s = part[0][threadIdx.x];
+            for (int i = 1; i < 16; ++i) s += part[i][threadIdx.x];
+            bc[threadIdx.x] = s;
         }
         __syncthreads();
-        return bc;
+        for (int j = 0; j < 4; ++j) v[j] = bc[j];
     };
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int t = threadIdx.x; t < frames; t += 1024) {
         const float4 v = src[t];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        acc[0] += (double)v.x; acc[1] += (double)v.y; acc[2] += (double)v.z; acc[3] += (double)v.w;
     }
-    float4 mean = block_sum(acc);
-    const float inv_n = 1.0f / (float)frames;
-    mean.x *= inv_n; mean.y *= inv_n; mean.z *= inv_n; mean.w *= inv_n;
-    acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    block_sum(acc);
+    const double mean[4] = {acc[0] / (double)frames, acc[1] / (double)frames, acc[2] / (double)frames, acc[3] / (double)frames};
+    acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
     for (int t = threadIdx.x; t < frames; t += 1024) {
         const float4 v = src[t];
-        const float dx = v.x - mean.x, dy = v.y - mean.y, dz = v.z - mean.z, dw = v.w - mean.w;
-        acc.x += dx * dx; acc.y += dy * dy; acc.z += dz * dz; acc.w += dw * dw;
+        const double dx = (double)v.x - mean[0], dy = (double)v.y - mean[1], dz = (double)v.z - mean[2], dw = (double)v.w - mean[3];
+        acc[0] += dx * dx; acc[1] += dy * dy; acc[2] += dz * dz; acc[3] += dw * dw;
+        src[t] = make_float4((float)dx, (float)dy, (float)dz, (float)dw);
     }
-    const float4 var = block_sum(acc);
+    block_sum(acc);
     if (threadIdx.x == 0) {
         float* o = stats + (int64_t)b * 8;
-        o[0] = mean.x; o[1] = mean.y; o[2] = mean.z; o[3] = mean.w;
-        o[4] = 1.0f / sqrtf(var.x * inv_n + 1e-5f);
-        o[5] = 1.0f / sqrtf(var.y * inv_n + 1e-5f);
-        o[6] = 1.0f / sqrtf(var.z * inv_n + 1e-5f);
-        o[7] = 1.0f / sqrtf(var.w * inv_n + 1e-5f);
+        o[0] = o[1] = o[2] = o[3] = 0.f;  // yi is centred
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[4 + j] = (float)(1.0 / sqrt(acc[j] / (double)frames + 1e-5));
     }
 }
 
@@ -173,8 +185,8 @@ int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, in
     return L3AC_OK;
 }
 
-int launch_enhance_stats(hipStream_t s, const float* yi, int batch, int frames, float* stats, const RaggedClips* rc) {
-    ProfScope prof(s, rc ? "enhance_stats_kernel<RAGGED>" : "enhance_stats_kernel", 16.0 * batch * frames, 32.0 * batch * frames);
+int launch_enhance_stats(hipStream_t s, float* yi, int batch, int frames, float* stats, const RaggedClips* rc) {
+    ProfScope prof(s, rc ? "enhance_stats_kernel<RAGGED>" : "enhance_stats_kernel", 16.0 * batch * frames, 48.0 * batch * frames);
     if (rc) hipLaunchKernelGGL(enhance_stats_kernel<true>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, rc->n, rc->mult);
     else hipLaunchKernelGGL(enhance_stats_kernel<false>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, nullptr, 1);
     L3AC_LAUNCH_CHECK();

@@ -42,8 +42,8 @@ struct UpFusedArgs {
     const float* nw;           // ChannelNorm affine [cout]
     const float* nb;
     float eps;
-    const float* yi;           // raw branch signals [batch][frames][4]
-    const float* stats;        // [batch][8] = mean[4], 1 / std[4]
+    const float* yi;           // branch signals [batch][frames][4], centred in place by enhance_stats_kernel
+    const float* stats;        // [batch][8] = mean[4] (0: yi arrives centred; the subtraction that is left is exact), 1 / std[4]
     const float* in_w;         // InstanceNorm affine [4]
     const float* in_b;
     const float* gate_w;       // merge conv [cin][4]

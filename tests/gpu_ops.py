@@ -54,6 +54,18 @@ def legacy_unit(ctx, unit, x_btc, out=None):
     return y
 
 
+def first_block_at(ctx, audio, samples=None, frames=None):
+    """l3ac_op_first_block_at: the stem on audio [B][stride] (GPU), of which each row's first `samples` floats are the clip (default:
+    the whole row), -> [B][frames][d0]; frames > samples: the zero right-padding folded into the load."""
+    b, stride = audio.shape[0], audio.stride(0) if audio.shape[0] > 1 else audio.shape[1]
+    samples = audio.shape[1] if samples is None else samples
+    frames = samples if frames is None else frames
+    y = torch.empty((b, max(frames, 1), ctx.mc.encoder_dims[0]), dtype=torch.float32, device=audio.device)
+    _capi.check(ctx.lib.l3ac_op_first_block_at(ctx.handle, audio.data_ptr(), b, samples, stride, frames, y.data_ptr(), _stream(audio.device)))
+    torch.cuda.synchronize()
+    return y
+
+
 def head(ctx, x_btc):
     """l3ac_op_head: snake -> Conv1d(C -> 1, k7) -> tanh (unless the context's head_pretanh is on), x [B][T][C] -> [B][T]."""
     return op_plain(ctx, "l3ac_op_head", x_btc, x_btc.shape[0], x_btc.shape[1], (x_btc.shape[0], x_btc.shape[1]))
