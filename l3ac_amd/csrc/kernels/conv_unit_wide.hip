@@ -1275,52 +1275,16 @@ int launch_conv_unit_wide(hipStream_t s, const ConvUnitW& w, const float* x, flo
 //   W1(nt): piece 2 b + hh (k block b, hidden half hh), plane p, lane (m, kg): W1[32 nt + 16 hh + m][32 b + 8 kg + j], j = 0..7
 //   W2(nt): piece rt (output row tile), plane p, lane (m, kg): W2[16 rt + m][32 nt + sigma(kg, j)], sigma(kg, j) = j < 4 ? 4 kg + j :
 //           16 + 4 kg + j - 4 — the order in which the activated accumulator tiles become the second product's B operand
-namespace {
-void put_split(std::vector<unsigned char>& img, size_t off, float v) {  // the three bf16 planes of v, 1 KB apart
-    uint16_t pl[3];
-    split3_host(v, pl);
-    for (int p = 0; p < 3; ++p) std::memcpy(img.data() + off + (size_t)p * 1024, &pl[p], 2);
-}
-std::vector<unsigned char> wide_w1_image(const float* w1, int c) {
-    const int h4 = 4 * c, pieces = c / 16;
-    std::vector<unsigned char> img((size_t)(h4 / 32) * pieces * 3072, 0);
-    for (int nt = 0; nt < h4 / 32; ++nt)
-        for (int b = 0; b < c / 32; ++b)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int m = 0; m < 16; ++m)
-                    for (int kg = 0; kg < 4; ++kg)
-                        for (int j = 0; j < 8; ++j)
-                            put_split(img, ((size_t)nt * pieces + 2 * b + hh) * 3072 + (size_t)(16 * kg + m) * 16 + 2 * j,
-                                      w1[(size_t)(32 * nt + 16 * hh + m) * c + 32 * b + 8 * kg + j]);
-    return img;
-}
-std::vector<unsigned char> wide_w2_image(const float* w2, int c) {
-    const int h4 = 4 * c, pieces = c / 16;
-    std::vector<unsigned char> img((size_t)(h4 / 32) * pieces * 3072, 0);
-    for (int nt = 0; nt < h4 / 32; ++nt)
-        for (int rt = 0; rt < pieces; ++rt)
-            for (int m = 0; m < 16; ++m)
-                for (int kg = 0; kg < 4; ++kg)
-                    for (int j = 0; j < 8; ++j) {
-                        const int sigma = j < 4 ? 4 * kg + j : 16 + 4 * kg + j - 4;
-                        put_split(img, ((size_t)nt * pieces + rt) * 3072 + (size_t)(16 * kg + m) * 16 + 2 * j,
-                                  w2[(size_t)(16 * rt + m) * h4 + 32 * nt + sigma]);
-                    }
-    return img;
-}
-}  // namespace
 std::vector<unsigned char> conv_unit_wide_image(const float* w1, const float* w2, int c) {
-    const std::vector<unsigned char> i1 = wide_w1_image(w1, c), i2 = wide_w2_image(w2, c);
-    const size_t t1 = (size_t)(c / 16) * 3072, t2 = t1;
     const int nt_n = 4 * c / 32;
     std::vector<unsigned char> img;
-    img.reserve(i1.size() + i2.size());
-    auto put = [&](const std::vector<unsigned char>& v, size_t off, size_t n) { img.insert(img.end(), v.begin() + off, v.begin() + off + n); };
-    put(i1, 0, t1);
-    for (int nt = 0; nt + 1 < nt_n; ++nt) {
-        put(i1, (size_t)(nt + 1) * t1, t1);
-        put(i2, (size_t)nt * t2, t2);
+    img.reserve((size_t)nt_n * 2 * (c / 16) * 3072);
+    for (int nt = 0; nt <= nt_n; ++nt) {  // step nt of the stream: W1(nt) W2(nt - 1)
+        if (nt < nt_n)
+            for (int b = 0; b < c / 32; ++b)
+                for (int hh = 0; hh < 2; ++hh) ring_put_piece(img, w1, c, 4 * c, c, 32 * nt + 16 * hh, 32 * b, RING_K_CONTIGUOUS);
+        if (nt > 0)
+            for (int rt = 0; rt < c / 16; ++rt) ring_put_piece(img, w2, 4 * c, c, 4 * c, 16 * rt, 32 * (nt - 1));
     }
-    put(i2, (size_t)(nt_n - 1) * t2, t2);
     return img;
 }

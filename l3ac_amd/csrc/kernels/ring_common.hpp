@@ -74,15 +74,21 @@ __device__ __forceinline__ void ring_static_for(F&& f) {
 }
 
 
+// the k a lane's j-th value comes from: sigma(g, j) where the other operand is made of accumulator tiles (above), 8 g + j where it is
+// loaded as 8 consecutive k per lane
+enum RingKOrder { RING_K_SIGMA, RING_K_CONTIGUOUS };
+
 // one piece: 16 rows x 32 k of a row-major [n][ld] matrix (rows >= n_rows / columns >= n_cols: zeros) as the three bf16 planes of
 // the operand fragment — lane (m = lane & 15, g = lane >> 4) holds the 8 values W[row0 + m][k0 + sigma(g, j)], j = 0 .. 7
-inline void ring_put_piece(std::vector<unsigned char>& img, const float* w, int64_t ld, int n_rows, int n_cols, int row0, int k0) {
+// (RING_K_CONTIGUOUS: W[row0 + m][k0 + 8 g + j])
+inline void ring_put_piece(std::vector<unsigned char>& img, const float* w, int64_t ld, int n_rows, int n_cols, int row0, int k0,
+                           RingKOrder order = RING_K_SIGMA) {
     const size_t base = img.size();
     img.resize(base + 3072, 0);
     for (int g = 0; g < 4; ++g)
         for (int m = 0; m < 16; ++m)
             for (int j = 0; j < 8; ++j) {
-                const int k = k0 + (j < 4 ? 4 * g + j : 16 + 4 * g + j - 4);
+                const int k = k0 + (order == RING_K_CONTIGUOUS ? 8 * g + j : j < 4 ? 4 * g + j : 16 + 4 * g + j - 4);
                 const int r = row0 + m;
                 const float v = (r < n_rows && k < n_cols) ? w[(int64_t)r * ld + k] : 0.f;
                 uint16_t pl[3];

@@ -4,25 +4,36 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 
 namespace {
 
 constexpr int HEADS = 6;  // LocalTrans.builder (reference l3ac/local_trans.py:51)
 
 struct Builder {
+    l3ac_ctx* ctx = nullptr;
     std::unordered_map<std::string, const l3ac_tensor*> map;
     std::vector<float> host;  // staging image of the device arena
     float* dev = nullptr;
     size_t cap = 0;
     std::string err;
-    struct GemmWeight { const float* d; int n, k; };
-    std::vector<GemmWeight> gemm_ws;  // [n][k] weights that get a split image
-    struct ExtraImage { std::vector<unsigned char> bytes; const unsigned char** target; };
-    std::vector<ExtraImage> extra_imgs;  // other bf16x3 images (fused kernels), bound to *target after the upload
+    // every weight image (bf16x3 split images of the GEMM weights, the fused kernels' streams) in the order of the walk: `write` puts it
+    // into the staging copy of the one device allocation they share, *target is bound to its place there
+    struct Image { size_t bytes; std::function<void(unsigned char*)> write; const unsigned char** target; };
+    std::vector<Image> images;
+    bool trans_stacks = false;  // some LocalTrans stack has its trans_stack_kernel image
     const float* host_of(const float* d) const { return host.data() + (d - dev); }
 
+    void image(std::vector<unsigned char> img, const unsigned char** target) {
+        const size_t bytes = img.size();
+        images.push_back({bytes, [img = std::move(img)](unsigned char* out) { std::memcpy(out, img.data(), img.size()); }, target});
+    }
+    // an [n][k] weight of the arena (its final layout) as a GEMM operand: queues its split image, bound to the weight's slot in split_img
+    // (the largest images: built straight into the staging copy)
     const float* gemm(const float* d, int n, int k) {
-        if (d && gemm_split_eligible(n, k)) gemm_ws.push_back({d, n, k});
+        if (d && err.empty() && gemm_split_eligible(n, k))
+            images.push_back({(size_t)gemm_split_image_bytes(n, k), [=](unsigned char* out) { gemm_split_image_host(host_of(d), k, n, k, out); },
+                              &ctx->split_img[d]});
         return d;
     }
     const float* find(const std::string& name, int64_t numel) {
@@ -39,14 +50,13 @@ struct Builder {
         }
         return it->second->data;
     }
-    // reserve n floats in the arena (256-byte aligned), return {host pointer, device pointer}
+    // reserve n floats in the arena (256-byte aligned), return {host pointer, device pointer}: both null when the arena is full
     float* alloc(size_t n, const float** dptr) {
         const size_t off = (host.size() + 63) / 64 * 64;
         if (off + n > cap) {
             if (err.empty()) err = "internal: weight arena overflow";
             *dptr = nullptr;
-            static float sink[1];
-            return sink;
+            return nullptr;
         }
         host.resize(off + n, 0.f);
         *dptr = dev + off;
@@ -79,6 +89,51 @@ struct Builder {
             for (int ch = 0; ch < c; ++ch)
                 for (int j = 0; j < 7; ++j) h[(size_t)j * c + ch] = src[(size_t)ch * 7 + j];
         return d;
+    }
+    // weight [n][k] -> [k][n]
+    const float* transposed(const std::string& name, int n, int k) {
+        const float* src = find(name, (int64_t)n * k);
+        const float* d = nullptr;
+        float* h = alloc((size_t)k * n, &d);
+        if (src && d)
+            for (int o = 0; o < n; ++o)
+                for (int i = 0; i < k; ++i) h[(size_t)i * n + o] = src[(size_t)o * k + i];
+        return d;
+    }
+    // FeedForward's first weight [2 * ffi][dim] -> (value, gate) 32-row tiles interleaved, zero padded: [ff_n][dim]
+    const float* ff_value_gate(const std::string& name, int ffi, int dim, int ff_n) {
+        const float* src = find(name, (int64_t)2 * ffi * dim);
+        const float* d = nullptr;
+        float* h = alloc((size_t)ff_n * dim, &d);
+        if (src && d)
+            for (int j = 0; j < ffi; ++j) {
+                const int jb = j / 32, r = j % 32;
+                std::memcpy(h + (size_t)(64 * jb + r) * dim, src + (size_t)j * dim, dim * sizeof(float));
+                std::memcpy(h + (size_t)(64 * jb + 32 + r) * dim, src + (size_t)(ffi + j) * dim, dim * sizeof(float));
+            }
+        return d;
+    }
+    // FeedForward's second weight [dim][ffi] -> [dim][ff_pad] zero padded along k
+    const float* ff_padded(const std::string& name, int dim, int ffi, int ff_pad) {
+        const float* src = find(name, (int64_t)dim * ffi);
+        const float* d = nullptr;
+        float* h = alloc((size_t)dim * ff_pad, &d);
+        if (src && d)
+            for (int o = 0; o < dim; ++o) std::memcpy(h + (size_t)o * ff_pad, src + (size_t)o * ffi, ffi * sizeof(float));
+        return d;
+    }
+    // the trend convs of n branches, p.blocks.<i>.1 = Conv1d weight [co][1][7] and bias [co], packed as [n][co][7] and [n][co]
+    void trend(const std::string& p, int n, int co, const float** tw, const float** tb) {
+        float* hw = alloc((size_t)n * co * 7, tw);
+        float* hb = alloc((size_t)n * co, tb);
+        for (int i = 0; i < n; ++i) {
+            const float* w = find(p + ".blocks." + std::to_string(i) + ".1.weight", co * 7);
+            const float* bb = find(p + ".blocks." + std::to_string(i) + ".1.bias", co);
+            if (w && bb && hw && hb) {
+                std::memcpy(hw + (size_t)i * co * 7, w, (size_t)co * 7 * sizeof(float));
+                std::memcpy(hb + (size_t)i * co, bb, co * sizeof(float));
+            }
+        }
     }
     // snake: 1 / (alpha + 1e-8) evaluated in fp32 exactly as layers.py:32 does
     const float* inv_alpha(const std::string& name, int n) {
@@ -122,8 +177,20 @@ const float* build_bias_table(Builder& b, const std::string& prefix, int dim, in
     return d;
 }
 
-ConvUnitW build_conv_unit(Builder& b, const std::string& p, int c) {
-    ConvUnitW u{};
+// One builder per block kind: it reads the block `p` of the reference's module list into the block it is given, queues the block's weight
+// images — only when every tensor of the network so far was found: the images are made from the arena's staging copy — and enters the
+// block into the name index of the l3ac_op_* entry points.  The images' targets point into the block: it must not move afterwards.
+
+void build_first_block(Builder& b, FirstBlockW& f, const std::string& p, int d0) {  // modules.py:71-93
+    b.trend(p, 5, 4, &f.tw, &f.tb);
+    f.d0 = d0;
+    f.w1 = b.copy(p + ".conv_1.weight", 80 * 20);
+    f.b1 = b.copy(p + ".conv_1.bias", 80);
+    f.w2 = b.transposed(p + ".conv_2.weight", d0, 81);  // [81][d0]
+    f.b2 = b.copy(p + ".conv_2.bias", d0);
+}
+
+void build_conv_unit(Builder& b, ConvUnitW& u, const std::string& p, int c) {
     u.c = c;
     u.dw_w = b.dwconv(p + ".dw_conv.weight", c);
     u.dw_b = b.copy(p + ".dw_conv.bias", c);
@@ -137,11 +204,93 @@ ConvUnitW build_conv_unit(Builder& b, const std::string& p, int c) {
     u.beta = b.copy(p + ".grn.beta", 4 * c);
     u.w2 = b.gemm(b.copy(p + ".pw_conv2.weight", (int64_t)4 * c * c), c, 4 * c);
     u.b2 = b.copy(p + ".pw_conv2.bias", c);
-    return u;
+    if (b.err.empty()) {
+        if (conv_unit_wide_supported(c)) {  // (C = 96 .. 256; on the exact route C = 96 takes conv_unit_fused_kernel: fp32 weights)
+            b.image(conv_unit_wide_image(b.host_of(u.w1), b.host_of(u.w2), c), &u.wide_img);
+        } else if (conv_unit_fused_supported(c)) {
+            b.image(conv_unit_w1_image(b.host_of(u.w1), c), &u.w1_img);
+            b.image(conv_unit_w2_image(b.host_of(u.w2), c), &u.w2_img);
+            if (conv_unit_ring_supported(c)) b.image(conv_unit_ring_image(b.host_of(u.w1), b.host_of(u.w2), c), &u.ring_img);
+        }
+    }
+    b.ctx->by_unit[p] = &u;
 }
 
-LocalTransW build_local_trans(Builder& b, l3ac_ctx* ctx, const std::string& p, int window, int depth) {
-    LocalTransW t{};
+// Conv1d(k = stride): with `norm` the layer p.0 of a Sequential whose p.1 is the ChannelNorm (encoder), else p itself (DownTrans)
+void build_down(Builder& b, DownW& d, const std::string& p, int cin, int cout, int stride, bool norm) {
+    d.cin = cin;
+    d.cout = cout;
+    d.stride = stride;
+    const std::string conv = norm ? p + ".0" : p;
+    d.w = b.gemm(b.conv(conv + ".weight", cout, cin, stride), cout, stride * cin);
+    d.b = b.copy(conv + ".bias", cout);
+    if (norm) {
+        d.nw = b.copy(p + ".1.weight", cout);
+        d.nb = b.copy(p + ".1.bias", cout);
+        if (b.err.empty() && down_exact_supported(cin, stride, cout)) b.image(down_exact_image(b.host_of(d.w), cin * stride, cout), &d.exact_img);
+    }
+    b.ctx->by_down[p] = &d;
+}
+
+// `split`: the conv runs as a GEMM that may take the bf16x3 route (the decoder's; the encoder's output conv stays on fp32)
+void build_conv_k3(Builder& b, ConvK3W& k, const std::string& p, int cin, int cout, bool split) {
+    k.cin = cin;
+    k.cout = cout;
+    k.w = b.conv(p + ".weight", cout, cin, 3);
+    if (split) b.gemm(k.w, cout, 3 * cin);
+    k.b = b.copy(p + ".bias", cout);
+    b.ctx->by_k3[p] = &k;
+}
+
+void build_enhance(Builder& b, EnhW& e, const std::string& p, int c) {
+    e.c = c;
+    b.trend(p, 4, 1, &e.t.tw, &e.t.tb);
+    e.in_w = b.copy(p + ".merge_layer.0.weight", 4);
+    e.in_b = b.copy(p + ".merge_layer.0.bias", 4);
+    e.gate_w = b.copy(p + ".merge_layer.1.weight", (int64_t)c * 4);
+    e.gate_b = b.copy(p + ".merge_layer.1.bias", c);
+    b.ctx->by_enh[p] = &e;
+}
+
+void build_up(Builder& b, UpW& u, const std::string& p, int cin, int cout, int scale) {
+    u.cin = cin;
+    u.cout = cout;
+    u.scale = scale;
+    u.w = b.gemm(b.copy(p + ".0.weight", (int64_t)cout * cin), cout, cin);
+    u.b = b.copy(p + ".0.bias", cout);
+    u.nw = b.copy(p + ".2.weight", cout);
+    u.nb = b.copy(p + ".2.bias", cout);
+    if (b.err.empty() && up_fused_supported(cin, cout)) b.image(up_fused_image(b.host_of(u.w), cin, cout), &u.fused_img);
+    b.ctx->by_up[p] = &u;
+}
+
+void build_legacy_unit(Builder& b, LegacyW& l, const std::string& p, int c, int dil) {
+    l.c = c;
+    l.dil = dil;
+    l.a0 = b.copy(p + ".0.alpha", c);
+    l.ia0 = b.inv_alpha(p + ".0.alpha", c);
+    l.w1 = b.conv(p + ".1.weight", c, c, 7);
+    l.b1 = b.copy(p + ".1.bias", c);
+    l.a1 = b.copy(p + ".2.alpha", c);
+    l.ia1 = b.inv_alpha(p + ".2.alpha", c);
+    l.w2 = b.copy(p + ".3.weight", (int64_t)c * c);
+    l.b2 = b.copy(p + ".3.bias", c);
+    if (b.err.empty() && last_block_fused_supported(c, 9)) {  // (9: the largest dilation of the last block's three units)
+        b.image(legacy_w1_image(b.host_of(l.w1), c), &l.w1_img);
+        b.image(legacy_w2_image(b.host_of(l.w2), c), &l.w2_img);
+    }
+}
+
+void build_head(Builder& b, HeadW& h, const std::string& p, int c) {
+    h.c = c;
+    h.alpha = b.copy(p + ".1.alpha", c);
+    h.inv_alpha = b.inv_alpha(p + ".1.alpha", c);
+    h.w = b.conv(p + ".2.weight", 1, c, 7);  // [1][7][c]
+    h.b = b.copy(p + ".2.bias", 1);
+}
+
+void build_local_trans(Builder& b, LocalTransW& t, const std::string& p, int window, int depth) {
+    const l3ac_ctx* ctx = b.ctx;
     t.window = window;
     const int dim = ctx->cfg.feature_dim;
     const int inner = ctx->inner, ffi = ctx->ff_inner;
@@ -155,33 +304,30 @@ LocalTransW build_local_trans(Builder& b, l3ac_ctx* ctx, const std::string& p, i
         w.wout = b.gemm(b.copy(a + ".to_out.weight", (int64_t)dim * inner), dim, inner);
         w.ln2w = b.copy(f + ".0.weight", dim);
         w.ln2b = b.copy(f + ".0.bias", dim);
-        {  // ff.1 [2*ffi][dim] -> (value, gate) 32-row tiles interleaved, zero padded: [ff_n][dim]
-            const float* src = b.find(f + ".1.weight", (int64_t)2 * ffi * dim);
-            const float* d = nullptr;
-            float* h = b.alloc((size_t)ctx->ff_n * dim, &d);
-            if (src && d) {
-                for (int jb = 0; jb * 32 < ffi; ++jb)
-                    for (int r = 0; r < 32; ++r) {
-                        const int j = jb * 32 + r;
-                        if (j >= ffi) continue;
-                        std::memcpy(h + (size_t)(64 * jb + r) * dim, src + (size_t)j * dim, dim * sizeof(float));
-                        std::memcpy(h + (size_t)(64 * jb + 32 + r) * dim, src + (size_t)(ffi + j) * dim, dim * sizeof(float));
-                    }
-            }
-            w.wff1 = b.gemm(d, ctx->ff_n, dim);
-        }
-        {  // ff.4 [dim][ffi] -> [dim][ff_pad] zero padded along k
-            const float* src = b.find(f + ".4.weight", (int64_t)dim * ffi);
-            const float* d = nullptr;
-            float* h = b.alloc((size_t)dim * ctx->ff_pad, &d);
-            if (src && d)
-                for (int o = 0; o < dim; ++o) std::memcpy(h + (size_t)o * ctx->ff_pad, src + (size_t)o * ffi, ffi * sizeof(float));
-            w.wff2 = b.gemm(d, dim, ctx->ff_pad);
-        }
+        w.wff1 = b.gemm(b.ff_value_gate(f + ".1.weight", ffi, dim, ctx->ff_n), ctx->ff_n, dim);
+        w.wff2 = b.gemm(b.ff_padded(f + ".4.weight", dim, ffi, ctx->ff_pad), dim, ctx->ff_pad);
         t.layers.push_back(w);
     }
     t.bias_table = build_bias_table(b, p + ".dynamic_pos_bias", dim, window);
-    return t;
+    // the stack as trans_stack_kernel takes it
+    if (b.err.empty() && trans_stack_supported(dim, ctx->dim_head, HEADS, ffi, 1, window, depth)) {
+        const float* d = nullptr;
+        float* ln = b.alloc((size_t)depth * 4 * dim, &d);
+        if (d) {
+            t.stack_ln = d;
+            std::vector<unsigned char> img;
+            img.reserve((size_t)depth * (size_t)trans_stack_layer_image_bytes());
+            for (int l = 0; l < depth; ++l) {
+                const TransLayerW& w = t.layers[l];
+                const float* srcs[4] = {w.ln1w, w.ln1b, w.ln2w, w.ln2b};
+                for (int q = 0; q < 4; ++q) std::memcpy(ln + ((size_t)l * 4 + q) * dim, b.host_of(srcs[q]), dim * sizeof(float));
+                trans_stack_layer_image(img, b.host_of(w.wqkv), b.host_of(w.wout), b.host_of(w.wff1), ctx->ff_n, b.host_of(w.wff2), ctx->ff_pad);
+            }
+            b.image(std::move(img), &t.stack_img);
+            b.trans_stacks = true;
+        }
+    }
+    b.ctx->by_trans[p] = &t;
 }
 
 int free_buf(float*& p) {
@@ -218,7 +364,21 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
     const bool compressed = c.en_coder_compress_rate != 1;
     if (compressed) L3AC_REQUIRE(c.en_coder_depth >= 2, "compressed en_decoder needs en_coder_depth >= 2");
 
+    // Every container of blocks gets its final size here, from the config alone: the walk below fills the blocks in place and none of them
+    // moves again — the queued images' targets and the name index point into them.
+    ctx->enc_units.resize(c.n_enc);
+    for (int i = 0; i < c.n_enc; ++i) ctx->enc_units[i].resize(std::max(c.enc_depths[i], 0));
+    ctx->enc_down.resize(c.n_enc - 1);
+    ctx->en_enc.resize(compressed ? 2 : 1);
+    ctx->en_dec.resize(compressed ? 2 : 1);
+    ctx->dec_units.resize(c.n_dec - 1);
+    for (int i = 0; i + 1 < c.n_dec; ++i) ctx->dec_units[i].resize(std::max(c.dec_depths[i], 0));
+    ctx->dec_enh.resize(c.n_dec - 1);
+    ctx->dec_up.resize(c.n_dec - 1);
+    ctx->legacy.resize(3);
+
     Builder b;
+    b.ctx = ctx;
     int64_t total = 0;
     for (int i = 0; i < n_tensors; ++i) {
         L3AC_REQUIRE(tensors[i].name && tensors[i].data && tensors[i].numel > 0, "tensor %d is malformed", i);
@@ -231,97 +391,34 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
     b.host.reserve(b.cap);
     ctx->arena_floats = b.cap;
 
-    // ---- encoder (modules.py:71-116) ------------------------------------------------------------------
-    {
-        const std::string p = "encoder.blocks.0";
-        const float* d = nullptr;
-        float* tw = b.alloc(5 * 4 * 7, &d);
-        ctx->first.tw = d;
-        float* tb = b.alloc(5 * 4, &d);
-        ctx->first.tb = d;
-        for (int i = 0; i < 5; ++i) {
-            const float* w = b.find(p + ".blocks." + std::to_string(i) + ".1.weight", 28);
-            const float* bb = b.find(p + ".blocks." + std::to_string(i) + ".1.bias", 4);
-            if (w && bb) {
-                std::memcpy(tw + i * 28, w, 28 * sizeof(float));
-                std::memcpy(tb + i * 4, bb, 4 * sizeof(float));
-            }
-        }
-        const int d0 = c.enc_dims[0];
-        ctx->first.d0 = d0;
-        ctx->first.w1 = b.copy(p + ".conv_1.weight", 80 * 20);
-        ctx->first.b1 = b.copy(p + ".conv_1.bias", 80);
-        const float* w2 = b.find(p + ".conv_2.weight", (int64_t)d0 * 81);
-        float* w2t = b.alloc((size_t)81 * d0, &d);  // transposed to [81][d0]
-        ctx->first.w2 = d;
-        if (w2)
-            for (int o = 0; o < d0; ++o)
-                for (int i = 0; i < 81; ++i) w2t[(size_t)i * d0 + o] = w2[(size_t)o * 81 + i];
-        ctx->first.b2 = b.copy(p + ".conv_2.bias", d0);
+    // ---- encoder (modules.py:71-116): first block, per stage its ConvUnits [and the down layer to the next], output conv ----------------
+    // the coders' module lists: each call names the next entry
+    int blk = 0;
+    auto enc = [&blk] { return "encoder.blocks." + std::to_string(blk++); };
+    auto dec = [&blk] { return "decoder.blocks." + std::to_string(blk++); };
+    build_first_block(b, ctx->first, enc(), c.enc_dims[0]);
+    for (int i = 0; i < c.n_enc; ++i) {
+        const std::string stage = enc();
+        for (size_t j = 0; j < ctx->enc_units[i].size(); ++j)
+            build_conv_unit(b, ctx->enc_units[i][j], stage + "." + std::to_string(j) + ".module", c.enc_dims[i]);
+        if (i + 1 == c.n_enc) break;
+        L3AC_REQUIRE(c.compress_rates[i] >= 1, "bad compress rate");
+        build_down(b, ctx->enc_down[i], enc(), c.enc_dims[i], c.enc_dims[i + 1], c.compress_rates[i], true);
     }
-    ctx->enc_units.assign(c.n_enc, {});
-    ctx->enc_down.assign(c.n_enc - 1, {});
-    int blk = 1;
-    for (int i = 0; i + 1 < c.n_enc; ++i) {
-        for (int j = 0; j < c.enc_depths[i]; ++j)
-            ctx->enc_units[i].push_back(build_conv_unit(b, "encoder.blocks." + std::to_string(blk) + "." + std::to_string(j) + ".module", c.enc_dims[i]));
-        DownW& d = ctx->enc_down[i];
-        d.cin = c.enc_dims[i];
-        d.cout = c.enc_dims[i + 1];
-        d.stride = c.compress_rates[i];
-        L3AC_REQUIRE(d.stride >= 1, "bad compress rate");
-        const std::string p = "encoder.blocks." + std::to_string(blk + 1);
-        d.w = b.gemm(b.conv(p + ".0.weight", d.cout, d.cin, d.stride), d.cout, d.stride * d.cin);
-        d.b = b.copy(p + ".0.bias", d.cout);
-        d.nw = b.copy(p + ".1.weight", d.cout);
-        d.nb = b.copy(p + ".1.bias", d.cout);
-        blk += 2;
-    }
-    for (int j = 0; j < c.enc_depths[c.n_enc - 1]; ++j)
-        ctx->enc_units[c.n_enc - 1].push_back(build_conv_unit(b, "encoder.blocks." + std::to_string(blk) + "." + std::to_string(j) + ".module", c.enc_dims[c.n_enc - 1]));
-    ctx->enc_out.cin = c.enc_dims[c.n_enc - 1];
-    ctx->enc_out.cout = c.feature_dim;
-    ctx->enc_out.w = b.conv("encoder.blocks." + std::to_string(blk + 1) + ".weight", c.feature_dim, ctx->enc_out.cin, 3);
-    ctx->enc_out.b = b.copy("encoder.blocks." + std::to_string(blk + 1) + ".bias", c.feature_dim);
-    const std::string enc_out_name = "encoder.blocks." + std::to_string(blk + 1);
+    build_conv_k3(b, ctx->enc_out, enc(), c.enc_dims[c.n_enc - 1], c.feature_dim, false);
 
-    // ---- local-attention stacks (local_trans.py:56-94, :129-186; en_codec.py:25-44) -------------------------
+    // ---- local-attention stacks in execution order (local_trans.py:56-94, :129-186; en_codec.py:25-44) ------------------------------
     const int win = c.en_coder_window_size;
     if (compressed) {
         const int r = c.en_coder_compress_rate;
-        ctx->en_enc.push_back(build_local_trans(b, ctx, "en_encoder.down_trans.trans", win * r, 3 / 2));
-        ctx->en_enc.push_back(build_local_trans(b, ctx, "en_encoder.local_trans", win, 3 - 3 / 2));
-        ctx->en_down.cin = ctx->en_down.cout = c.feature_dim;
-        ctx->en_down.stride = r;
-        ctx->en_down.w = b.gemm(b.conv("en_encoder.down_trans.down_layer.weight", c.feature_dim, c.feature_dim, r), c.feature_dim, r * c.feature_dim);
-        ctx->en_down.b = b.copy("en_encoder.down_trans.down_layer.bias", c.feature_dim);
-        ctx->en_dec.push_back(build_local_trans(b, ctx, "en_decoder.local_trans", win, c.en_coder_depth - 2));
-        ctx->en_dec.push_back(build_local_trans(b, ctx, "en_decoder.up_trans.trans", win * r, 2));
+        build_local_trans(b, ctx->en_enc[0], "en_encoder.down_trans.trans", win * r, 3 / 2);
+        build_local_trans(b, ctx->en_enc[1], "en_encoder.local_trans", win, 3 - 3 / 2);
+        build_down(b, ctx->en_down, "en_encoder.down_trans.down_layer", c.feature_dim, c.feature_dim, r, false);
+        build_local_trans(b, ctx->en_dec[0], "en_decoder.local_trans", win, c.en_coder_depth - 2);
+        build_local_trans(b, ctx->en_dec[1], "en_decoder.up_trans.trans", win * r, 2);
     } else {
-        ctx->en_enc.push_back(build_local_trans(b, ctx, "en_encoder.local_trans", win, 1));
-        ctx->en_dec.push_back(build_local_trans(b, ctx, "en_decoder.local_trans", win, c.en_coder_depth));
-    }
-
-    // the stacks as trans_stack_kernel takes them (the stack vectors no longer reallocate: the image targets stay valid)
-    if (b.err.empty()) {
-        const int dim = c.feature_dim;
-        for (auto* stacks : {&ctx->en_enc, &ctx->en_dec})
-            for (LocalTransW& t : *stacks) {
-                if (!trans_stack_supported(dim, ctx->dim_head, HEADS, ctx->ff_inner, 1, t.window, (int)t.layers.size())) continue;
-                const float* d = nullptr;
-                float* ln = b.alloc(t.layers.size() * 4 * (size_t)dim, &d);
-                if (!d) continue;
-                t.stack_ln = d;
-                std::vector<unsigned char> img;
-                img.reserve(t.layers.size() * (size_t)trans_stack_layer_image_bytes());
-                for (size_t l = 0; l < t.layers.size(); ++l) {
-                    const TransLayerW& w = t.layers[l];
-                    const float* srcs[4] = {w.ln1w, w.ln1b, w.ln2w, w.ln2b};
-                    for (int q = 0; q < 4; ++q) std::memcpy(ln + (l * 4 + q) * dim, b.host_of(srcs[q]), dim * sizeof(float));
-                    trans_stack_layer_image(img, b.host_of(w.wqkv), b.host_of(w.wout), b.host_of(w.wff1), ctx->ff_n, b.host_of(w.wff2), ctx->ff_pad);
-                }
-                b.extra_imgs.push_back({std::move(img), &t.stack_img});
-            }
+        build_local_trans(b, ctx->en_enc[0], "en_encoder.local_trans", win, 1);
+        build_local_trans(b, ctx->en_dec[0], "en_decoder.local_trans", win, c.en_coder_depth);
     }
 
     // ---- quantiser (vq/__init__.py:13-14) -------------------------------------------------------------
@@ -330,100 +427,22 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
     ctx->q_wout = b.copy("quantizer.project_out.weight", (int64_t)c.feature_dim * c.n_levels);
     ctx->q_bout = b.copy("quantizer.project_out.bias", c.feature_dim);
 
-    // ---- decoder (modules.py:135-201) -----------------------------------------------------------------
-    ctx->dec_in.cin = c.feature_dim;
-    ctx->dec_in.cout = c.dec_dims[0];
-    ctx->dec_in.w = b.gemm(b.conv("decoder.blocks.0.weight", c.dec_dims[0], c.feature_dim, 3), c.dec_dims[0], 3 * c.feature_dim);
-    ctx->dec_in.b = b.copy("decoder.blocks.0.bias", c.dec_dims[0]);
-    ctx->dec_units.assign(c.n_dec - 1, {});
-    ctx->dec_enh.assign(c.n_dec - 1, {});
-    ctx->dec_up.assign(c.n_dec - 1, {});
-    blk = 1;
+    // ---- decoder (modules.py:135-201): input conv, per stage its ConvUnits, EnhanceBlock and up layer, last block ----------------------
+    blk = 0;
+    build_conv_k3(b, ctx->dec_in, dec(), c.feature_dim, c.dec_dims[0], true);
     for (int i = 0; i + 1 < c.n_dec; ++i) {
-        const int ci = c.dec_dims[i], co = c.dec_dims[i + 1];
-        for (int j = 0; j < c.dec_depths[i]; ++j)
-            ctx->dec_units[i].push_back(build_conv_unit(b, "decoder.blocks." + std::to_string(blk) + "." + std::to_string(j) + ".module", ci));
-        EnhW& e = ctx->dec_enh[i];
-        e.c = ci;
-        const std::string ep = "decoder.blocks." + std::to_string(blk + 1);
-        const float* d = nullptr;
-        float* tw = b.alloc(4 * 7, &d);
-        e.t.tw = d;
-        float* tb = b.alloc(4, &d);
-        e.t.tb = d;
-        for (int p = 0; p < 4; ++p) {
-            const float* w = b.find(ep + ".blocks." + std::to_string(p) + ".1.weight", 7);
-            const float* bb = b.find(ep + ".blocks." + std::to_string(p) + ".1.bias", 1);
-            if (w && bb) {
-                std::memcpy(tw + p * 7, w, 7 * sizeof(float));
-                tb[p] = bb[0];
-            }
-        }
-        e.in_w = b.copy(ep + ".merge_layer.0.weight", 4);
-        e.in_b = b.copy(ep + ".merge_layer.0.bias", 4);
-        e.gate_w = b.copy(ep + ".merge_layer.1.weight", (int64_t)ci * 4);
-        e.gate_b = b.copy(ep + ".merge_layer.1.bias", ci);
-        UpW& u = ctx->dec_up[i];
-        u.cin = ci;
-        u.cout = co;
-        u.scale = c.decode_rates[i];
-        const std::string up = "decoder.blocks." + std::to_string(blk + 2);
-        u.w = b.gemm(b.copy(up + ".0.weight", (int64_t)co * ci), co, ci);
-        u.b = b.copy(up + ".0.bias", co);
-        u.nw = b.copy(up + ".2.weight", co);
-        u.nb = b.copy(up + ".2.bias", co);
-        blk += 3;
+        const std::string stage = dec();
+        for (size_t j = 0; j < ctx->dec_units[i].size(); ++j)
+            build_conv_unit(b, ctx->dec_units[i][j], stage + "." + std::to_string(j) + ".module", c.dec_dims[i]);
+        build_enhance(b, ctx->dec_enh[i], dec(), c.dec_dims[i]);
+        build_up(b, ctx->dec_up[i], dec(), c.dec_dims[i], c.dec_dims[i + 1], c.decode_rates[i]);
     }
     {
+        const std::string last = dec() + ".block";
         const int cl = c.dec_dims[c.n_dec - 1];
-        const std::string lp = "decoder.blocks." + std::to_string(blk) + ".block";
         const int dils[3] = {1, 3, 9};
-        for (int u = 0; u < 3; ++u) {
-            const std::string p = lp + ".0." + std::to_string(u) + ".module.block";
-            LegacyW l{};
-            l.c = cl;
-            l.dil = dils[u];
-            l.a0 = b.copy(p + ".0.alpha", cl);
-            l.ia0 = b.inv_alpha(p + ".0.alpha", cl);
-            l.w1 = b.conv(p + ".1.weight", cl, cl, 7);
-            l.b1 = b.copy(p + ".1.bias", cl);
-            l.a1 = b.copy(p + ".2.alpha", cl);
-            l.ia1 = b.inv_alpha(p + ".2.alpha", cl);
-            l.w2 = b.copy(p + ".3.weight", (int64_t)cl * cl);
-            l.b2 = b.copy(p + ".3.bias", cl);
-            ctx->legacy.push_back(l);
-        }
-        if (b.err.empty()) {  // (the unit vectors no longer reallocate: the image targets stay valid)
-            for (auto* stages : {&ctx->enc_units, &ctx->dec_units})
-                for (auto& stage : *stages)
-                    for (ConvUnitW& u : stage)
-                        if (conv_unit_wide_supported(u.c)) {  // (C = 96 .. 256; on the exact route C = 96 takes conv_unit_fused_kernel: fp32 weights)
-                            b.extra_imgs.push_back({conv_unit_wide_image(b.host_of(u.w1), b.host_of(u.w2), u.c), &u.wide_img});
-                        } else if (conv_unit_fused_supported(u.c)) {
-                            b.extra_imgs.push_back({conv_unit_w1_image(b.host_of(u.w1), u.c), &u.w1_img});
-                            b.extra_imgs.push_back({conv_unit_w2_image(b.host_of(u.w2), u.c), &u.w2_img});
-                            if (conv_unit_ring_supported(u.c))
-                                b.extra_imgs.push_back({conv_unit_ring_image(b.host_of(u.w1), b.host_of(u.w2), u.c), &u.ring_img});
-                        }
-        }
-        if (b.err.empty()) {  // (ctx->dec_up was sized before the loop above: the targets stay valid)
-            for (UpW& u : ctx->dec_up)
-                if (up_fused_supported(u.cin, u.cout)) b.extra_imgs.push_back({up_fused_image(b.host_of(u.w), u.cin, u.cout), &u.fused_img});
-            for (DownW& d : ctx->enc_down)  // (sized before the loops above as well)
-                if (d.nw && down_exact_supported(d.cin, d.stride, d.cout))
-                    b.extra_imgs.push_back({down_exact_image(b.host_of(d.w), d.cin * d.stride, d.cout), &d.exact_img});
-        }
-        if (b.err.empty() && last_block_fused_supported(cl, 9)) {  // (ctx->legacy no longer reallocates: the targets stay valid)
-            for (LegacyW& l : ctx->legacy) {
-                b.extra_imgs.push_back({legacy_w1_image(b.host_of(l.w1), cl), &l.w1_img});
-                b.extra_imgs.push_back({legacy_w2_image(b.host_of(l.w2), cl), &l.w2_img});
-            }
-        }
-        ctx->head.c = cl;
-        ctx->head.alpha = b.copy(lp + ".1.alpha", cl);
-        ctx->head.inv_alpha = b.inv_alpha(lp + ".1.alpha", cl);
-        ctx->head.w = b.conv(lp + ".2.weight", 1, cl, 7);  // [1][7][c]
-        ctx->head.b = b.copy(lp + ".2.bias", 1);
+        for (int u = 0; u < 3; ++u) build_legacy_unit(b, ctx->legacy[u], last + ".0." + std::to_string(u) + ".module.block", cl, dils[u]);
+        build_head(b, ctx->head, last, cl);
     }
     if (!b.err.empty()) {
         l3ac_set_error("%s", b.err.c_str());
@@ -431,27 +450,20 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
     }
     L3AC_HIP_CHECK(hipMemcpy(ctx->arena, b.host.data(), b.host.size() * sizeof(float), hipMemcpyHostToDevice));
 
-    // ---- bf16x3 split images of the GEMM weights (from the arena's host staging copy: final layouts) and of the
-    //      fused kernels' weights, in one device allocation ------------------------------------------------------
+    // ---- the weight images, each padded to 256 bytes, in one device allocation ---------------------------------------------------------
     {
         auto pad = [](size_t n) { return (n + 255) / 256 * 256; };
         size_t total_img = 0;
-        for (const auto& g : b.gemm_ws) total_img += pad((size_t)gemm_split_image_bytes(g.n, g.k));
-        for (const auto& e : b.extra_imgs) total_img += pad(e.bytes.size());
+        for (const auto& e : b.images) total_img += pad(e.bytes);
         if (total_img) {
             std::vector<unsigned char> himg(total_img, 0);
             L3AC_HIP_CHECK(hipMalloc((void**)&ctx->img_arena, total_img));
             ctx->img_bytes = total_img;
             size_t off = 0;
-            for (const auto& g : b.gemm_ws) {
-                gemm_split_image_host(b.host_of(g.d), g.k, g.n, g.k, himg.data() + off);
-                ctx->split_img[g.d] = ctx->img_arena + off;
-                off += pad((size_t)gemm_split_image_bytes(g.n, g.k));
-            }
-            for (const auto& e : b.extra_imgs) {
-                std::memcpy(himg.data() + off, e.bytes.data(), e.bytes.size());
+            for (const auto& e : b.images) {
+                e.write(himg.data() + off);
                 *e.target = ctx->img_arena + off;
-                off += pad(e.bytes.size());
+                off += pad(e.bytes);
             }
             L3AC_HIP_CHECK(hipMemcpy(ctx->img_arena, himg.data(), total_img, hipMemcpyHostToDevice));
         }
@@ -461,52 +473,19 @@ int network_build(l3ac_ctx* ctx, const l3ac_tensor* tensors, int n_tensors) {
     L3AC_HIP_CHECK(hipMemset(ctx->bad_index_count, 0, sizeof(int)));
     L3AC_HIP_CHECK(hipMalloc((void**)&ctx->wide_counters, 64));
     L3AC_HIP_CHECK(hipMemset(ctx->wide_counters, 0, 64));
-    {  // cooperative form of the transformer stacks (few clips: the streaming chunk): its scratch, counters zeroed ONCE here —
-       // every launch leaves them zeroed again
-        bool any = false;
-        for (const std::vector<LocalTransW>* v : {&ctx->en_enc, &ctx->en_dec})
-            for (const LocalTransW& t : *v) any = any || t.stack_img != nullptr;
-        if (any) {
-            L3AC_HIP_CHECK(hipMalloc(&ctx->coop.scratch, trans_stack_coop_bytes()));
-            L3AC_HIP_CHECK(hipMemset(ctx->coop.scratch, 0, trans_stack_coop_bytes()));
-            // the failure word lives in pinned host memory the device can add to: the host reads it without a device call
-            L3AC_HIP_CHECK(hipHostMalloc((void**)&ctx->coop.fail_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
-            *ctx->coop.fail_host = 0;
-            L3AC_HIP_CHECK(hipHostGetDevicePointer((void**)&ctx->coop.fail_dev, ctx->coop.fail_host, 0));
-        }
+    if (b.trans_stacks) {  // cooperative form of the transformer stacks (few clips: the streaming chunk): its scratch, counters zeroed ONCE
+                           // here — every launch leaves them zeroed again
+        L3AC_HIP_CHECK(hipMalloc(&ctx->coop.scratch, trans_stack_coop_bytes()));
+        L3AC_HIP_CHECK(hipMemset(ctx->coop.scratch, 0, trans_stack_coop_bytes()));
+        // the failure word lives in pinned host memory the device can add to: the host reads it without a device call
+        L3AC_HIP_CHECK(hipHostMalloc((void**)&ctx->coop.fail_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        *ctx->coop.fail_host = 0;
+        L3AC_HIP_CHECK(hipHostGetDevicePointer((void**)&ctx->coop.fail_dev, ctx->coop.fail_host, 0));
     }
     {  // GRN guard: starts at +inf
         const float inf = INFINITY;
         L3AC_HIP_CHECK(hipMalloc((void**)&ctx->grn_min_sumsq, sizeof(float)));
         L3AC_HIP_CHECK(hipMemcpy(ctx->grn_min_sumsq, &inf, sizeof(float), hipMemcpyHostToDevice));
-    }
-    // ---- name index for the per-block entry points ------------------------------------------------------
-    blk = 1;
-    for (int i = 0; i < c.n_enc; ++i) {
-        for (size_t j = 0; j < ctx->enc_units[i].size(); ++j)
-            ctx->by_unit["encoder.blocks." + std::to_string(blk) + "." + std::to_string(j) + ".module"] = &ctx->enc_units[i][j];
-        if (i + 1 < c.n_enc) ctx->by_down["encoder.blocks." + std::to_string(blk + 1)] = &ctx->enc_down[i];
-        blk += 2;
-    }
-    ctx->by_k3[enc_out_name] = &ctx->enc_out;
-    ctx->by_k3["decoder.blocks.0"] = &ctx->dec_in;
-    blk = 1;
-    for (int i = 0; i + 1 < c.n_dec; ++i) {
-        for (size_t j = 0; j < ctx->dec_units[i].size(); ++j)
-            ctx->by_unit["decoder.blocks." + std::to_string(blk) + "." + std::to_string(j) + ".module"] = &ctx->dec_units[i][j];
-        ctx->by_enh["decoder.blocks." + std::to_string(blk + 1)] = &ctx->dec_enh[i];
-        ctx->by_up["decoder.blocks." + std::to_string(blk + 2)] = &ctx->dec_up[i];
-        blk += 3;
-    }
-    if (compressed) {
-        ctx->by_trans["en_encoder.down_trans.trans"] = &ctx->en_enc[0];
-        ctx->by_trans["en_encoder.local_trans"] = &ctx->en_enc[1];
-        ctx->by_down["en_encoder.down_trans.down_layer"] = &ctx->en_down;
-        ctx->by_trans["en_decoder.local_trans"] = &ctx->en_dec[0];
-        ctx->by_trans["en_decoder.up_trans.trans"] = &ctx->en_dec[1];
-    } else {
-        ctx->by_trans["en_encoder.local_trans"] = &ctx->en_enc[0];
-        ctx->by_trans["en_decoder.local_trans"] = &ctx->en_dec[0];
     }
     return L3AC_OK;
 }

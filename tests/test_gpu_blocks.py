@@ -1160,3 +1160,51 @@ def test_context_options_start_from_the_environment(monkeypatch):
             assert created(**{env: value}).get_option(name) == stored, (env, value)
     with pytest.raises(RuntimeError, match="L3AC_DOWN_FUSED.*down_fused = 1.*retired.*DESIGN.md section 4"):
         created(L3AC_DOWN_FUSED="1")
+
+
+def test_construction_and_block_lookup_errors(full):
+    """What l3ac_create answers to a weight set it cannot build from, and an l3ac_op_* entry point to a name that is no block
+    (include/l3ac_hip.h: L3AC_EWEIGHT = -2, L3AC_EINVAL = -1).  One tensor is left out, or given a wrong element count, per block kind:
+    the message names that tensor (the first one the construction misses is the only one that is wrong) and gives both counts."""
+    L3AC_EINVAL, L3AC_EWEIGHT = -1, -2
+    codec, mc, _ = full
+    folded = W.folded_weights(codec.network.state_dicts())
+    device = torch.cuda.current_device()
+    victims = ("encoder.blocks.0.blocks.3.1.bias", "encoder.blocks.0.conv_2.weight",         # first block: a trend branch, conv_2
+               "encoder.blocks.5.0.module.pw_conv2.weight", "decoder.blocks.7.0.module.grn.gamma",  # ConvUnits of both coders
+               "encoder.blocks.6.1.weight", "en_encoder.down_trans.down_layer.bias",          # down layers
+               "encoder.blocks.8.bias", "decoder.blocks.0.weight",                             # k3 convs
+               "en_encoder.down_trans.trans.layers.0.1.4.weight", "en_decoder.local_trans.dynamic_pos_bias.mlp.2.weight",
+               "quantizer.project_out.weight",
+               "decoder.blocks.8.blocks.0.1.weight", "decoder.blocks.8.merge_layer.1.bias",  # EnhanceBlock
+               "decoder.blocks.9.2.bias",                                                      # up layer
+               "decoder.blocks.13.block.0.2.module.block.3.weight", "decoder.blocks.13.block.2.weight")  # LegacyUnit, head
+    for name in victims:
+        assert name in folded, name
+        with pytest.raises(_capi.L3acError) as e:
+            _capi.Context(mc, {k: v for k, v in folded.items() if k != name}, device)
+        print(f"[missing {name}] {e.value}")
+        assert f"error {L3AC_EWEIGHT}:" in str(e.value) and f"missing weight tensor '{name}'" in str(e.value), str(e.value)
+    for name in victims:
+        good = folded[name].numel()
+        for bad in (good + 1, max(1, good - 1)) if good > 1 else (2,):
+            wrong = dict(folded)
+            wrong[name] = torch.zeros(bad)
+            with pytest.raises(_capi.L3acError) as e:
+                _capi.Context(mc, wrong, device)
+            print(f"[{bad} elements for {name}] {e.value}")
+            assert f"error {L3AC_EWEIGHT}:" in str(e.value), str(e.value)
+            assert f"weight tensor '{name}' has {bad} elements, expected {good}" in str(e.value), str(e.value)
+    ctx = codec.network.context()
+    ctx.reserve(2, 16000)
+    x = torch.zeros(2, 50, 96, device="cuda")
+    y = torch.empty_like(x)
+    s = torch.cuda.current_stream().cuda_stream
+    for block in (b"encoder.blocks.5.1.module", b"encoder.blocks.6", b"encoder.blocks.5.0", b""):  # a unit too many, a down layer, a prefix
+        rc = ctx.lib.l3ac_op_conv_unit(ctx.handle, block, x.data_ptr(), 2, 50, y.data_ptr(), s)
+        assert rc == L3AC_EINVAL, (block, rc)
+        assert ctx.lib.l3ac_last_error().decode() == f"no ConvUnit block named '{block.decode()}'"
+    torch.cuda.synchronize()
+    # (and the name beside them is one)
+    _capi.check(ctx.lib.l3ac_op_conv_unit(ctx.handle, b"encoder.blocks.5.0.module", x.data_ptr(), 2, 50, y.data_ptr(), s))
+    torch.cuda.synchronize()
