@@ -279,6 +279,46 @@ int l3ac_chunk_cut(const void* src, int32_t recs, int64_t src_stride, int32_t c,
 int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
                      void* dst, int32_t recs, int64_t dst_stride, int64_t out_frames, void* stream);
 
+/* ---- streaming sessions: the state carried between pushes ---------------------------------------------
+ * S live streams are cut with a step of CL frames and a look-back of P frames: chunk k of a stream covers
+ * [max(0, k * CL - P), (k + 1) * CL) and emits what lies at or after k * CL; P may be at or above CL, which l3ac_chunk_plan refuses.
+ * A session keeps one state buffer [streams][state_frames][c] (state_frames >= P + CL): stream i's row holds, from frame 0, the
+ * frames that can still be needed, its look-back followed directly by its pending frames.  How many they are is a host value.
+ * A push of new frames fresh [streams][fresh_stride][c] (fresh_frames <= fresh_stride of them valid per row; may be null when no
+ * descriptor takes any) runs in rounds, each stream completing at most one chunk per round:
+ *   l3ac_stream_gather: row desc.row of rows [n_rows][row_frames][c] = state[slot][0 : held] ++ fresh[slot][off : off + take] ++
+ *                       pad zero frames.  Frames of a row after these are not written.
+ *   l3ac_stream_carry:  state[slot][0 : keep] = frames [held + take - keep, held + take) of row desc.row: the stream's next look-back,
+ *                       read from the row just built because it overlaps what the state held (no kernel moves a span onto an
+ *                       overlapping span of its own buffer).
+ *   l3ac_stream_append: state[slot][held : held + take] = fresh[slot][off : off + take]: what a push leaves pending.
+ *   l3ac_stream_emit:   rows [n_rows][row_frames][c] (a ragged call's output) -> dst [streams][dst_stride][c]: frames
+ *                       [prefix, held + take + pad) of row desc.row go to dst[slot][out ...], followed by `zero` zero frames, all
+ *                       below out_frames <= dst_stride.  A descriptor with held + take + pad == prefix writes zeros only.
+ * Each call reads only the fields named for it.  Context-free, 4-byte elements moved bit for bit, like the chunk entries; `desc` is a
+ * HOST array, checked against the shapes before anything is launched (bounds, and that no two descriptors write the same frame) and
+ * handed to the device as kernel arguments, 72 per launch: graph-safe.  Enqueue only. */
+typedef struct l3ac_stream_desc {
+    int32_t slot;    /* stream: row of the state, of the new frames and of the output */
+    int32_t row;     /* row of the rows layout */
+    int32_t held;    /* frames taken from the front of the stream's state row */
+    int32_t take;    /* new frames taken */
+    int64_t off;     /* ... from this frame of the stream's row of new frames */
+    int32_t pad;     /* zero frames at the row's end (a flushed last chunk rounded up to a whole hop) */
+    int32_t keep;    /* carry: frames the stream keeps as its next look-back */
+    int32_t prefix;  /* emit: leading frames of the row that are look-back, dropped */
+    int32_t zero;    /* emit: zero frames written after the emitted ones */
+    int64_t out;     /* emit: first frame written in the stream's output row */
+} l3ac_stream_desc;
+int l3ac_stream_gather(const void* state, int32_t streams, int64_t state_frames, const void* fresh, int64_t fresh_frames, int64_t fresh_stride,
+                       int32_t c, const l3ac_stream_desc* desc, int32_t count, void* rows, int32_t n_rows, int64_t row_frames, void* stream);
+int l3ac_stream_carry(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* state,
+                      int32_t streams, int64_t state_frames, void* stream);
+int l3ac_stream_append(const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int32_t c, const l3ac_stream_desc* desc, int32_t count,
+                       void* state, int32_t streams, int64_t state_frames, void* stream);
+int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* dst,
+                     int32_t streams, int64_t dst_stride, int64_t out_frames, void* stream);
+
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */

@@ -36,10 +36,11 @@ import torch
 from . import _capi
 from . import weights as _weights
 from .chunking import ChunkData, plan as _chunk_plan
+from .streaming import StreamDecoder, StreamEncoder
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
-           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan"]
+           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -570,6 +571,26 @@ class L3AC:
             return audio
         audio = resample(audio, self.config.sample_rate, rate)
         return _zero_after(audio, [resample_length(self.config.sample_rate, rate, n * hop) for n in tok])
+
+
+    # ---- streaming sessions (l3ac_amd/streaming.py) -------------------------------------------
+    def stream_encoder(self, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
+                       chunks_per_call: Optional[int] = None) -> StreamEncoder:
+        """A session of ``streams`` concurrent live streams: ``enc.push(audio, lengths=None, end=None)`` takes each stream's new
+        samples and returns the tokens of the windows they complete — the bits ``encode_long`` gives the whole recording
+        (``StreamEncoder.push``).  ``process_window``: the step in samples at the codec's rate, rounded down to whole hops as in
+        ``extract_unit``, at least one hop.  ``prefix_tokens``: the look-back (default: the attention window, as everywhere else); it
+        may be below, at or above the step, and 0 means independent windows.  ``chunks_per_call``: as in ``encode_long``.  The network
+        must be on its GPU; a session belongs to the context it was created on.  There is no ``sample_rate=``: converting a live
+        stream needs the filter's own carried state."""
+        return StreamEncoder(self, streams, process_window, prefix_tokens, chunks_per_call)
+
+    def stream_decoder(self, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
+                       chunks_per_call: Optional[int] = None) -> StreamDecoder:
+        """The decoding side: ``dec.push(audio_feature=None, indices=None, lengths=None, end=None)`` takes each stream's new tokens
+        and returns the audio of the windows they complete — ``decode_long``'s bits (``StreamDecoder.push``).  The step is
+        ``process_window // hop`` tokens; the other arguments as in ``stream_encoder``."""
+        return StreamDecoder(self, streams, process_window, prefix_tokens, chunks_per_call)
 
 
 def set_gemm_split(enable: bool) -> None:

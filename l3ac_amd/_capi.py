@@ -45,6 +45,12 @@ class ChunkDesc(C.Structure):
                 ("pad", C.c_int32), ("last", C.c_int32)]
 
 
+class StreamDesc(C.Structure):
+    """l3ac_stream_desc: one chunk of one live stream (include/l3ac_hip.h)."""
+    _fields_ = [("slot", C.c_int32), ("row", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("off", C.c_int64), ("pad", C.c_int32),
+                ("keep", C.c_int32), ("prefix", C.c_int32), ("zero", C.c_int32), ("out", C.c_int64)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -111,6 +117,10 @@ SIGNATURES = {
     "l3ac_chunk_plan": (_I64, [C.POINTER(_I64), _I32, _I64, _I64, _I32, C.POINTER(ChunkDesc), _I64]),
     "l3ac_chunk_cut": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(ChunkDesc), _I32, _P, _I32, _I64, _P]),
     "l3ac_chunk_merge": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(ChunkDesc), _I32, _P, _I32, _I64, _I64, _P]),
+    "l3ac_stream_gather": (C.c_int, [_P, _I32, _I64, _P, _I64, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _P]),
+    "l3ac_stream_carry": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _P]),
+    "l3ac_stream_append": (C.c_int, [_P, _I64, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _P]),
+    "l3ac_stream_emit": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

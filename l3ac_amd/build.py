@@ -44,6 +44,7 @@ SOURCES = [
     "kernels/ragged.hip",
     "kernels/resample.hip",
     "kernels/chunk.hip",
+    "kernels/stream.hip",
 ]
 
 

@@ -752,6 +752,28 @@ int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int3
     return launch_chunk_merge((hipStream_t)stream, src, rows, src_row_frames, c, desc, count, dst, recs, dst_stride, out_frames);
 }
 
+// ---- streaming sessions: the state carried between pushes -------------------------
+int l3ac_stream_gather(const void* state, int32_t streams, int64_t state_frames, const void* fresh, int64_t fresh_frames, int64_t fresh_stride,
+                       int32_t c, const l3ac_stream_desc* desc, int32_t count, void* rows, int32_t n_rows, int64_t row_frames, void* stream) {
+    return launch_stream_gather((hipStream_t)stream, state, streams, state_frames, fresh, fresh_frames, fresh_stride, c, desc, count, rows, n_rows,
+                                row_frames);
+}
+
+int l3ac_stream_carry(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* state,
+                      int32_t streams, int64_t state_frames, void* stream) {
+    return launch_stream_carry((hipStream_t)stream, rows, n_rows, row_frames, c, desc, count, state, streams, state_frames);
+}
+
+int l3ac_stream_append(const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int32_t c, const l3ac_stream_desc* desc, int32_t count,
+                       void* state, int32_t streams, int64_t state_frames, void* stream) {
+    return launch_stream_append((hipStream_t)stream, fresh, fresh_frames, fresh_stride, c, desc, count, state, streams, state_frames);
+}
+
+int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* dst,
+                     int32_t streams, int64_t dst_stride, int64_t out_frames, void* stream) {
+    return launch_stream_emit((hipStream_t)stream, rows, n_rows, row_frames, c, desc, count, dst, streams, dst_stride, out_frames);
+}
+
 int l3ac_profile_begin(void) {
     L3AC_REQUIRE(g_profiler == nullptr, "profile already active on this thread");
     g_profiler = new (std::nothrow) Profiler();

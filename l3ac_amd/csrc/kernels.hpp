@@ -212,6 +212,23 @@ int launch_chunk_cut(hipStream_t s, const void* src, int recs, int64_t src_strid
 // chunk rows [rows][src_row_frames][c] -> recordings [recs][dst_stride][c], prefixes dropped, zeros from a recording's end to out_frames
 int launch_chunk_merge(hipStream_t s, const void* src, int rows, int64_t src_row_frames, int c, const l3ac_chunk_desc* desc, int count,
                        void* dst, int recs, int64_t dst_stride, int64_t out_frames);
+// streaming sessions (kernels/stream.hip): the state carried between pushes; descriptors as kernel arguments, CAP per launch
+struct StreamBlock {
+    static constexpr int CAP = 72;  // 3.4 KiB of the 4 KiB a launch's arguments may take
+    l3ac_stream_desc desc[CAP];
+};
+// chunk row desc.row = state[slot][0 : held] ++ fresh[slot][off : off + take] ++ zeros(pad); `desc` is a host array
+int launch_stream_gather(hipStream_t s, const void* state, int streams, int64_t state_frames, const void* fresh, int64_t fresh_frames,
+                         int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count, void* rows, int n_rows, int64_t row_frames);
+// state[slot][0 : keep] = the last keep of row desc.row's held + take own frames
+int launch_stream_carry(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* state,
+                        int streams, int64_t state_frames);
+// state[slot][held : held + take] = fresh[slot][off : off + take]
+int launch_stream_append(hipStream_t s, const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count,
+                         void* state, int streams, int64_t state_frames);
+// frames [prefix, held + take + pad) of row desc.row -> dst[slot][out ...], then `zero` zero frames
+int launch_stream_emit(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* dst,
+                       int streams, int64_t dst_stride, int64_t out_frames);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -22,40 +22,11 @@
 #include <algorithm>
 
 #include "../kernels.hpp"
+#include "span_copy.hpp"
 
 namespace {
 
-constexpr int THREADS = 256;
-
-__device__ __forceinline__ void copy_span(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int64_t n, int64_t tid,
-                                          int64_t stride) {
-    const uintptr_t da = reinterpret_cast<uintptr_t>(dst), sa = reinterpret_cast<uintptr_t>(src);
-    if (((da ^ sa) & 15) == 0) {
-        int64_t head = (int64_t)(((16 - (da & 15)) & 15) >> 2);
-        if (head > n) head = n;
-        const int64_t body = (n - head) >> 2;
-        if (tid < head) dst[tid] = src[tid];
-        const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
-        uint4* d4 = reinterpret_cast<uint4*>(dst + head);
-        for (int64_t e = tid; e < body; e += stride) d4[e] = s4[e];
-        const int64_t done = head + body * 4;
-        if (tid < n - done) dst[done + tid] = src[done + tid];
-    } else {
-        for (int64_t e = tid; e < n; e += stride) dst[e] = src[e];
-    }
-}
-
-__device__ __forceinline__ void zero_span(uint32_t* __restrict__ dst, int64_t n, int64_t tid, int64_t stride) {
-    const uintptr_t da = reinterpret_cast<uintptr_t>(dst);
-    int64_t head = (int64_t)(((16 - (da & 15)) & 15) >> 2);
-    if (head > n) head = n;
-    const int64_t body = (n - head) >> 2;
-    if (tid < head) dst[tid] = 0u;
-    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
-    for (int64_t e = tid; e < body; e += stride) d4[e] = make_uint4(0u, 0u, 0u, 0u);
-    const int64_t done = head + body * 4;
-    if (tid < n - done) dst[done + tid] = 0u;
-}
+constexpr int THREADS = SPAN_THREADS;
 
 // grid (span blocks, chunks of this block of descriptors)
 __global__ __launch_bounds__(THREADS) void chunk_cut_kernel(const uint32_t* __restrict__ src, int64_t src_stride, int c,
@@ -78,10 +49,6 @@ __global__ __launch_bounds__(THREADS) void chunk_merge_kernel(const uint32_t* __
               tid, stride);
     const int64_t end = d.start + d.frames;
     if (d.last && end < out_frames) zero_span(rec + end * c, (out_frames - end) * c, tid, stride);
-}
-
-unsigned span_blocks(int64_t elements) {  // 16 elements (four 16-byte accesses) per lane, at most 64 workgroups per chunk
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div64(elements, (int64_t)THREADS * 16), 1), 64);
 }
 
 }  // namespace

@@ -1,0 +1,466 @@
+"""Streaming sessions: live audio in, the chunker's bits out.
+
+Geometry first, as pure functions of host integers (no tensors, no GPU): a stream of frames arrives in pushes of any size and is cut
+with a step of ``step`` frames and a look-back of ``lookback`` frames.  Chunk k covers ``[max(0, k * step - lookback),
+min(n', (k + 1) * step))`` and emits what lies at or after ``k * step``; ``n'`` is the stream's length rounded up to ``round_to``
+(audio: the hop, the zero padding of ``Network.preprocess``).  For ``lookback < step`` that is ``ChunkData``'s / ``l3ac_chunk_plan``'s
+geometry; for ``lookback >= step`` — a short step with the attention's whole window behind it, which the offline chunker refuses — the
+look-back grows over the first ``ceil(lookback / step)`` chunks until it is full.
+
+Then the sessions, ``StreamEncoder`` / ``StreamDecoder`` (``L3AC.stream_encoder`` / ``L3AC.stream_decoder``): the state carried
+between pushes lives in one device buffer per session, moved by the kernels of csrc/kernels/stream.hip; every chunk runs as a row of
+the ragged calls, so its bits are those of ``encode_audio`` / ``decode_audio`` on that chunk alone.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from . import _capi
+
+
+# ---- 1. geometry -------------------------------------------------------------------------------------------------------------
+class StreamState(NamedTuple):
+    """What one stream holds between pushes: ``context`` frames of look-back followed directly by ``pending`` frames that have not
+    completed a chunk yet (``held = context + pending`` frames, one contiguous piece of the stream), and the frames seen so far."""
+    context: int = 0
+    pending: int = 0
+    seen: int = 0
+
+    @property
+    def held(self) -> int:
+        return self.context + self.pending
+
+
+class StreamRow(NamedTuple):
+    """One completed chunk.  (start, frames, prefix, pad) are ``l3ac_chunk_desc``'s fields: the chunk's first frame in its stream,
+    its frames (look-back and zero padding included), the look-back frames its emission drops, the zero frames at its end.  The row is
+    ``state[0:held] ++ new[off:off + take] ++ zeros(pad)``; afterwards the stream keeps the row's last ``keep`` real frames."""
+    start: int
+    frames: int
+    prefix: int
+    pad: int
+    held: int
+    off: int
+    take: int
+    keep: int
+
+
+def check_geometry(step: int, lookback: int, round_to: int = 1) -> None:
+    if round_to < 1 or step < round_to or step % round_to or lookback < 0 or lookback % round_to:
+        raise ValueError(f"a step of {step} and a look-back of {lookback} frames must be whole multiples of {round_to}, the step at least one")
+
+
+def advance(state: StreamState, new_frames: int, end: bool, step: int, lookback: int, round_to: int = 1) -> Tuple[List[StreamRow], StreamState]:
+    """One push of ``new_frames`` frames onto a stream in ``state``: the chunks it completes, in order, and the state afterwards.
+    ``end``: the stream ends with this push; what is pending is flushed as its last chunk, padded with zeros to a multiple of
+    ``round_to``, and the state afterwards is a fresh stream's."""
+    check_geometry(step, lookback, round_to)
+    if new_frames < 0:
+        raise ValueError(f"{new_frames} new frames")
+    context, pending, seen = state
+    rows: List[StreamRow] = []
+    off = 0
+    while pending + (new_frames - off) >= step:
+        take = step - pending
+        frames = context + step
+        keep = min(lookback, frames)
+        rows.append(StreamRow(seen - pending - context, frames, context, 0, context + pending, off, take, keep))
+        seen += take
+        off += take
+        context, pending = keep, 0
+    rest = new_frames - off
+    if not end:
+        return rows, StreamState(context, pending + rest, seen + rest)
+    if pending + rest > 0:
+        pad = -(pending + rest) % round_to
+        rows.append(StreamRow(seen - pending - context, context + pending + rest + pad, context, pad, context + pending, off, rest, 0))
+    return rows, StreamState()
+
+
+def leftover(rows: Sequence[StreamRow], after: StreamState, new_frames: int) -> Optional[Tuple[int, int, int]]:
+    """(held, off, take) of the append that follows a push's last chunk: ``new[off:off + take]`` goes behind the ``held`` frames the
+    stream holds by then; None when the push leaves nothing over (always when it ended the stream)."""
+    off = sum(r.take for r in rows)
+    take = new_frames - off
+    if take <= 0 or after.held == 0:
+        return None
+    return after.held - take, off, take
+
+
+def emitted(seen: int, ended: bool, step: int, round_to: int = 1) -> int:
+    """Frames' worth of output (in units of ``round_to`` frames: tokens) a stream has emitted after ``seen`` frames."""
+    return -(-seen // round_to) if ended else seen // step * (step // round_to)
+
+
+def round4(n: int) -> int:
+    return -(-n // 4) * 4
+
+
+# ---- 2. sessions -------------------------------------------------------------------------------------------------------------
+class _PushPlan(NamedTuple):
+    rows: list       # (slot, round, StreamRow), in row order of the whole push: shortest first
+    groups: list     # lists of indices into rows: one ragged call each
+    appends: list    # (slot, held, off, take)
+    after: list      # StreamState per slot
+    rounds: int
+
+
+class _Session:
+    """What StreamEncoder and StreamDecoder share: the per-stream host state, the device state buffer and the kernels that move it."""
+    _what = "stream"
+
+    def __init__(self, codec, streams: int, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int], in_tokens: bool):
+        mc = codec.network.mc
+        hop = mc.hop_length
+        if isinstance(streams, bool) or int(streams) != streams or int(streams) < 1:
+            raise ValueError(f"streams must be a positive integer, got {streams!r}")
+        if int(process_window) != process_window or int(process_window) < hop:
+            raise ValueError(f"process_window ({process_window} samples) must be at least one hop ({hop} samples)")
+        prefix_tokens = mc.en_coder_window_size if prefix_tokens is None else prefix_tokens
+        if int(prefix_tokens) != prefix_tokens or int(prefix_tokens) < 0:
+            raise ValueError(f"prefix_tokens must be a non-negative integer, got {prefix_tokens!r}")
+        self.codec = codec
+        self.streams = int(streams)
+        self.hop = hop
+        self.step_tokens = int(process_window) // hop
+        self.prefix_tokens = int(prefix_tokens)
+        unit = 1 if in_tokens else hop  # frames per token on the input side
+        self.round_to = unit
+        self.step = self.step_tokens * unit
+        self.lookback = self.prefix_tokens * unit
+        check_geometry(self.step, self.lookback, self.round_to)
+        if chunks_per_call is None:
+            chunks_per_call = max(1, (512 * codec.config.sample_rate) // ((self.step_tokens + self.prefix_tokens) * hop))
+        if int(chunks_per_call) < 1:
+            raise ValueError(f"chunks_per_call must be at least 1, got {chunks_per_call}")
+        self.chunks_per_call = min(int(chunks_per_call), 65535)
+        self.state_frames = round4(self.lookback + self.step)
+        self._states = [StreamState() for _ in range(self.streams)]
+        self._ctx = codec.network.context()  # raises when the network is not on a GPU
+        self._device = codec.network.device
+        self._lib = _capi.load_library()
+        self._buf, self._c = None, 0  # [streams][state_frames][c], allocated at the first push (a decoder learns c there)
+
+    # ---- host side ------------------------------------------------------------------------------------------------------
+    @property
+    def states(self) -> List[StreamState]:
+        """The streams' host state (a copy): look-back held, frames pending, frames seen since the stream began."""
+        return list(self._states)
+
+    def reset(self, streams=None) -> None:
+        """Make the given streams (an index, a sequence of them; absent: all) fresh: what they hold is dropped, nothing is emitted."""
+        which = range(self.streams) if streams is None else [streams] if isinstance(streams, int) else list(streams)
+        which = [int(i) for i in which]
+        bad = [i for i in which if not 0 <= i < self.streams]
+        if bad:
+            raise ValueError(f"stream {bad[0]} of {self.streams}")
+        for i in which:
+            self._states[i] = StreamState()
+
+    def _lengths(self, lengths, n: int, what: str) -> List[int]:
+        if lengths is None:
+            return [n] * self.streams
+        if isinstance(lengths, torch.Tensor):
+            lengths = lengths.detach().cpu().reshape(-1).tolist()
+        try:
+            seq = list(lengths)
+            vals = [int(v) for v in seq]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a sequence of {self.streams} ints") from None
+        if any(float(v) != int(v) for v in seq):
+            raise ValueError(f"{what} must be integers")
+        if len(vals) != self.streams:
+            raise ValueError(f"{what}: {len(vals)} entries for {self.streams} streams")
+        bad = [v for v in vals if not 0 <= v <= n]
+        if bad:
+            raise ValueError(f"{what}: {bad[0]} outside [0, {n}]")
+        return vals
+
+    def _ends(self, end) -> List[bool]:
+        if end is None or isinstance(end, bool):
+            return [bool(end)] * self.streams
+        if isinstance(end, torch.Tensor):
+            end = end.detach().cpu().reshape(-1).tolist()
+        vals = [bool(v) for v in end]
+        if len(vals) != self.streams:
+            raise ValueError(f"end: {len(vals)} entries for {self.streams} streams")
+        return vals
+
+    def _check_network(self, t, what: str) -> None:
+        net = self.codec.network
+        if net.training:
+            raise RuntimeError("call codec.network.eval() first: the training-mode quantiser injects noise "
+                               "(reference vq/fsq.py:31,40-43), which this inference path does not implement")
+        if net._ctx is not self._ctx or self._ctx.handle is None:
+            raise RuntimeError(f"{self._what}: the network was moved to another device or reloaded after this session was created; its "
+                               "state belongs to the context it was created on: create a new session")
+        if not t.is_cuda or t.device != self._device:
+            raise RuntimeError(f"{what} is on {t.device} but the network is on {self._device}")
+        if net.grn_exact:
+            raise _capi.L3acError(f"{self._what}: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
+                                  f"would include their padding: use {self._offline} per recording")
+
+    def _plan(self, lens: List[int], ends: List[bool]) -> _PushPlan:
+        per, after, appends = [], [], []
+        for i in range(self.streams):
+            rows, st = advance(self._states[i], lens[i], ends[i], self.step, self.lookback, self.round_to)
+            tail = leftover(rows, st, lens[i])
+            if tail is not None:
+                appends.append((i,) + tail)
+            per.append(rows)
+            after.append(st)
+        flat = [(i, j, r) for i, rows in enumerate(per) for j, r in enumerate(rows)]
+        flat.sort(key=lambda e: e[2].frames)  # shortest first (stable), as encode_long groups its chunks
+        groups = [list(range(k0, min(k0 + self.chunks_per_call, len(flat)))) for k0 in range(0, len(flat), self.chunks_per_call)]
+        return _PushPlan(flat, groups, appends, after, max([len(rows) for rows in per] + [0]))
+
+    def _steady(self, lens: List[int], ends: List[bool]) -> Optional[str]:
+        """None when this push is steady (capturable), else the condition it breaks."""
+        for i, st in enumerate(self._states):
+            if st.context != self.lookback:
+                return f"stream {i}'s look-back is not full ({st.context} of {self.lookback} frames)"
+            if st.pending:
+                return f"stream {i} has {st.pending} frames pending"
+            if lens[i] != self.step:
+                return f"lengths[{i}] = {lens[i]} is not the step ({self.step})"
+            if ends[i]:
+                return f"stream {i} ends with this push"
+        return None
+
+    def _check_capture(self, lens, ends) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            why = self._steady(lens, ends)
+            if why is None and self._buf is None:
+                why = "the session has not run yet"
+            if why is not None:
+                raise RuntimeError(f"{self._what}: only a steady push can be captured into a graph (every look-back full, nothing pending, "
+                                   f"every length the step, no end), but {why}; run the pushes up to the steady state outside stream capture")
+
+    # ---- device side ----------------------------------------------------------------------------------------------------
+    def _state_buffer(self, like, c: int):
+        if self._buf is None or self._buf.dtype != like.dtype or self._c != c:
+            self._buf = torch.zeros((self.streams, self.state_frames * c), dtype=like.dtype, device=self._device)
+            self._c = c
+        return self._buf
+
+    def _desc(self, entries):
+        return (_capi.StreamDesc * len(entries))(*entries)
+
+    def _move(self, plan: _PushPlan, new, new_stride: int, c: int, stream):
+        """gather / carry round by round, then append: the rows tensors of the plan's groups (group order), state updated."""
+        lib, buf = self._lib, self._buf
+        rows_t = []
+        where = {}  # index into plan.rows -> (group, row in group)
+        for g, group in enumerate(plan.groups):
+            longest = max(plan.rows[k][2].frames for k in group)
+            width = round4(longest) if c == 1 and self.round_to > 1 else longest  # audio rows: stride rounded to 4, as encode_long's
+            shape = (len(group), width) if c == 1 else (len(group), width, c)
+            rows_t.append(torch.empty(shape, dtype=new.dtype, device=self._device))
+            for k_in, k in enumerate(group):
+                where[k] = (g, k_in)
+        new_ptr = new.data_ptr() if new.numel() else None
+        new_frames = new.shape[1]
+        for rnd in range(plan.rounds):
+            for g, group in enumerate(plan.groups):
+                entries = [_capi.StreamDesc(slot, where[k][1], r.held, r.take, r.off, r.pad, r.keep, r.prefix, 0, 0)
+                           for k in group for slot, j, r in [plan.rows[k]] if j == rnd]
+                if not entries:
+                    continue
+                desc = self._desc(entries)
+                rt = rows_t[g]
+                _capi.check(lib.l3ac_stream_gather(buf.data_ptr(), self.streams, self.state_frames, new_ptr, new_frames, new_stride, c, desc,
+                                                   len(desc), rt.data_ptr(), rt.shape[0], rt.stride(0) // c, stream))
+                if any(e.keep for e in entries):
+                    _capi.check(lib.l3ac_stream_carry(rt.data_ptr(), rt.shape[0], rt.stride(0) // c, c, desc, len(desc), buf.data_ptr(),
+                                                      self.streams, self.state_frames, stream))
+        if plan.appends:
+            desc = self._desc([_capi.StreamDesc(slot, 0, held, take, off, 0, 0, 0, 0, 0) for slot, held, off, take in plan.appends])
+            _capi.check(lib.l3ac_stream_append(new_ptr, new_frames, new_stride, c, desc, len(desc), buf.data_ptr(), self.streams,
+                                               self.state_frames, stream))
+        return rows_t
+
+    def _emit_plan(self, plan: _PushPlan, scale_num: int, scale_den: int):
+        """Per group the emit descriptors in output frames (input frames * scale_num / scale_den), the per-stream output counts and the
+        widest of them.  A stream's last chunk of the push zeroes its output row up to the width; a stream that emits nothing gets a
+        descriptor of zeros only (in the first group's launch)."""
+        sc = lambda v: v * scale_num // scale_den
+        total = [0] * self.streams
+        for slot, j, r in plan.rows:
+            total[slot] += sc(r.frames - r.prefix)
+        width = max(total)
+        pos = [0] * self.streams
+        out = [[None] * len(group) for group in plan.groups]
+        order = sorted(range(len(plan.rows)), key=lambda k: (plan.rows[k][0], plan.rows[k][1]))  # each stream's chunks in time order
+        where = {k: (g, k_in) for g, group in enumerate(plan.groups) for k_in, k in enumerate(group)}
+        for k in order:
+            slot, j, r = plan.rows[k]
+            n = sc(r.frames - r.prefix)
+            last = pos[slot] + n == total[slot]
+            g, k_in = where[k]
+            out[g][k_in] = _capi.StreamDesc(slot, k_in, sc(r.frames), 0, 0, 0, 0, sc(r.prefix), width - total[slot] if last else 0, pos[slot])
+            pos[slot] += n
+        if width and out:
+            out[0] += [_capi.StreamDesc(slot, 0, 0, 0, 0, 0, 0, 0, width, 0) for slot in range(self.streams) if total[slot] == 0]
+        return [self._desc(e) for e in out], total, width
+
+    def _emit(self, src, desc, dst, stream) -> None:
+        c = dst.shape[2] if dst.dim() == 3 else 1
+        _capi.check(self._lib.l3ac_stream_emit(src.data_ptr(), src.shape[0], src.stride(0) // c, c, desc, len(desc), dst.data_ptr(),
+                                               dst.shape[0], dst.stride(0) // c, dst.shape[1], stream))
+
+
+class StreamEncoder(_Session):
+    """``codec.stream_encoder(streams=S, process_window=16000, prefix_tokens=None)``: S concurrent live streams; see ``push``."""
+    _what = "stream_encoder"
+    _offline = "extract_unit"
+
+    def __init__(self, codec, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
+                 chunks_per_call: Optional[int] = None):
+        super().__init__(codec, streams, process_window, prefix_tokens, chunks_per_call, in_tokens=False)
+
+    def push(self, audio, lengths=None, end=None, validate: bool = False):
+        """New samples of every stream -> the tokens of the windows they complete.
+
+        ``audio`` (S, n) fp32 CUDA at the codec's rate, n >= 0: row i holds stream i's new samples, ``lengths[i]`` in 0..n of them
+        (absent: n; 0: the stream brings nothing this call; samples at or after ``lengths[i]`` are ignored, whatever they hold).
+        ``end``: a bool or S bools; a stream that ends flushes what is pending as its last chunk, zero-padded to a whole hop, and its
+        slot starts fresh for the next stream.  Returns ``encode_audio(..., lengths=)``'s shapes: ``q (S, T_out, C)``,
+        ``{"indices": (S, T_out) int32, "level_indices": (S, T_out, D), "lengths": int32 on the CPU}``; ``lengths`` holds the tokens
+        emitted per stream by this call, rows are zero after them, ``T_out`` is their maximum and may be 0.
+
+        However a stream's samples are split over pushes, and whatever the other streams do, the concatenation of what it emits is,
+        chunk by chunk, ``encode_audio`` of chunk ``[max(0, k * CL - P), (k + 1) * CL)`` alone with the look-back tokens dropped, bit
+        for bit (CL = ``process_window`` in whole hops, P = ``prefix_tokens`` hops): for P < CL, ``encode_long``'s row.  After t
+        samples ``floor(t / CL) * CL / hop`` tokens have been emitted, after ``end`` ``ceil(t / hop)``.
+        There is no ``sample_rate=``: converting a live stream needs the filter's own carried state; convert packets with
+        ``l3ac.resample`` at your own risk of edge effects, or push at the codec's rate.
+        A steady push (every look-back full, nothing pending, every length CL, no end) can be captured into a graph after
+        ``context().reserve(S, P + CL)`` and one eager steady push; under stream capture any other push raises RuntimeError.
+        ``validate``: as encode_audio."""
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 2 or audio.shape[0] != self.streams:
+            raise ValueError(f"audio must be a ({self.streams}, samples) tensor, got {tuple(getattr(audio, 'shape', ()))}")
+        lens = self._lengths(lengths, audio.shape[1], "lengths")
+        ends = self._ends(end)
+        self._check_network(audio, "audio")
+        self._check_capture(lens, ends)
+        codec, mc, hop, dev = self.codec, self.codec.network.mc, self.hop, self._device
+        plan = self._plan(lens, ends)
+        new = audio.to(torch.float32)
+        if new.stride(-1) != 1 and new.numel():
+            new = new.contiguous()
+        descs, total, width = self._emit_plan(plan, 1, hop)
+        q_feature = torch.empty((self.streams, width, mc.feature_dim), dtype=torch.float32, device=dev)
+        indices = torch.empty((self.streams, width), dtype=torch.int32, device=dev)
+        level_indices = torch.empty((self.streams, width, len(mc.levels)), dtype=torch.float32, device=dev)
+        ctx = self._ctx
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if validate:
+                codec._coop_check_before(ctx, "stream_encoder.push")
+            self._state_buffer(new, 1)
+            rows_t = self._move(plan, new, new.stride(0) if self.streams > 1 and new.shape[1] else max(new.shape[1], 1), 1, stream)
+            self._states = plan.after
+            for group, rows, desc in zip(plan.groups, rows_t, descs):
+                g = len(group)
+                samples = [plan.rows[k][2].frames for k in group]
+                longest = max(samples)
+                g_tok = longest // hop
+                q = torch.empty((g, g_tok, mc.feature_dim), dtype=torch.float32, device=dev)
+                idx = torch.empty((g, g_tok), dtype=torch.int32, device=dev)
+                li = torch.empty((g, g_tok, len(mc.levels)), dtype=torch.float32, device=dev)
+                if min(samples) == longest:  # rows of one length (every steady push): the plain call, the same bits
+                    _capi.check(ctx.lib.l3ac_encode(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), q.data_ptr(), idx.data_ptr(),
+                                                    li.data_ptr(), stream))
+                else:
+                    _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), (ctypes.c_int32 * g)(*samples),
+                                                           q.data_ptr(), idx.data_ptr(), li.data_ptr(), stream))
+                self._emit(q, desc, q_feature, stream)
+                self._emit(idx, desc, indices, stream)
+                self._emit(li, desc, level_indices, stream)
+            if validate:
+                codec._raise_on_coop_timeout(ctx, "stream_encoder.push")
+        return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": torch.tensor(total, dtype=torch.int32)}
+
+
+class StreamDecoder(_Session):
+    """``codec.stream_decoder(streams=S, process_window=16000, prefix_tokens=None)``: the decoding side of S live streams; see ``push``."""
+    _what = "stream_decoder"
+    _offline = "decode_unit"
+
+    def __init__(self, codec, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
+                 chunks_per_call: Optional[int] = None):
+        super().__init__(codec, streams, process_window, prefix_tokens, chunks_per_call, in_tokens=True)
+
+    def push(self, audio_feature=None, indices=None, lengths=None, end=None, validate: bool = False):
+        """New tokens of every stream — int indices (S, m) or features (S, m, C), ``lengths`` in tokens (0..m) — -> ``(wave, n_tok)``:
+        ``wave (S, T_out * hop)`` fp32, zero after each stream's own samples, and ``n_tok`` (int32, CPU): tokens' worth of audio emitted
+        per stream by this call.  ``end`` as in ``StreamEncoder.push``.
+
+        The step is ``process_window // hop`` tokens, as in ``decode_long``.  The concatenation of what a stream emits is, chunk by
+        chunk, ``decode_audio`` of tokens ``[max(0, k * cl - P), (k + 1) * cl)`` alone with its first look-back samples dropped, bit
+        for bit; for P < cl, ``decode_long``'s row.  The feature form and the index form agree; a session keeps the form of its first
+        push (another form is accepted once no stream holds anything).  Out-of-range indices are clamped and counted as in
+        ``decode_long``: a token inside a look-back counts each time it is decoded, and ``validate=True`` raises — after the push has
+        taken effect — reporting occurrences.  A flush whose row is too short for the first EnhanceBlock raises ``decode_audio``'s
+        ValueError before any device work, the session unchanged.  No ``sample_rate=`` (see ``StreamEncoder.push``); steady pushes are
+        capturable as there."""
+        src = audio_feature if audio_feature is not None else indices
+        if src is None:
+            raise ValueError("stream_decoder.push needs audio_feature or indices")
+        mc, hop, dev = self.codec.network.mc, self.hop, self._device
+        if not isinstance(src, torch.Tensor):
+            raise ValueError("stream_decoder.push needs a tensor")
+        if audio_feature is not None:
+            if src.dim() != 3 or src.shape[-1] != mc.feature_dim or src.shape[0] != self.streams:
+                raise ValueError(f"audio_feature must be ({self.streams}, tokens, {mc.feature_dim}), got {tuple(src.shape)}")
+        elif src.dim() != 2 or src.shape[0] != self.streams or src.dtype.is_floating_point:
+            raise ValueError(f"indices must be an integer ({self.streams}, tokens) tensor, got {src.dtype} {tuple(src.shape)}")
+        c = mc.feature_dim if audio_feature is not None else 1
+        lens = self._lengths(lengths, src.shape[1], "lengths (tokens)")
+        ends = self._ends(end)
+        self._check_network(src, "decode input")
+        self._check_capture(lens, ends)
+        dtype = torch.float32 if audio_feature is not None else torch.int32
+        if self._buf is not None and (self._buf.dtype != dtype or self._c != c) and any(st.held for st in self._states):
+            raise ValueError("stream_decoder.push: this session holds " + ("features" if self._c > 1 else "indices") +
+                             "; the other form is accepted once no stream holds anything (end or reset)")
+        plan = self._plan(lens, ends)
+        if plan.rows and min(r.frames for _, _, r in plan.rows) * mc.en_coder_compress_rate < 2:
+            # reference behaviour, as decode_audio: the first EnhanceBlock's InstanceNorm1d raises on a single frame
+            raise ValueError(f"Expected more than 1 spatial element when training, got input size torch.Size([{self.streams}, 4, 1])")
+        new = src.to(dtype)
+        if not new.is_contiguous() and new.numel():
+            new = new.contiguous()
+        descs, total, width = self._emit_plan(plan, hop, 1)
+        wave = torch.empty((self.streams, width), dtype=torch.float32, device=dev)
+        ctx = self._ctx
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            before = ctx.bad_index_count() if validate and audio_feature is None else 0
+            if validate:
+                self.codec._coop_check_before(ctx, "stream_decoder.push")
+            self._state_buffer(new, c)
+            rows_t = self._move(plan, new, max(new.shape[1], 1), c, stream)
+            self._states = plan.after
+            for group, rows, desc in zip(plan.groups, rows_t, descs):
+                g = len(group)
+                toks = [plan.rows[k][2].frames for k in group]
+                longest = max(toks)
+                out = torch.empty((g, longest * hop), dtype=torch.float32, device=dev)
+                f_ptr, i_ptr = (rows.data_ptr(), None) if audio_feature is not None else (None, rows.data_ptr())
+                if min(toks) == longest:  # rows of one length: the plain call, the same bits
+                    _capi.check(ctx.lib.l3ac_decode(ctx.handle, f_ptr, i_ptr, g, longest, out.data_ptr(), stream))
+                else:
+                    _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, g, longest, (ctypes.c_int32 * g)(*toks), out.data_ptr(), stream))
+                self._emit(out, desc, wave, stream)
+            if validate:
+                self.codec._raise_on_coop_timeout(ctx, "stream_decoder.push")
+            if validate and audio_feature is None:
+                bad = ctx.bad_index_count() - before
+                if bad:
+                    raise ValueError(f"{bad} index occurrences in the chunk rows (a token in a look-back counts each time it is decoded) "
+                                     f"lie outside [0, {mc.codebook_size}): corrupted token stream")
+        return wave, torch.tensor([n // hop for n in total], dtype=torch.int32)
