@@ -319,6 +319,46 @@ int l3ac_stream_append(const void* fresh, int64_t fresh_frames, int64_t fresh_st
 int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* dst,
                      int32_t streams, int64_t dst_stride, int64_t out_frames, void* stream);
 
+/* ---- streaming sample-rate conversion: packets in, l3ac_resample's bits out ---------------------------
+ * S live streams at in_rate are converted to out_rate push by push.  With l3ac_resample's up, down, half_len and
+ * K = ceil((2 half_len + 1) / up), output m of a stream reads its inputs i(m) - (K - 1) .. i(m), i(m) = (m down + half_len) div up, with the
+ * taps of phase (m down + half_len) mod up.  A stream that has received N inputs and emitted E outputs keeps its last `held` inputs
+ * (0 <= held <= K - 1) in its row of a state buffer [streams][state_stride], state_stride >= l3ac_resample_stream_state().  A push of n new
+ * inputs makes N' = N + n and emits outputs [E, E'):
+ *   not ended:  E' = max(0, ceil((N' up - half_len) / down))   exactly the outputs whose newest input exists: the output lags the input
+ *                                                              by half_len / up input samples;
+ *               held' = N' - max(0, i(E') - (K - 1))
+ *   ended:      E' = ceil(N' up / down), held' = 0             inputs past the end count as zeros, as in l3ac_resample; the slot is fresh.
+ * The device is told none of N, E: a descriptor carries q0 = E down + half_len - (N - held) up, which lies in [0, K up), so nothing handed
+ * over grows with the age of a stream.  The stream's input is the virtual row state_in[slot][0 : held] ++ fresh[slot][0 : take] ++ zeros
+ * (zeros before it as well), read in place; output j of the push has its newest input at row position (q0 + j down) div up.
+ *   l3ac_resample_stream_state: HOST only: floats per state row, K - 1 rounded up to a multiple of 4; < 0 for unsupported rates.
+ *   l3ac_resample_stream:       ONE launch per ResampleStreamBlock of descriptors (128): out[slot][0 : count] = the stream's outputs, zeros from
+ *                               there to out_frames (<= out_stride; every element below out_frames of a described stream's row is written
+ *                               once, rows without a descriptor are not touched), and state_out[slot][0 : keep] = the last `keep` frames of
+ *                               state_in[slot][0 : held] ++ fresh[slot][0 : take].  state_in and state_out are two buffers that must not
+ *                               overlap (a session alternates them; describe idle streams too, with keep = held, so that their state
+ *                               follows); `bank` is the DEVICE copy of l3ac_resample_bank's output.  out may be null when out_frames is 0,
+ *                               fresh when no descriptor takes any.  Equal rates: out[slot][0 : take] = fresh[slot][0 : take] bit for bit
+ *                               (held, keep must be 0 and count == take; the state buffers and the bank are not used).
+ * Bit guarantee: every output is the fp32 fmaf chain over t = 0 .. K - 1 in that order from +0, l3ac_resample's documented arithmetic;
+ * for finite input, and however a stream's samples are split over pushes, the concatenation of what it emits equals l3ac_resample of the
+ * whole stream bit for bit.  `desc` is a HOST array with at most one descriptor per stream, checked before anything is launched (stream
+ * in range, held within the state row, take within the packet, count within the output row, keep <= held + take, q0 in [0, K up)) and
+ * handed to the device as kernel arguments: graph-safe as far as the entry goes.  Enqueue only. */
+typedef struct l3ac_resample_stream_desc {
+    int32_t slot;    /* stream: row of the state buffers, of the new samples and of the output */
+    int32_t held;    /* samples at the front of the stream's row of state_in */
+    int32_t take;    /* new samples, from the front of the stream's row of `fresh` */
+    int32_t count;   /* outputs this push emits */
+    int32_t keep;    /* samples the stream holds afterwards: the last `keep` of held + take */
+    int32_t q0;      /* E down + half_len - (N - held) up */
+} l3ac_resample_stream_desc;
+int64_t l3ac_resample_stream_state(int32_t in_rate, int32_t out_rate);
+int l3ac_resample_stream(const float* state_in, float* state_out, int32_t streams, int64_t state_stride, const float* fresh, int64_t fresh_frames,
+                         int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
+                         int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream);
+
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */

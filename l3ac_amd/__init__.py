@@ -36,11 +36,12 @@ import torch
 from . import _capi
 from . import weights as _weights
 from .chunking import ChunkData, plan as _chunk_plan
-from .streaming import StreamDecoder, StreamEncoder
+from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
-           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder"]
+           "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder",
+           "StreamResampler", "stream_resampler"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -582,7 +583,8 @@ class L3AC:
         ``extract_unit``, at least one hop.  ``prefix_tokens``: the look-back (default: the attention window, as everywhere else); it
         may be below, at or above the step, and 0 means independent windows.  ``chunks_per_call``: as in ``encode_long``.  The network
         must be on its GPU; a session belongs to the context it was created on.  There is no ``sample_rate=``: converting a live
-        stream needs the filter's own carried state."""
+        stream needs the filter's own carried state, which is a session of its own: put ``l3ac_amd.stream_resampler(streams, rate,
+        config.sample_rate)`` in front (``StreamResampler``) for ``encode_long(..., sample_rate=rate)``'s bits."""
         return StreamEncoder(self, streams, process_window, prefix_tokens, chunks_per_call)
 
     def stream_decoder(self, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
@@ -797,6 +799,24 @@ def resample(audio: torch.Tensor, orig_sr: int, target_sr: int) -> torch.Tensor:
             x.data_ptr(), b, t, x.stride(0) if b > 1 else t, orig_sr, target_sr, None if bank is None else bank.data_ptr(),
             y.data_ptr(), n_out, torch.cuda.current_stream(dev).cuda_stream))
     return y
+
+
+def stream_resampler(streams: int, orig_sr: int, target_sr: int) -> StreamResampler:
+    """A session that converts ``streams`` concurrent live streams from ``orig_sr`` to ``target_sr`` packet by packet:
+    ``y, n = rs.push(audio, lengths=None, end=None)`` takes each stream's new samples and returns the converted samples they complete.
+    However a stream is split over pushes, what it emits adds up to ``resample`` of the whole stream, bit for bit, and to
+    ``resample_length`` samples once it has ended (``StreamResampler.push``).  Needs no codec; it composes with the codec's sessions::
+
+        rs  = l3ac.stream_resampler(S, 48000, codec.config.sample_rate)
+        enc = codec.stream_encoder(streams=S, process_window=16000)
+        y, n = rs.push(packet_48k, lengths=new_samples, end=finished)
+        q_feature, indices = enc.push(y, lengths=n, end=finished)        # encode_long(..., sample_rate=48000)'s bits
+        # decoding side
+        wave, n_tok = dec.push(indices=..., lengths=..., end=finished)
+        out, n_out = rs_out.push(wave, lengths=n_tok * hop, end=finished)  # decode_long(..., sample_rate=44100)'s bits
+
+    Rates are checked here (``resample_length``'s errors); the state lives on the device of the first push."""
+    return StreamResampler(streams, orig_sr, target_sr)
 
 
 def get_model(config_name, model_dir=None, synthetic_seed: Optional[int] = None, synthetic_profile: str = "mild") -> L3AC:

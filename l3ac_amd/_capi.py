@@ -51,6 +51,11 @@ class StreamDesc(C.Structure):
                 ("keep", C.c_int32), ("prefix", C.c_int32), ("zero", C.c_int32), ("out", C.c_int64)]
 
 
+class ResampleStreamDesc(C.Structure):
+    """l3ac_resample_stream_desc: one stream's share of one converting push (include/l3ac_hip.h)."""
+    _fields_ = [("slot", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("count", C.c_int32), ("keep", C.c_int32), ("q0", C.c_int32)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -121,6 +126,8 @@ SIGNATURES = {
     "l3ac_stream_carry": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _P]),
     "l3ac_stream_append": (C.c_int, [_P, _I64, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _P]),
     "l3ac_stream_emit": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _I64, _P]),
+    "l3ac_resample_stream_state": (_I64, [_I32, _I32]),
+    "l3ac_resample_stream": (C.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _I32, _P, C.POINTER(ResampleStreamDesc), _I32, _P, _I64, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

@@ -43,6 +43,7 @@ SOURCES = [
     "kernels/up_fused.hip",
     "kernels/ragged.hip",
     "kernels/resample.hip",
+    "kernels/resample_stream.hip",
     "kernels/chunk.hip",
     "kernels/stream.hip",
 ]

@@ -774,6 +774,20 @@ int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32
     return launch_stream_emit((hipStream_t)stream, rows, n_rows, row_frames, c, desc, count, dst, streams, dst_stride, out_frames);
 }
 
+// ---- streaming sample-rate conversion ---------------------------------------------
+int64_t l3ac_resample_stream_state(int32_t in_rate, int32_t out_rate) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    return resample_stream_state_floats(p);
+}
+
+int l3ac_resample_stream(const float* state_in, float* state_out, int32_t streams, int64_t state_stride, const float* fresh, int64_t fresh_frames,
+                         int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
+                         int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream) {
+    return launch_resample_stream((hipStream_t)stream, state_in, state_out, streams, state_stride, fresh, fresh_frames, fresh_stride, in_rate,
+                                  out_rate, bank, desc, count, out, out_frames, out_stride);
+}
+
 int l3ac_profile_begin(void) {
     L3AC_REQUIRE(g_profiler == nullptr, "profile already active on this thread");
     g_profiler = new (std::nothrow) Profiler();

@@ -229,6 +229,16 @@ int launch_stream_append(hipStream_t s, const void* fresh, int64_t fresh_frames,
 // frames [prefix, held + take + pad) of row desc.row -> dst[slot][out ...], then `zero` zero frames
 int launch_stream_emit(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* dst,
                        int streams, int64_t dst_stride, int64_t out_frames);
+// streaming sample-rate conversion (kernels/resample_stream.hip): one launch per push computes every stream's outputs
+// from state ++ new samples and writes its next state into the other state buffer; descriptors as kernel arguments, CAP per launch
+struct ResampleStreamBlock {
+    static constexpr int CAP = 128;  // 3 KiB of the 4 KiB a launch's arguments may take
+    l3ac_resample_stream_desc desc[CAP];
+};
+int64_t resample_stream_state_floats(const ResamplePlan& p);  // K - 1 rounded up to a multiple of 4
+int launch_resample_stream(hipStream_t s, const float* state_in, float* state_out, int streams, int64_t state_stride, const float* fresh,
+                           int64_t fresh_frames, int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank,
+                           const l3ac_resample_stream_desc* desc, int count, float* out, int64_t out_frames, int64_t out_stride);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -10,10 +10,14 @@ look-back grows over the first ``ceil(lookback / step)`` chunks until it is full
 Then the sessions, ``StreamEncoder`` / ``StreamDecoder`` (``L3AC.stream_encoder`` / ``L3AC.stream_decoder``): the state carried
 between pushes lives in one device buffer per session, moved by the kernels of csrc/kernels/stream.hip; every chunk runs as a row of
 the ragged calls, so its bits are those of ``encode_audio`` / ``decode_audio`` on that chunk alone.
+
+Last, streaming sample-rate conversion: its geometry (``resample_advance``) and ``StreamResampler``
+(``l3ac_amd.stream_resampler``), whose carried state is each stream's last inputs; one launch of csrc/kernels/resample_stream.hip per push.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -99,7 +103,81 @@ def round4(n: int) -> int:
     return -(-n // 4) * 4
 
 
+# ---- 1b. streaming sample-rate conversion: geometry ----------------------------------------------------------
+class ResampleGeometry(NamedTuple):
+    """``resample``'s plan for a rate pair: up / down = target / orig reduced, half_len = 10 max(up, down), K taps per output.  Output m reads
+    inputs ``i(m) - (K - 1) .. i(m)``, ``i(m) = (m * down + half_len) // up``, with the taps of phase ``(m * down + half_len) % up``."""
+    up: int
+    down: int
+    half_len: int
+    K: int
+
+    def newest(self, m: int) -> int:
+        return (m * self.down + self.half_len) // self.up
+
+    def length(self, n_in: int) -> int:
+        """``resample_length``: ceil(n_in * up / down)."""
+        return -(-n_in * self.up // self.down)
+
+
+def resample_geometry(orig_sr: int, target_sr: int) -> ResampleGeometry:
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if orig_sr < 1 or target_sr < 1:
+        raise ValueError(f"resample: rates must be positive (got {orig_sr} -> {target_sr})")
+    g = math.gcd(orig_sr, target_sr)
+    up, down = target_sr // g, orig_sr // g
+    half_len = 10 * max(up, down)
+    return ResampleGeometry(up, down, half_len, -(-(2 * half_len + 1) // up))
+
+
+class ResampleState(NamedTuple):
+    """What one converted stream is between pushes: its last ``held`` inputs are on the device; ``seen`` inputs received, ``emitted`` outputs
+    produced so far (Python ints: they never reach the device)."""
+    held: int = 0
+    seen: int = 0
+    emitted: int = 0
+
+
+class ResamplePush(NamedTuple):
+    """One stream's share of one push, l3ac_resample_stream_desc's fields: the stream's input is ``state[0:held] ++ new[0:take] ++ zeros``,
+    output j of the push has ``q = q0 + j * down`` (newest input at row position ``q // up``, phase ``q % up``), ``count`` outputs are
+    emitted, and the stream keeps the last ``keep`` of its held + take inputs."""
+    q0: int
+    count: int
+    held: int
+    take: int
+    keep: int
+
+
+def resample_advance(state: ResampleState, new_frames: int, end: bool, geo: ResampleGeometry) -> Tuple[ResamplePush, ResampleState]:
+    """One push of ``new_frames`` inputs onto a stream in ``state``.  Not ended: the outputs whose newest input exists by now are emitted
+    (they lag the input by half_len / up input samples).  ``end``: inputs past the end count as zeros, as in ``resample``; the outputs up to
+    ``ceil(seen * up / down)`` are emitted and the state afterwards is a fresh stream's.  Equal rates pass the inputs through at once."""
+    if new_frames < 0:
+        raise ValueError(f"{new_frames} new frames")
+    up, down, half_len, K = geo
+    held, seen, done = state
+    now = seen + new_frames
+    q0 = done * down + half_len - (seen - held) * up
+    if up == down:
+        count, keep = new_frames, 0
+    elif end:
+        count, keep = geo.length(now) - done, 0
+    else:
+        upto = max(0, -(-(now * up - half_len) // down))
+        count = upto - done
+        keep = now - max(0, geo.newest(upto) - (K - 1))
+    push = ResamplePush(q0, count, held, new_frames, keep)
+    return push, (ResampleState() if end else ResampleState(keep, now, done + count))
+
+
 # ---- 2. sessions -------------------------------------------------------------------------------------------------------------
+def _check_streams(streams) -> int:
+    if isinstance(streams, bool) or int(streams) != streams or int(streams) < 1:
+        raise ValueError(f"streams must be a positive integer, got {streams!r}")
+    return int(streams)
+
+
 class _PushPlan(NamedTuple):
     rows: list       # (slot, round, StreamRow), in row order of the whole push: shortest first
     groups: list     # lists of indices into rows: one ragged call each
@@ -115,8 +193,7 @@ class _Session:
     def __init__(self, codec, streams: int, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int], in_tokens: bool):
         mc = codec.network.mc
         hop = mc.hop_length
-        if isinstance(streams, bool) or int(streams) != streams or int(streams) < 1:
-            raise ValueError(f"streams must be a positive integer, got {streams!r}")
+        _check_streams(streams)
         if int(process_window) != process_window or int(process_window) < hop:
             raise ValueError(f"process_window ({process_window} samples) must be at least one hop ({hop} samples)")
         prefix_tokens = mc.en_coder_window_size if prefix_tokens is None else prefix_tokens
@@ -335,8 +412,9 @@ class StreamEncoder(_Session):
         chunk by chunk, ``encode_audio`` of chunk ``[max(0, k * CL - P), (k + 1) * CL)`` alone with the look-back tokens dropped, bit
         for bit (CL = ``process_window`` in whole hops, P = ``prefix_tokens`` hops): for P < CL, ``encode_long``'s row.  After t
         samples ``floor(t / CL) * CL / hop`` tokens have been emitted, after ``end`` ``ceil(t / hop)``.
-        There is no ``sample_rate=``: converting a live stream needs the filter's own carried state; convert packets with
-        ``l3ac.resample`` at your own risk of edge effects, or push at the codec's rate.
+        There is no ``sample_rate=``: converting a live stream needs the filter's own carried state, which ``l3ac_amd.stream_resampler``
+        keeps: push its output (``y, n = rs.push(packet, ...)``; ``enc.push(y, lengths=n, end=...)``) for
+        ``encode_long(..., sample_rate=)``'s bits (``StreamResampler``).
         A steady push (every look-back full, nothing pending, every length CL, no end) can be captured into a graph after
         ``context().reserve(S, P + CL)`` and one eager steady push; under stream capture any other push raises RuntimeError.
         ``validate``: as encode_audio."""
@@ -405,8 +483,9 @@ class StreamDecoder(_Session):
         push (another form is accepted once no stream holds anything).  Out-of-range indices are clamped and counted as in
         ``decode_long``: a token inside a look-back counts each time it is decoded, and ``validate=True`` raises — after the push has
         taken effect — reporting occurrences.  A flush whose row is too short for the first EnhanceBlock raises ``decode_audio``'s
-        ValueError before any device work, the session unchanged.  No ``sample_rate=`` (see ``StreamEncoder.push``); steady pushes are
-        capturable as there."""
+        ValueError before any device work, the session unchanged.  No ``sample_rate=``: push ``wave`` with ``lengths=n_tok * hop`` into a
+        ``l3ac_amd.stream_resampler(S, config.sample_rate, rate)`` for ``decode_long(..., sample_rate=rate)``'s bits
+        (``StreamResampler``).  Steady pushes are capturable as in ``StreamEncoder.push``."""
         src = audio_feature if audio_feature is not None else indices
         if src is None:
             raise ValueError("stream_decoder.push needs audio_feature or indices")
@@ -464,3 +543,125 @@ class StreamDecoder(_Session):
                     raise ValueError(f"{bad} index occurrences in the chunk rows (a token in a look-back counts each time it is decoded) "
                                      f"lie outside [0, {mc.codebook_size}): corrupted token stream")
         return wave, torch.tensor([n // hop for n in total], dtype=torch.int32)
+
+
+# ---- 3. streaming sample-rate conversion: the session -------------------------------------------------------------
+class StreamResampler:
+    """``l3ac_amd.stream_resampler(streams, orig_sr, target_sr)``: S concurrent live streams converted from ``orig_sr`` to ``target_sr``
+    packet by packet, with ``resample``'s bits; see ``push``.  Needs no codec and no context, as ``resample`` needs none.  In front of a
+    ``stream_encoder``, or behind a ``stream_decoder``, it makes a live stream at another rate give ``encode_long(..., sample_rate=)``'s /
+    ``decode_long(..., sample_rate=)``'s bits::
+
+        rs  = l3ac.stream_resampler(S, 48000, codec.config.sample_rate)
+        enc = codec.stream_encoder(streams=S, process_window=16000)
+        y, n = rs.push(packet_48k, lengths=new_samples, end=finished)
+        q_feature, indices = enc.push(y, lengths=n, end=finished)        # encode_long(..., sample_rate=48000)'s bits
+        # decoding side
+        wave, n_tok = dec.push(indices=..., lengths=..., end=finished)
+        out, n_out = rs_out.push(wave, lengths=n_tok * hop, end=finished)  # decode_long(..., sample_rate=44100)'s bits
+    """
+
+    def __init__(self, streams: int, orig_sr: int, target_sr: int):
+        self.streams = _check_streams(streams)
+        if isinstance(orig_sr, bool) or isinstance(target_sr, bool) or int(orig_sr) != orig_sr or int(target_sr) != target_sr:
+            raise ValueError(f"rates must be integers, got {orig_sr!r} -> {target_sr!r}")
+        self.orig_sr, self.target_sr = int(orig_sr), int(target_sr)
+        self._lib = _capi.load_library()
+        if not (0 < self.orig_sr < 2 ** 31 and 0 < self.target_sr < 2 ** 31):
+            raise ValueError(f"resample: rates must be positive 32-bit integers (got {self.orig_sr} -> {self.target_sr})")
+        state = self._lib.l3ac_resample_stream_state(self.orig_sr, self.target_sr)
+        if state < 0:  # resample_length's error: a reduced max(up, down) above 1024
+            raise ValueError(self._lib.l3ac_last_error().decode())
+        self.geometry = resample_geometry(self.orig_sr, self.target_sr)
+        self.state_frames = int(state)
+        assert self.state_frames == round4(self.geometry.K - 1)
+        self._states = [ResampleState() for _ in range(self.streams)]
+        self._device = None
+        self._bufs = None  # two [streams][state_frames] buffers, read and written alternately: allocated at the first push
+        self._bank = None
+
+    _lengths = _Session._lengths
+    _ends = _Session._ends
+
+    @property
+    def states(self) -> List[ResampleState]:
+        """The streams' host state (a copy): inputs held on the device, inputs seen and outputs emitted since the stream began."""
+        return list(self._states)
+
+    @property
+    def delay(self) -> float:
+        """How far the output lags the input, in input samples: half_len / up (0 at equal rates).  ``end`` flushes it."""
+        geo = self.geometry
+        return 0.0 if geo.up == geo.down else geo.half_len / geo.up
+
+    def reset(self, streams=None) -> None:
+        """Make the given streams (an index, a sequence of them; absent: all) fresh: what they hold is dropped, nothing is emitted."""
+        which = range(self.streams) if streams is None else [streams] if isinstance(streams, int) else list(streams)
+        which = [int(i) for i in which]
+        bad = [i for i in which if not 0 <= i < self.streams]
+        if bad:
+            raise ValueError(f"stream {bad[0]} of {self.streams}")
+        for i in which:
+            self._states[i] = ResampleState()
+
+    @torch.no_grad()
+    def push(self, audio, lengths=None, end=None):
+        """New samples of every stream at ``orig_sr`` -> ``(y, lengths_out)``: the samples at ``target_sr`` they complete.
+
+        ``audio`` (S, n) fp32 CUDA, n >= 0: row i holds stream i's new samples, ``lengths[i]`` in 0..n of them (absent: n; samples at or
+        after ``lengths[i]`` are ignored, whatever they hold).  ``end``: a bool or S bools; a stream that ends emits the rest of its
+        outputs, the samples after its end counting as zeros, and its slot starts fresh.  ``y`` is (S, T_out) fp32, zero after each
+        stream's own outputs; ``lengths_out`` (int32, CPU) holds the outputs per stream, ``T_out`` is their maximum and may be 0.
+
+        For finite input, however a stream's samples are split over pushes and whatever the other streams do, the concatenation of what
+        stream i emits is ``resample(x_i[None, :], orig_sr, target_sr)[0]`` bit for bit; ``resample_length(orig_sr, target_sr, N)`` samples
+        have been emitted once a stream of N samples has ended.  Before that an output is emitted as soon as its newest input has
+        arrived: the output lags the input by ``delay`` input samples.  Equal rates pass the samples through at once, bit for bit.
+        Non-finite samples INSIDE a stream are outside the guarantee (the offline kernel multiplies a few more of them by zero taps).
+        One kernel launch per push, no host synchronisation; every count is a host integer.  Errors are raised before any device work and
+        leave the session unchanged.  A push under stream capture raises RuntimeError: the host position advances with every push, so
+        a captured push would replay one position for ever."""
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 2 or audio.shape[0] != self.streams:
+            raise ValueError(f"audio must be a ({self.streams}, samples) tensor, got {tuple(getattr(audio, 'shape', ()))}")
+        n = audio.shape[1]
+        lens = self._lengths(lengths, n, "lengths")
+        ends = self._ends(end)
+        if not audio.is_cuda:
+            raise RuntimeError(f"stream_resampler: audio is on {audio.device}: l3ac_amd has no CPU path")
+        if self._device is not None and audio.device != self._device:
+            raise RuntimeError(f"stream_resampler: audio is on {audio.device} but the session's state is on {self._device}")
+        if n >= 2 ** 31:
+            raise ValueError(f"stream_resampler: a push of {n} samples")
+        dev = audio.device
+        with torch.cuda.device(dev):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("stream_resampler: a push cannot be captured into a graph: the position of every stream in the filter's "
+                                   "phase cycle is a host value that advances with every push")
+        from . import _resample_bank
+        geo = self.geometry
+        plan = [resample_advance(st, m, e, geo) for st, m, e in zip(self._states, lens, ends)]
+        total = [p.count for p, _ in plan]
+        width = max(total)
+        new = audio.to(torch.float32)
+        if new.stride(-1) != 1 and new.numel():
+            new = new.contiguous()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            copy = geo.up == geo.down
+            if self._device is None:
+                bank = _resample_bank(dev, self.orig_sr, self.target_sr)
+                bufs = None if copy else [torch.zeros((self.streams, self.state_frames), dtype=torch.float32, device=dev) for _ in range(2)]
+                self._device, self._bank, self._bufs = dev, bank, bufs
+            y = torch.empty((self.streams, width), dtype=torch.float32, device=dev)
+            desc = (_capi.ResampleStreamDesc * self.streams)(*[_capi.ResampleStreamDesc(i, p.held, p.take, p.count, p.keep, p.q0)
+                                                                for i, (p, _) in enumerate(plan)])
+            src, dst = (None, None) if copy else (self._bufs[0].data_ptr(), self._bufs[1].data_ptr())
+            _capi.check(self._lib.l3ac_resample_stream(
+                src, dst, self.streams, self.state_frames, new.data_ptr() if new.numel() else None, n,
+                new.stride(0) if self.streams > 1 and n else max(n, 1), self.orig_sr, self.target_sr,
+                None if self._bank is None else self._bank.data_ptr(), desc, self.streams, y.data_ptr() if width else None, width,
+                max(width, 1), stream))
+            if not copy:
+                self._bufs.reverse()
+            self._states = [after for _, after in plan]
+        return y, torch.tensor(total, dtype=torch.int32)

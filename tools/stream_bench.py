@@ -5,7 +5,10 @@ window), in the steady state.  One push of every stream, encoder and decoder tim
   graph   the same steady push captured once and replayed
   cat     what a caller had to write before sessions: keep the look-back in a tensor, torch.cat it in front of the new frames, run
           encode_audio / decode_audio on the rows, slice the look-back off again and keep the rows' tail for the next step
-`eager`, `graph` and `cat` are checked bit-equal before anything is timed.  Timings: device events around --inner pushes, --reps passes
+  conv    the eager sessions with sample-rate conversion on both sides: a --in-rate (48 kHz) stream_resampler in
+          front of the encoder, fed packets that convert to one step, and a --out-rate (44.1 kHz) one behind the decoder; `rs_in` /
+          `rs_out` time those resampler pushes alone, `resample_in` / `resample_out` the offline l3ac_amd.resample on the same packet
+`eager`, `graph` and `cat` are checked bit-equal before anything is timed, and the resampler's pushes against resample of what it was fed.  Timings: device events around --inner pushes, --reps passes
 per variant after --warm, the variants alternating pass by pass; the JSON line (one per S) gives each variant's median and its
 min .. max in ms PER PUSH."""
 import argparse
@@ -105,6 +108,34 @@ def run(codec, streams, args):
         assert torch.equal(q, qc) and torch.equal(cat_decode(ic), wave), f"step {j}: cat gives other bits"
     new_idx = ind["indices"]
 
+    # ---- conversion on both sides: sessions of their own behind / in front of resamplers, brought to the steady state ---------------------
+    sr = codec.config.sample_rate
+    ratio_num, ratio_den = args.in_rate, sr
+    n_in = cl * ratio_num // ratio_den  # a packet at the input rate that converts to one step
+    x_in = (torch.rand(streams, n_in, generator=g) - 0.5).cuda()
+    rs_in, rs_out = l3ac_amd.stream_resampler(streams, args.in_rate, sr), l3ac_amd.stream_resampler(streams, sr, args.out_rate)
+    rs_in_alone, rs_out_alone = l3ac_amd.stream_resampler(streams, args.in_rate, sr), l3ac_amd.stream_resampler(streams, sr, args.out_rate)
+    c_enc, c_dec = codec.stream_encoder(streams=streams, process_window=args.window), codec.stream_decoder(streams=streams, process_window=args.window)
+
+    def conv_encode():
+        y, n = rs_in.push(x_in)
+        return c_enc.push(y, lengths=n)
+
+    def conv_decode():
+        w, n_tok = c_dec.push(indices=new_idx)
+        return rs_out.push(w, lengths=n_tok * hop)
+
+    got_in, got_out = [], []
+    for j in range(fill + 2):
+        conv_encode()
+        conv_decode()
+        got_in.append(rs_in_alone.push(x_in)[0])
+        got_out.append(rs_out_alone.push(wave)[0])
+    for got, piece, rates in ((got_in, x_in, (args.in_rate, sr)), (got_out, wave, (sr, args.out_rate))):
+        got = torch.cat(got, dim=1)
+        want = l3ac_amd.resample(torch.cat([piece] * (fill + 2), dim=1), *rates)
+        assert torch.equal(got, want[:, :got.shape[1]]), "the streaming resampler gives other bits than resample"
+
     # ---- timing: every variant stays in the steady state, so any step serves as the next push ----------------------------------
     inner = args.inner
     x = steps[-1]
@@ -122,14 +153,22 @@ def run(codec, streams, args):
         "dec_eager": lambda: dec.push(indices=new_idx),
         "dec_graph": graph_dec.replay,
         "dec_cat": lambda: cat_decode(new_idx),
+        "enc_conv": conv_encode,
+        "dec_conv": conv_decode,
+        "rs_in": lambda: rs_in_alone.push(x_in),
+        "rs_out": lambda: rs_out_alone.push(wave),
+        "resample_in": lambda: l3ac_amd.resample(x_in, args.in_rate, sr),
+        "resample_out": lambda: l3ac_amd.resample(wave, sr, args.out_rate),
     }.items()}, args.reps, args.warm)
     out = {"config": args.config, "streams": streams, "step_samples": cl, "step_tokens": cl_tok, "lookback_tokens": p_tok,
-           "row_tokens": p_tok + cl_tok, "bit_equal": True, "inner": inner}
+           "row_tokens": p_tok + cl_tok, "bit_equal": True, "inner": inner, "in_rate": args.in_rate, "out_rate": args.out_rate,
+           "in_packet_samples": n_in}
     for name, v in ms.items():
         out[name] = summary(v, inner)
     for side in ("enc", "dec"):
         out[f"{side}_eager_over_cat"] = round(out[f"{side}_eager"]["median_ms"] / out[f"{side}_cat"]["median_ms"], 3)
         out[f"{side}_graph_over_eager"] = round(out[f"{side}_graph"]["median_ms"] / out[f"{side}_eager"]["median_ms"], 3)
+        out[f"{side}_conv_added_ms"] = round(out[f"{side}_conv"]["median_ms"] - out[f"{side}_eager"]["median_ms"], 3)
     print(json.dumps(out), flush=True)
 
 
@@ -142,6 +181,8 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--in-rate", type=int, default=48000, help="rate of the live input of the `conv` variant")
+    ap.add_argument("--out-rate", type=int, default=44100, help="rate of the audio the `conv` variant returns")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs a GPU: a timing taken anywhere else says nothing")
