@@ -359,6 +359,54 @@ int l3ac_resample_stream(const float* state_in, float* state_out, int32_t stream
                          int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
                          int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream);
 
+/* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
+ * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
+ * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the
+ * first ceil(n*bits/8) bytes of the row that the rectangular pack call writes for the same tokens (the rest of that row is zero).  Bits of an
+ * index above `bits` are dropped.  bits in 1..32.
+ * S live streams are packed / unpacked push by push; a stream's carried state is ONE uint32 in its slot of a state buffer [streams]:
+ *   packing:    the `held` bits (0..7, the low bits of state_in[slot]) that have not filled a byte yet.  The stream's input is the virtual bit
+ *               string  held bits ++ `take` tokens from the front of fresh[slot] (int32 [streams][fresh_stride]),  T = held + take*bits bits.
+ *               not ended: count = T div 8 bytes, keep = T mod 8;     ended: count = ceil(T / 8), keep = 0 and the slot is fresh.
+ *   unpacking:  the `held` bits (0..bits-1) that have not completed a token yet, followed by `take` bytes from the front of fresh[slot]
+ *               (uint8 [streams][fresh_stride], any byte alignment), T = held + 8*take bits.
+ *               not ended: count = T div bits tokens, keep = T mod bits;     ended: keep = 0, the slot is fresh, and count tokens are emitted
+ *               with 0 <= T - count*bits < max(bits, 8): the bits dropped are a stream's byte padding (for bits >= 8: count = T div bits).
+ * Neither the tokens nor the bytes a stream has seen reach the device: nothing in a descriptor grows with the age of a stream.
+ *   l3ac_packed_bytes:   HOST only: ceil(n_tok*bits/8), or < 0 for n_tok < 0 or bits outside 1..32.
+ *   l3ac_pack_stream:    ONE launch per 160 descriptors: out[slot][0 : count] (uint8 [streams][out_stride], out_stride a multiple of 4, rows
+ *                        4-byte aligned) = the first count bytes of the virtual bit string, zeros from there to out_bytes (<= out_stride; every
+ *                        byte below out_bytes of a described stream's row is written once, rows without a descriptor are not touched), and
+ *                        state_out[slot] = the string's last `keep` bits.  Tokens at or after `take` are never read.
+ *   l3ac_unpack_stream:  the mirror: out[slot][0 : count] (int32 [streams][out_stride]) = the tokens, zeros from there to out_tokens, and
+ *                        state_out[slot] = the last `keep` bits.  Bytes at or after `take` are never read.
+ * state_in and state_out are two buffers that must not overlap (a session alternates them; describe idle streams too, with take = 0 and
+ * keep = held, so that their state follows).  They may be null when every held and keep is 0, fresh when no descriptor takes any, out when
+ * the output size is 0.  `desc` is a HOST array with at most one descriptor per stream, checked before anything is launched (stream in range,
+ * held in range, take within the packet, count within the output row, count and keep one of the two forms above) and handed to the device
+ * as kernel arguments: graph-safe as far as the entry goes.  Integer and byte work, exact by construction.  Enqueue only. */
+typedef struct l3ac_pack_stream_desc {
+    int32_t slot;    /* stream: row of the new tokens and of the output, element of the state buffers */
+    int32_t held;    /* pending bits in state_in[slot]: 0..7 */
+    int32_t take;    /* new tokens, from the front of the stream's row of `fresh` */
+    int32_t count;   /* bytes this push emits */
+    int32_t keep;    /* pending bits afterwards, written to state_out[slot] */
+} l3ac_pack_stream_desc;
+typedef struct l3ac_unpack_stream_desc {
+    int32_t slot;    /* stream: row of the new bytes and of the output, element of the state buffers */
+    int32_t held;    /* pending bits in state_in[slot]: 0..bits-1 */
+    int32_t take;    /* new bytes, from the front of the stream's row of `fresh` */
+    int32_t count;   /* tokens this push emits */
+    int32_t keep;    /* pending bits afterwards, written to state_out[slot] */
+} l3ac_unpack_stream_desc;
+int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits);
+int l3ac_pack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const int32_t* fresh, int64_t fresh_tokens,
+                     int64_t fresh_stride, int32_t bits, const l3ac_pack_stream_desc* desc, int32_t count, uint8_t* out, int64_t out_bytes,
+                     int64_t out_stride, void* stream);
+int l3ac_unpack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const uint8_t* fresh, int64_t fresh_bytes,
+                       int64_t fresh_stride, int32_t bits, const l3ac_unpack_stream_desc* desc, int32_t count, int32_t* out, int64_t out_tokens,
+                       int64_t out_stride, void* stream);
+
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
  * Shapes: x / y are [batch][frames][channels] frame-major. */

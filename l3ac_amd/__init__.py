@@ -37,11 +37,14 @@ from . import _capi
 from . import weights as _weights
 from .chunking import ChunkData, plan as _chunk_plan
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
+from . import wire as _wire
+from .wire import StreamPacker, StreamUnpacker, frame_header, pack_advance, packed_bytes, parse_frame, unpack_advance
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
            "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder",
-           "StreamResampler", "stream_resampler"]
+           "StreamResampler", "stream_resampler", "StreamPacker", "StreamUnpacker", "stream_packer", "stream_unpacker", "packed_bytes", "pack_advance",
+           "unpack_advance", "frame_header", "parse_frame"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -574,6 +577,55 @@ class L3AC:
         return _zero_after(audio, [resample_length(self.config.sample_rate, rate, n * hop) for n in tok])
 
 
+    # ---- audio -> bytes -> audio (l3ac_amd/wire.py) --------------------------------------------
+    @torch.no_grad()
+    def compress(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
+                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, validate: bool = False) -> list:
+        """A batch of recordings -> one frame of bytes per recording: ``encode_long`` (its arguments, ``sample_rate`` and ``lengths``
+        included), the ragged ``pack_indices``, one device-to-host copy.  A frame is ``wire.frame_header``'s 24 bytes followed by the
+        recording's ``packed_bytes(n_tok, bits)`` bytes; its header carries the token count and the sample count at the codec's rate
+        (after conversion, when ``sample_rate`` is given)."""
+        _, info = self.encode_long(audio_data, lengths=lengths, process_window=process_window, prefix_tokens=prefix_tokens,
+                                   sample_rate=sample_rate, chunks_per_call=chunks_per_call, validate=validate)
+        samples = ragged_lengths([audio_data.shape[1]] * audio_data.shape[0] if lengths is None else lengths, audio_data.shape[0],
+                                 audio_data.shape[1], "lengths")
+        rate = self._rate(sample_rate)
+        if rate is not None:
+            samples = [resample_length(rate, self.config.sample_rate, n) for n in samples]
+        mc = self.network.mc
+        tok = info["lengths"].tolist()
+        packed, nbytes = pack_indices(info["indices"], bits_per_token(mc), lengths=tok)
+        host = packed.cpu().numpy()
+        return [frame_header(mc, self.config.sample_rate, tok[i], samples[i]) + host[i, :k].tobytes() for i, k in enumerate(nbytes.tolist())]
+
+    @torch.no_grad()
+    def decompress(self, frames, sample_rate: Optional[int] = None, process_window: int = 5 * 16000, prefix_tokens: Optional[int] = None,
+                   chunks_per_call: Optional[int] = None, validate: bool = False):
+        """The frames of ``compress`` -> ``(audio (B, T) fp32, lengths int32 CPU)``: row i holds recording i's ``lengths[i]`` samples
+        (its header's sample count; converted with ``resample_length`` when ``sample_rate`` is given) followed by zeros, T is their
+        maximum.  Every frame is parsed and checked against this codec before any device work (``wire.parse_frame``: ValueError naming
+        the field); then one upload, the ragged ``unpack_indices`` and ``decode_long`` (its arguments).  ``decompress(compress(x, n))``
+        is ``decode_long(indices=encode_long(x, n)[1]["indices"], lengths=...)`` trimmed to the sample counts, bit for bit."""
+        if isinstance(frames, (bytes, bytearray, memoryview)):
+            raise ValueError("frames must be a sequence of frames, one per recording")
+        mc = self.network.mc
+        parsed = [parse_frame(f, mc, self.config.sample_rate) for f in frames]
+        if not parsed:
+            raise ValueError("no frames")
+        rate = self._rate(sample_rate)
+        bits = bits_per_token(mc)
+        tok = [f.n_tok for f in parsed]
+        n_tok = max(tok)
+        host = torch.zeros((len(parsed), 4 * (-(-n_tok * bits // 32))), dtype=torch.uint8)
+        for i, f in enumerate(parsed):
+            host[i, :len(f.payload)] = torch.frombuffer(bytearray(f.payload), dtype=torch.uint8)
+        self.network.context()  # raises when the network is not on a GPU
+        indices = unpack_indices(host.to(self.network.device), n_tok, bits, lengths=tok)
+        audio = self.decode_long(indices=indices, lengths=tok, process_window=process_window, prefix_tokens=prefix_tokens, sample_rate=sample_rate,
+                                 chunks_per_call=chunks_per_call, validate=validate)
+        samples = [f.n_samples if rate is None else resample_length(self.config.sample_rate, rate, f.n_samples) for f in parsed]
+        return _zero_after(audio[:, :max(samples)], samples), torch.tensor(samples, dtype=torch.int32)
+
     # ---- streaming sessions (DESIGN.md section 3.9; l3ac_amd/streaming.py) -------------------------------------------
     def stream_encoder(self, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,
                        chunks_per_call: Optional[int] = None) -> StreamEncoder:
@@ -634,11 +686,20 @@ def bits_per_token(mc) -> int:
     return max(1, (mc.codebook_size - 1).bit_length())
 
 
-def pack_indices(indices: torch.Tensor, bits: int) -> torch.Tensor:
+def pack_indices(indices: torch.Tensor, bits: int, lengths=None):
     """int indices (B, T_tok) on the GPU -> little-endian bit stream, one row of whole 32-bit words per clip, as
-    uint8 (B, 4 * ceil(T_tok * bits / 32)).  The reference has no wire format (it keeps int32 tensors)."""
+    uint8 (B, 4 * ceil(T_tok * bits / 32)).  The reference has no wire format (it keeps int32 tensors).
+    ``lengths`` (B token counts in 0..T_tok; a sequence, an array or a tensor, checked as ``ragged_lengths`` checks but a row may be
+    empty): the ragged form, ``(packed, nbytes)``: row i is the stream of its first ``lengths[i]`` tokens alone, ``nbytes[i] =
+    packed_bytes(lengths[i], bits)`` bytes (int32, CPU) followed by zeros; tokens at or after ``lengths[i]`` are ignored, whatever they
+    hold (``encode_audio(..., lengths=)`` and ``encode_long`` return such rows)."""
     if not indices.is_cuda or indices.dim() != 2:
         raise ValueError("indices must be a (batch, tokens) CUDA tensor")
+    if lengths is not None:
+        lens = _wire.token_lengths(lengths, indices.shape[0], indices.shape[1])
+        if not 1 <= int(bits) <= 32 or int(bits) != bits or indices.shape[0] == 0 or indices.shape[1] == 0:
+            raise ValueError(f"pack_indices: {tuple(indices.shape)} indices of {bits!r} bits")
+        return _wire.pack_ragged(indices.to(torch.int32).contiguous(), int(bits), lens)
     idx = indices.to(torch.int32).contiguous()
     b, n_tok = idx.shape
     words = -(-n_tok * bits // 32)
@@ -650,13 +711,19 @@ def pack_indices(indices: torch.Tensor, bits: int) -> torch.Tensor:
     return out.view(torch.uint8)
 
 
-def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int) -> torch.Tensor:
-    """Inverse of `pack_indices`: uint8 (B, 4 * words) -> int32 (B, n_tok)."""
+def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int, lengths=None) -> torch.Tensor:
+    """Inverse of `pack_indices`: uint8 (B, 4 * words) -> int32 (B, n_tok).  ``lengths`` (B token counts in 0..n_tok): the ragged form:
+    row i is zero after its own ``lengths[i]`` tokens, and bytes beyond its ``packed_bytes(lengths[i], bits)`` are never read."""
     if not packed.is_cuda or packed.dim() != 2 or packed.dtype != torch.uint8 or packed.shape[1] % 4:
         raise ValueError("packed must be a (batch, 4 * words) uint8 CUDA tensor")
     words = packed.shape[1] // 4
     if words * 32 < n_tok * bits:
         raise ValueError("packed stream too short for n_tok tokens")
+    if lengths is not None:
+        lens = _wire.token_lengths(lengths, packed.shape[0], n_tok)
+        if not 1 <= int(bits) <= 32 or int(bits) != bits or packed.shape[0] == 0 or n_tok < 1:
+            raise ValueError(f"unpack_indices: {packed.shape[0]} rows of {n_tok} tokens of {bits!r} bits")
+        return _wire.unpack_ragged(packed.contiguous(), int(n_tok), int(bits), lens)
     src = packed.contiguous().view(torch.int32)
     out = torch.empty((packed.shape[0], n_tok), dtype=torch.int32, device=packed.device)
     lib = _capi.load_library()
@@ -664,6 +731,20 @@ def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int) -> torch.Tensor:
         _capi.check(lib.l3ac_unpack_indices(src.data_ptr(), packed.shape[0], n_tok, bits, words, out.data_ptr(),
                                             torch.cuda.current_stream(packed.device).cuda_stream))
     return out
+
+
+def stream_packer(streams: int, bits: int) -> StreamPacker:
+    """A session that packs the tokens of ``streams`` concurrent live streams into the bytes of the wire, push by push:
+    ``packed, n_bytes = packer.push(indices, lengths=None, end=None)``.  However a stream's tokens are split over pushes, what it emits
+    adds up to the first ``packed_bytes(n, bits)`` bytes of ``pack_indices`` of the whole stream (``StreamPacker.push``).  ``bits`` in
+    8..32 (``bits_per_token``: 17 and 18 for the shipped models).  Needs no codec; the state lives on the device of the first push."""
+    return StreamPacker(streams, bits)
+
+
+def stream_unpacker(streams: int, bits: int) -> StreamUnpacker:
+    """The receiving side: ``indices, n_tok = unpacker.push(packed, lengths=None, end=None)`` takes any run of each stream's bytes and
+    returns the tokens they complete; what a stream emits adds up to ``unpack_indices`` of the whole stream (``StreamUnpacker.push``)."""
+    return StreamUnpacker(streams, bits)
 
 
 def _zero_after(x: torch.Tensor, ends) -> torch.Tensor:

@@ -56,6 +56,17 @@ class ResampleStreamDesc(C.Structure):
     _fields_ = [("slot", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("count", C.c_int32), ("keep", C.c_int32), ("q0", C.c_int32)]
 
 
+class PackStreamDesc(C.Structure):
+    """l3ac_pack_stream_desc: one stream's share of one packing push: held / keep in bits, take in tokens, count in bytes
+    (include/l3ac_hip.h)."""
+    _fields_ = [("slot", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("count", C.c_int32), ("keep", C.c_int32)]
+
+
+class UnpackStreamDesc(C.Structure):
+    """l3ac_unpack_stream_desc: one stream's share of one unpacking push: held / keep in bits, take in bytes, count in tokens."""
+    _fields_ = [("slot", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("count", C.c_int32), ("keep", C.c_int32)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -128,6 +139,9 @@ SIGNATURES = {
     "l3ac_stream_emit": (C.c_int, [_P, _I32, _I64, _I32, C.POINTER(StreamDesc), _I32, _P, _I32, _I64, _I64, _P]),
     "l3ac_resample_stream_state": (_I64, [_I32, _I32]),
     "l3ac_resample_stream": (C.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _I32, _P, C.POINTER(ResampleStreamDesc), _I32, _P, _I64, _I64, _P]),
+    "l3ac_packed_bytes": (_I64, [_I64, _I32]),
+    "l3ac_pack_stream": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _I32, C.POINTER(PackStreamDesc), _I32, _P, _I64, _I64, _P]),
+    "l3ac_unpack_stream": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _I32, C.POINTER(UnpackStreamDesc), _I32, _P, _I64, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

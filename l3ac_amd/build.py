@@ -40,6 +40,7 @@ SOURCES = [
     "kernels/conv_unit_ring.hip",
     "kernels/last_block.hip",
     "kernels/bitpack.hip",
+    "kernels/bitpack_stream.hip",
     "kernels/up_fused.hip",
     "kernels/ragged.hip",
     "kernels/resample.hip",

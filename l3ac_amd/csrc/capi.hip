@@ -788,6 +788,23 @@ int l3ac_resample_stream(const float* state_in, float* state_out, int32_t stream
                                   out_rate, bank, desc, count, out, out_frames, out_stride);
 }
 
+// ---- streaming token wire format ---------------------------------------------------
+int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
+
+int l3ac_pack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const int32_t* fresh, int64_t fresh_tokens,
+                     int64_t fresh_stride, int32_t bits, const l3ac_pack_stream_desc* desc, int32_t count, uint8_t* out, int64_t out_bytes,
+                     int64_t out_stride, void* stream) {
+    return launch_pack_stream((hipStream_t)stream, state_in, state_out, streams, fresh, fresh_tokens, fresh_stride, bits, desc, count, out,
+                              out_bytes, out_stride);
+}
+
+int l3ac_unpack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const uint8_t* fresh, int64_t fresh_bytes,
+                       int64_t fresh_stride, int32_t bits, const l3ac_unpack_stream_desc* desc, int32_t count, int32_t* out, int64_t out_tokens,
+                       int64_t out_stride, void* stream) {
+    return launch_unpack_stream((hipStream_t)stream, state_in, state_out, streams, fresh, fresh_bytes, fresh_stride, bits, desc, count, out,
+                                out_tokens, out_stride);
+}
+
 int l3ac_profile_begin(void) {
     L3AC_REQUIRE(g_profiler == nullptr, "profile already active on this thread");
     g_profiler = new (std::nothrow) Profiler();

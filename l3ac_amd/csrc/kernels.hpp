@@ -239,6 +239,23 @@ int64_t resample_stream_state_floats(const ResamplePlan& p);  // K - 1 rounded u
 int launch_resample_stream(hipStream_t s, const float* state_in, float* state_out, int streams, int64_t state_stride, const float* fresh,
                            int64_t fresh_frames, int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank,
                            const l3ac_resample_stream_desc* desc, int count, float* out, int64_t out_frames, int64_t out_stride);
+// streaming token wire format (kernels/bitpack_stream.hip): one launch per push packs / unpacks every stream's
+// held bits ++ new tokens / bytes and writes its next pending bits into the other state buffer; descriptors as kernel arguments, CAP per launch
+struct PackStreamBlock {
+    static constexpr int CAP = 160;  // 3.1 KiB of the 4 KiB a launch's arguments may take
+    l3ac_pack_stream_desc desc[CAP];
+};
+struct UnpackStreamBlock {
+    static constexpr int CAP = 160;
+    l3ac_unpack_stream_desc desc[CAP];
+};
+int64_t packed_bytes(int64_t n_tok, int bits);  // HOST: ceil(n_tok * bits / 8), L3AC_EINVAL for n_tok < 0 or bits outside 1..32
+int launch_pack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const int32_t* fresh, int64_t fresh_tokens,
+                       int64_t fresh_stride, int bits, const l3ac_pack_stream_desc* desc, int count, uint8_t* out, int64_t out_bytes,
+                       int64_t out_stride);
+int launch_unpack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const uint8_t* fresh, int64_t fresh_bytes,
+                         int64_t fresh_stride, int bits, const l3ac_unpack_stream_desc* desc, int count, int32_t* out, int64_t out_tokens,
+                         int64_t out_stride);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)
