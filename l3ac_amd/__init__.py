@@ -23,7 +23,6 @@ without the built extension, raises.
 """
 from __future__ import annotations
 
-import ctypes
 import logging
 import math
 import os
@@ -35,10 +34,13 @@ import torch
 
 from . import _capi
 from . import weights as _weights
-from .chunking import ChunkData, plan as _chunk_plan
+from ._rows import (check_codec_input, contiguous_rows, decode_rows, encode_rows, int_list, refuse_grn_exact, row_stride, validated, window_args,
+                    zero_after as _zero_after)
+from .chunking import ChunkData, _chunk_cut, _chunk_groups, _chunk_merge, _group_desc, chunk_plan, plan as _chunk_plan
+from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
-from . import wire as _wire
-from .wire import StreamPacker, StreamUnpacker, frame_header, pack_advance, packed_bytes, parse_frame, unpack_advance
+from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
+                   unpack_advance, unpack_indices)
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
 
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
@@ -207,35 +209,7 @@ class L3AC:
 
     # ---- hot path -------------------------------------------------------------------------------------
     def _check_input(self, t: torch.Tensor, what: str):
-        if self.network.training:
-            raise RuntimeError("call codec.network.eval() first: the training-mode quantiser injects noise "
-                               "(reference vq/fsq.py:31,40-43), which this inference path does not implement")
-        ctx = self.network.context()
-        if not t.is_cuda or t.device != self.network.device:
-            raise RuntimeError(f"{what} is on {t.device} but the network is on {self.network.device}")
-        return ctx
-
-    @staticmethod
-    def _coop_check_before(ctx, what: str):
-        """validate=True, before the call: an EARLIER call's expired polls that nobody has been told about must not disappear into this
-        call's baseline (they would: l3ac_coop_timeout_count acknowledges what it reports).  Synchronises."""
-        earlier = ctx.coop_timeout_pending()
-        if earlier:
-            ctx.coop_timeout_count()  # delivered by the exception below: fall back, re-zero the arrival counters
-            raise _capi.L3acError(
-                f"{what}(validate=True): an EARLIER call on this context lost {earlier} arrival poll(s) of the cooperative transformer "
-                "kernel to its time limit; that call's outputs are invalid (every call since the last validated one is suspect). "
-                "Nothing was run. The context now runs the one-workgroup form (same bits): repeat those calls")
-
-    @staticmethod
-    def _raise_on_coop_timeout(ctx, what: str):
-        lost = ctx.coop_timeout_pending()  # (synchronises)
-        if lost:
-            ctx.coop_timeout_count()  # delivered here: the context falls back to the one-workgroup form, counters re-zeroed
-            raise _capi.L3acError(
-                f"{what}: the cooperative transformer kernel lost {lost} arrival poll(s) to its time limit (its six workgroups per "
-                "clip were not co-resident: another process or a CU mask on the device?); this call's outputs are invalid. The "
-                "context now runs the one-workgroup form (same bits): repeat the call")
+        return check_codec_input(self.network, None, t, what)
 
     def _rate(self, sample_rate) -> Optional[int]:
         """None when `sample_rate` is absent or the codec's own rate (the plain path runs), else the validated rate."""
@@ -258,12 +232,10 @@ class L3AC:
         ``lengths[i]`` in row i are ignored, whatever they hold; clip i's first ``ceil(lengths[i] / hop)`` tokens are bit-identical
         to ``encode_audio(audio_data[i:i+1, :lengths[i]])``, the rest are zero, and the dict gains ``"lengths"``: those token counts
         (int32, on the CPU).  With ``sample_rate`` the lengths count samples at that rate."""
-        if lengths is not None and audio_data.dim() != 2:
+        if audio_data.dim() != 2:
             raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
         lens = None if lengths is None else ragged_lengths(lengths, audio_data.shape[0], audio_data.shape[1], "lengths")
         ctx = self._check_input(audio_data, "audio_data")
-        if audio_data.dim() != 2:
-            raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
         rate = self._rate(sample_rate)
         if rate is not None and lens is not None:
             # each clip is converted as it would be alone: its zero padding, not its neighbour's samples, after its end
@@ -278,24 +250,9 @@ class L3AC:
         if t == 0 or b == 0:
             raise ValueError("empty audio")
         mc = self.network.mc
-        n_tok = math.ceil(t / mc.hop_length)
         dev = audio.device
-        q_feature = torch.empty((b, n_tok, mc.feature_dim), dtype=torch.float32, device=dev)
-        indices = torch.empty((b, n_tok), dtype=torch.int32, device=dev)
-        level_indices = torch.empty((b, n_tok, len(mc.levels)), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if validate:
-                self._coop_check_before(ctx, "encode_audio")
-            if lens is None:
-                _capi.check(ctx.lib.l3ac_encode(ctx.handle, audio.data_ptr(), b, t, audio.stride(0) if b > 1 else t,
-                                                q_feature.data_ptr(), indices.data_ptr(), level_indices.data_ptr(), stream))
-            else:
-                host = (ctypes.c_int32 * b)(*lens)
-                _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, audio.data_ptr(), b, t, audio.stride(0) if b > 1 else t, host,
-                                                       q_feature.data_ptr(), indices.data_ptr(), level_indices.data_ptr(), stream))
-            if validate:
-                self._raise_on_coop_timeout(ctx, "encode_audio")
+        with torch.cuda.device(dev), validated(ctx, "encode_audio", validate):
+            q_feature, indices, level_indices = encode_rows(ctx, audio, b, t, row_stride(audio), lens, torch.cuda.current_stream(dev).cuda_stream)
         if lens is not None:
             tok = torch.tensor([math.ceil(n / mc.hop_length) for n in lens], dtype=torch.int32)
             return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": tok}
@@ -323,37 +280,20 @@ class L3AC:
         if audio_feature is not None:
             if audio_feature.dim() != 3 or audio_feature.shape[-1] != mc.feature_dim:
                 raise ValueError(f"audio_feature must be (batch, tokens, {mc.feature_dim})")
-            feat = audio_feature.to(torch.float32).contiguous()
-            b, n_tok = feat.shape[:2]
-            f_ptr, i_ptr, keep = feat.data_ptr(), None, feat
+            rows = audio_feature.to(torch.float32).contiguous()
         else:
             if indices.dim() != 2:
                 raise ValueError("indices must be (batch, tokens)")
-            idx = indices.to(torch.int32).contiguous()
-            b, n_tok = idx.shape
-            f_ptr, i_ptr, keep = None, idx.data_ptr(), idx
+            rows = indices.to(torch.int32).contiguous()
+        b, n_tok = rows.shape[:2]
         lens = None if lengths is None else ragged_lengths(lengths, b, n_tok, "lengths (tokens)")
         if min(lens or [n_tok]) * mc.en_coder_compress_rate < 2:
             # reference behaviour: the first EnhanceBlock's InstanceNorm1d (tconv/__init__.py:36) raises on a single frame
             raise ValueError(f"Expected more than 1 spatial element when training, got input size torch.Size([{b}, 4, 1])")
-        audio = torch.empty((b, n_tok * mc.hop_length), dtype=torch.float32, device=src.device)
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            before = ctx.bad_index_count() if validate and i_ptr is not None else 0  # cumulative counter: read, never reset here
-            if validate:
-                self._coop_check_before(ctx, "decode_audio")
-            if lens is None:
-                _capi.check(ctx.lib.l3ac_decode(ctx.handle, f_ptr, i_ptr, b, n_tok, audio.data_ptr(), stream))
-            else:
-                host = (ctypes.c_int32 * b)(*lens)
-                _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, b, n_tok, host, audio.data_ptr(), stream))
-            if validate:
-                self._raise_on_coop_timeout(ctx, "decode_audio")
-            if validate and i_ptr is not None:
-                bad = ctx.bad_index_count() - before
-                if bad:
-                    raise ValueError(f"{bad} of {b * n_tok} indices lie outside [0, {mc.codebook_size}): corrupted token stream")
-        del keep
+        bad_indices = None if audio_feature is not None else lambda bad: (
+            f"{bad} of {b * n_tok} indices lie outside [0, {mc.codebook_size}): corrupted token stream")
+        with torch.cuda.device(src.device), validated(ctx, "decode_audio", validate, bad_indices):
+            audio = decode_rows(ctx, rows, audio_feature is not None, b, n_tok, lens, torch.cuda.current_stream(src.device).cuda_stream)
         if rate is None:
             return audio
         audio = resample(audio, self.config.sample_rate, rate)
@@ -425,14 +365,8 @@ class L3AC:
 
     # ---- batches of long recordings through ragged chunk calls -------------------------------
     def _long_plan(self, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int]):
-        mc = self.network.mc
-        prefix_tokens = mc.en_coder_window_size if prefix_tokens is None else int(prefix_tokens)
-        chunk_len, prefix_len = _chunk_plan(mc.hop_length, process_window, prefix_tokens)
-        if chunks_per_call is None:
-            chunks_per_call = max(1, (512 * self.config.sample_rate) // (chunk_len + prefix_len))
-        if int(chunks_per_call) < 1:
-            raise ValueError(f"chunks_per_call must be at least 1, got {chunks_per_call}")
-        return chunk_len, prefix_tokens, min(int(chunks_per_call), 65535)
+        return window_args(self.network.mc, self.config.sample_rate, process_window, None if prefix_tokens is None else int(prefix_tokens),
+                           chunks_per_call, _chunk_plan)
 
     @torch.no_grad()
     def encode_long(self, audio_data: torch.Tensor, lengths=None, process_window: int = 5 * 16000, prefix_tokens: Optional[int] = None,
@@ -450,6 +384,10 @@ class L3AC:
         encode_audio with ``lengths=`` (each recording converted as it would be alone, lengths counted at that rate).
         ``validate``: as encode_audio.  Capturable into a graph after ``context().reserve(chunks_per_call, row_samples)`` and one
         eager call: the plan and the lengths are host values fixed at capture."""
+        return self._encode_long(audio_data, lengths, process_window, prefix_tokens, sample_rate, chunks_per_call, validate)[:2]
+
+    def _encode_long(self, audio_data, lengths, process_window, prefix_tokens, sample_rate, chunks_per_call, validate):
+        """``encode_long``, and third the recordings' sample counts at the codec's rate (``compress`` puts them into its headers)."""
         if audio_data.dim() != 2:
             raise ValueError(f"audio_data must be (batch, samples), got {tuple(audio_data.shape)}")
         if audio_data.shape[0] == 0 or audio_data.shape[1] == 0:
@@ -459,17 +397,14 @@ class L3AC:
         chunk_len, prefix_tokens, per_call = self._long_plan(process_window, prefix_tokens, chunks_per_call)
         rate = self._rate(sample_rate)
         ctx = self._check_input(audio_data, "audio_data")
-        if self.network.grn_exact:
-            raise _capi.L3acError("encode_long: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
-                                  "would include their padding: use extract_unit per recording")
+        refuse_grn_exact(self.network, "encode_long", "extract_unit")
         mc = self.network.mc
         hop = mc.hop_length
         audio = audio_data.to(torch.float32)
         if rate is not None:
             audio = resample(_zero_after(audio, lens), rate, self.config.sample_rate)
             lens = [resample_length(rate, self.config.sample_rate, n) for n in lens]
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        audio = contiguous_rows(audio)
         b, t = audio.shape
         n_tok = math.ceil(t / hop)
         tok = [math.ceil(n / hop) for n in lens]
@@ -480,29 +415,19 @@ class L3AC:
         q_feature = torch.empty((b, n_tok, mc.feature_dim), dtype=torch.float32, device=dev)
         indices = torch.empty((b, n_tok), dtype=torch.int32, device=dev)
         level_indices = torch.empty((b, n_tok, len(mc.levels)), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), validated(ctx, "encode_long", validate):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            if validate:
-                self._coop_check_before(ctx, "encode_long")
             for group in _chunk_groups(cut, per_call):
-                g = len(group)
                 samples = [cut[j].frames for j in group]
                 longest = max(samples)
-                g_tok = longest // hop
-                rows = torch.empty((g, -(-longest // 4) * 4), dtype=torch.float32, device=dev)
-                q = torch.empty((g, g_tok, mc.feature_dim), dtype=torch.float32, device=dev)
-                idx = torch.empty((g, g_tok), dtype=torch.int32, device=dev)
-                li = torch.empty((g, g_tok, len(mc.levels)), dtype=torch.float32, device=dev)
+                rows = torch.empty((len(group), -(-longest // 4) * 4), dtype=torch.float32, device=dev)
                 _chunk_cut(audio, _group_desc(cut, group), rows, stream)
-                _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), (ctypes.c_int32 * g)(*samples),
-                                                       q.data_ptr(), idx.data_ptr(), li.data_ptr(), stream))
+                q, idx, li = encode_rows(ctx, rows, len(group), longest, rows.stride(0), samples, stream)
                 desc = _group_desc(merge, group)
                 _chunk_merge(q, desc, q_feature, stream)
                 _chunk_merge(idx, desc, indices, stream)
                 _chunk_merge(li, desc, level_indices, stream)
-            if validate:
-                self._raise_on_coop_timeout(ctx, "encode_long")
-        return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": torch.tensor(tok, dtype=torch.int32)}
+        return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": torch.tensor(tok, dtype=torch.int32)}, lens
 
     @torch.no_grad()
     def decode_long(self, audio_feature: torch.Tensor = None, indices: torch.Tensor = None, lengths=None, process_window: int = 5 * 16000,
@@ -542,35 +467,22 @@ class L3AC:
             # reference behaviour, as decode_audio: the first EnhanceBlock's InstanceNorm1d raises on a single frame
             raise ValueError(f"Expected more than 1 spatial element when training, got input size torch.Size([{b}, 4, 1])")
         ctx = self._check_input(src, "decode input")
-        if self.network.grn_exact:
-            raise _capi.L3acError("decode_long: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
-                                  "would include their padding: use decode_unit per recording")
+        refuse_grn_exact(self.network, "decode_long", "decode_unit")
         src = src.to(torch.float32 if audio_feature is not None else torch.int32).contiguous()
         dev = src.device
         audio = torch.empty((b, n_tok * hop), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        bad_indices = None if audio_feature is not None else lambda bad: (
+            f"{bad} index occurrences in the chunk rows (a token in an overlap counts twice) lie outside "
+            f"[0, {mc.codebook_size}): corrupted token stream")
+        with torch.cuda.device(dev), validated(ctx, "decode_long", validate, bad_indices):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            before = ctx.bad_index_count() if validate and audio_feature is None else 0
-            if validate:
-                self._coop_check_before(ctx, "decode_long")
             for group in _chunk_groups(cut, per_call):
-                g = len(group)
                 toks = [cut[j].frames for j in group]
                 longest = max(toks)
-                rows = torch.empty((g, longest) + tuple(src.shape[2:]), dtype=src.dtype, device=dev)
-                wave = torch.empty((g, longest * hop), dtype=torch.float32, device=dev)
+                rows = torch.empty((len(group), longest) + tuple(src.shape[2:]), dtype=src.dtype, device=dev)
                 _chunk_cut(src, _group_desc(cut, group), rows, stream)
-                f_ptr, i_ptr = (rows.data_ptr(), None) if audio_feature is not None else (None, rows.data_ptr())
-                _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, g, longest, (ctypes.c_int32 * g)(*toks), wave.data_ptr(),
-                                                       stream))
+                wave = decode_rows(ctx, rows, audio_feature is not None, len(group), longest, toks, stream)
                 _chunk_merge(wave, _group_desc(cut, group, hop), audio, stream)
-            if validate:
-                self._raise_on_coop_timeout(ctx, "decode_long")
-            if validate and audio_feature is None:
-                bad = ctx.bad_index_count() - before
-                if bad:
-                    raise ValueError(f"{bad} index occurrences in the chunk rows (a token in an overlap counts twice) lie outside "
-                                     f"[0, {mc.codebook_size}): corrupted token stream")
         if rate is None:
             return audio
         audio = resample(audio, self.config.sample_rate, rate)
@@ -585,13 +497,7 @@ class L3AC:
         included), the ragged ``pack_indices``, one device-to-host copy.  A frame is ``wire.frame_header``'s 24 bytes followed by the
         recording's ``packed_bytes(n_tok, bits)`` bytes; its header carries the token count and the sample count at the codec's rate
         (after conversion, when ``sample_rate`` is given)."""
-        _, info = self.encode_long(audio_data, lengths=lengths, process_window=process_window, prefix_tokens=prefix_tokens,
-                                   sample_rate=sample_rate, chunks_per_call=chunks_per_call, validate=validate)
-        samples = ragged_lengths([audio_data.shape[1]] * audio_data.shape[0] if lengths is None else lengths, audio_data.shape[0],
-                                 audio_data.shape[1], "lengths")
-        rate = self._rate(sample_rate)
-        if rate is not None:
-            samples = [resample_length(rate, self.config.sample_rate, n) for n in samples]
+        _, info, samples = self._encode_long(audio_data, lengths, process_window, prefix_tokens, sample_rate, chunks_per_call, validate)
         mc = self.network.mc
         tok = info["lengths"].tolist()
         packed, nbytes = pack_indices(info["indices"], bits_per_token(mc), lengths=tok)
@@ -681,58 +587,6 @@ def restore_gemm_split_routes(routes: dict, default: Optional[bool] = None) -> N
         net.set_gemm_split(route)
 
 
-def bits_per_token(mc) -> int:
-    """ceil(log2(codebook size)): 17 at 1kbps (117 649 codes), 18 at 3kbps (250 047)."""
-    return max(1, (mc.codebook_size - 1).bit_length())
-
-
-def pack_indices(indices: torch.Tensor, bits: int, lengths=None):
-    """int indices (B, T_tok) on the GPU -> little-endian bit stream, one row of whole 32-bit words per clip, as
-    uint8 (B, 4 * ceil(T_tok * bits / 32)).  The reference has no wire format (it keeps int32 tensors).
-    ``lengths`` (B token counts in 0..T_tok; a sequence, an array or a tensor, checked as ``ragged_lengths`` checks but a row may be
-    empty): the ragged form, ``(packed, nbytes)``: row i is the stream of its first ``lengths[i]`` tokens alone, ``nbytes[i] =
-    packed_bytes(lengths[i], bits)`` bytes (int32, CPU) followed by zeros; tokens at or after ``lengths[i]`` are ignored, whatever they
-    hold (``encode_audio(..., lengths=)`` and ``encode_long`` return such rows)."""
-    if not indices.is_cuda or indices.dim() != 2:
-        raise ValueError("indices must be a (batch, tokens) CUDA tensor")
-    if lengths is not None:
-        lens = _wire.token_lengths(lengths, indices.shape[0], indices.shape[1])
-        if not 1 <= int(bits) <= 32 or int(bits) != bits or indices.shape[0] == 0 or indices.shape[1] == 0:
-            raise ValueError(f"pack_indices: {tuple(indices.shape)} indices of {bits!r} bits")
-        return _wire.pack_ragged(indices.to(torch.int32).contiguous(), int(bits), lens)
-    idx = indices.to(torch.int32).contiguous()
-    b, n_tok = idx.shape
-    words = -(-n_tok * bits // 32)
-    out = torch.empty((b, words), dtype=torch.int32, device=idx.device)
-    lib = _capi.load_library()
-    with torch.cuda.device(idx.device):
-        _capi.check(lib.l3ac_pack_indices(idx.data_ptr(), b, n_tok, bits, out.data_ptr(), words,
-                                          torch.cuda.current_stream(idx.device).cuda_stream))
-    return out.view(torch.uint8)
-
-
-def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int, lengths=None) -> torch.Tensor:
-    """Inverse of `pack_indices`: uint8 (B, 4 * words) -> int32 (B, n_tok).  ``lengths`` (B token counts in 0..n_tok): the ragged form:
-    row i is zero after its own ``lengths[i]`` tokens, and bytes beyond its ``packed_bytes(lengths[i], bits)`` are never read."""
-    if not packed.is_cuda or packed.dim() != 2 or packed.dtype != torch.uint8 or packed.shape[1] % 4:
-        raise ValueError("packed must be a (batch, 4 * words) uint8 CUDA tensor")
-    words = packed.shape[1] // 4
-    if words * 32 < n_tok * bits:
-        raise ValueError("packed stream too short for n_tok tokens")
-    if lengths is not None:
-        lens = _wire.token_lengths(lengths, packed.shape[0], n_tok)
-        if not 1 <= int(bits) <= 32 or int(bits) != bits or packed.shape[0] == 0 or n_tok < 1:
-            raise ValueError(f"unpack_indices: {packed.shape[0]} rows of {n_tok} tokens of {bits!r} bits")
-        return _wire.unpack_ragged(packed.contiguous(), int(n_tok), int(bits), lens)
-    src = packed.contiguous().view(torch.int32)
-    out = torch.empty((packed.shape[0], n_tok), dtype=torch.int32, device=packed.device)
-    lib = _capi.load_library()
-    with torch.cuda.device(packed.device):
-        _capi.check(lib.l3ac_unpack_indices(src.data_ptr(), packed.shape[0], n_tok, bits, words, out.data_ptr(),
-                                            torch.cuda.current_stream(packed.device).cuda_stream))
-    return out
-
-
 def stream_packer(streams: int, bits: int) -> StreamPacker:
     """A session that packs the tokens of ``streams`` concurrent live streams into the bytes of the wire, push by push:
     ``packed, n_bytes = packer.push(indices, lengths=None, end=None)``.  However a stream's tokens are split over pushes, what it emits
@@ -747,139 +601,10 @@ def stream_unpacker(streams: int, bits: int) -> StreamUnpacker:
     return StreamUnpacker(streams, bits)
 
 
-def _zero_after(x: torch.Tensor, ends) -> torch.Tensor:
-    """(B, T) with row i zero from ends[i] on: each clip of a ragged batch masked to its own end (sample_rate= with lengths=)."""
-    keep = torch.arange(x.shape[1], device=x.device)[None, :] < torch.tensor(ends, device=x.device)[:, None]
-    return torch.where(keep, x, 0.0)
-
-
-def chunk_plan(frames, chunk_len: int, prefix_len: int, round_to: int = 1):
-    """The chunks of a batch of recordings of ``frames[i]`` frames each, as a ctypes array of ``_capi.ChunkDesc`` (rec, row, start,
-    frames, prefix, pad, last): ``ChunkData``'s geometry, computed by the library (l3ac_chunk_plan, host only; DESIGN.md section
-    3.8).  Rows are numbered recording after recording.  Raises ValueError on bad arguments."""
-    lib = _capi.load_library()
-    vals = [int(v) for v in frames]
-    host = (ctypes.c_int64 * max(len(vals), 1))(*vals)
-    n = lib.l3ac_chunk_plan(host, len(vals), int(chunk_len), int(prefix_len), int(round_to), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    desc = (_capi.ChunkDesc * n)()
-    if lib.l3ac_chunk_plan(host, len(vals), int(chunk_len), int(prefix_len), int(round_to), desc, n) != n:
-        raise ValueError(lib.l3ac_last_error().decode())
-    return desc
-
-
-def _chunk_groups(desc, chunks_per_call: int):
-    """A plan's chunks as the groups of at most `chunks_per_call` chunk numbers that run in one ragged call each, shortest first: a
-    ragged call computes the grid of its longest row, so every recording's short chunks (its first has no prefix, its last is what is
-    left) share calls of their own size (3.5 % of a call).  The bits do not depend on the grouping."""
-    order = sorted(range(len(desc)), key=lambda k: desc[k].frames)  # (stable)
-    return [order[k0:k0 + chunks_per_call] for k0 in range(0, len(order), chunks_per_call)]
-
-
-def _group_desc(desc, group, scale: int = 1):
-    """The descriptors of one group with rows renumbered 0 .. len(group) - 1 (the rows of that group's call)."""
-    out = (_capi.ChunkDesc * len(group))()
-    for k, j in enumerate(group):
-        d = desc[j]
-        out[k] = _capi.ChunkDesc(d.rec, k, d.start * scale, d.frames * scale, d.prefix * scale, d.pad * scale, d.last)
-    return out
-
-
-def _chunk_cut(src: torch.Tensor, desc, rows: torch.Tensor, stream) -> None:
-    """src (B, stride[, c]) -> rows (N, row_frames[, c]) on the device (l3ac_chunk_cut)."""
-    c = src.shape[2] if src.dim() == 3 else 1
-    _capi.check(_capi.load_library().l3ac_chunk_cut(src.data_ptr(), src.shape[0], src.stride(0) // c if src.shape[0] > 1 else src.shape[1],
-                                                     c, desc, len(desc), rows.data_ptr(), rows.shape[0], rows.stride(0) // c, stream))
-
-
-def _chunk_merge(rows: torch.Tensor, desc, dst: torch.Tensor, stream) -> None:
-    """rows (N, row_frames[, c]) -> dst (B, out_frames[, c]), prefixes dropped, zeros after each recording (l3ac_chunk_merge)."""
-    c = dst.shape[2] if dst.dim() == 3 else 1
-    _capi.check(_capi.load_library().l3ac_chunk_merge(rows.data_ptr(), rows.shape[0], rows.stride(0) // c, c, desc, len(desc), dst.data_ptr(),
-                                                       dst.shape[0], dst.shape[1], dst.shape[1], stream))
-
-
 def ragged_lengths(lengths, batch: int, limit: int, what: str = "lengths") -> list:
     """``lengths=`` of encode_audio / decode_audio as B Python ints in 1..limit; raises ValueError (before any device work)
     otherwise.  Accepts a sequence, a NumPy array or a tensor (a CUDA tensor is copied to the host)."""
-    if isinstance(lengths, torch.Tensor):
-        lengths = lengths.detach().cpu().reshape(-1).tolist()
-    try:
-        seq = list(lengths)
-        vals = [int(v) for v in seq]
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} must be a sequence of {batch} ints") from None
-    if any(float(v) != int(v) for v in seq):
-        raise ValueError(f"{what} must be integers")
-    if len(vals) != batch:
-        raise ValueError(f"{what}: {len(vals)} entries for a batch of {batch}")
-    bad = [v for v in vals if not 1 <= v <= limit]
-    if bad:
-        raise ValueError(f"{what}: {bad[0]} outside [1, {limit}]")
-    return vals
-
-
-def resample_length(orig_sr: int, target_sr: int, n_in: int) -> int:
-    """Samples out of ``resample`` for ``n_in`` samples in: ceil(n_in * up / down).  Raises ValueError for rates the library does
-    not support (non-positive, or a reduced max(up, down) above 1024)."""
-    n = _capi.load_library().l3ac_resample_length(int(orig_sr), int(target_sr), int(n_in))
-    if n < 0:
-        raise ValueError(_capi.load_library().l3ac_last_error().decode())
-    return int(n)
-
-
-_banks = {}  # (device, orig_sr, target_sr) -> device copy of the library's polyphase filter bank
-
-
-def _resample_bank(device: torch.device, orig_sr: int, target_sr: int) -> Optional[torch.Tensor]:
-    key = (device, orig_sr, target_sr)
-    if key in _banks:
-        return _banks[key]
-    lib = _capi.load_library()
-    n = lib.l3ac_resample_bank(orig_sr, target_sr, None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    if n > 0 and torch.cuda.is_current_stream_capturing():
-        # uploading the bank would be a host -> device copy inside the graph; the eager warm-up call before capture fills the cache
-        raise RuntimeError(f"resample {orig_sr} -> {target_sr}: this rate pair's filter bank is not on {device} yet; run the call "
-                           "once outside stream capture (the warm-up call before graph capture) to upload it")
-    bank = None
-    if n > 0:
-        host = torch.empty(n, dtype=torch.float32)
-        lib.l3ac_resample_bank(orig_sr, target_sr, host.data_ptr(), n)
-        bank = host.to(device)
-    _banks[key] = bank
-    return bank
-
-
-@torch.no_grad()
-def resample(audio: torch.Tensor, orig_sr: int, target_sr: int) -> torch.Tensor:
-    """(B, T) fp32 CUDA audio at ``orig_sr`` -> (B, resample_length(orig_sr, target_sr, T)) at ``target_sr``, on the GPU.
-    ``scipy.signal.resample_poly(audio, up, down, axis=-1)`` with its defaults (Kaiser-windowed sinc, beta 5, zero padding at
-    both ends; up / down = target_sr / orig_sr reduced), in fp32: each output is one fmaf chain in a fixed tap order, so a clip's
-    bits do not depend on the batch it is in.  Equal rates return a copy.  No CPU path: CPU tensors raise.  Each rate pair's
-    filter bank is uploaded once per device and cached; under stream capture a pair that has not run on the device yet raises."""
-    orig_sr, target_sr = int(orig_sr), int(target_sr)
-    if not isinstance(audio, torch.Tensor) or not audio.is_cuda:
-        raise RuntimeError("resample needs a CUDA tensor: l3ac_amd has no CPU path")
-    if audio.dim() != 2:
-        raise ValueError(f"audio must be (batch, samples), got {tuple(audio.shape)}")
-    b, t = audio.shape
-    if b == 0 or t == 0:
-        raise ValueError("empty audio")
-    n_out = resample_length(orig_sr, target_sr, t)  # validates the rates before any device work
-    x = audio.to(torch.float32)
-    if x.stride(-1) != 1:
-        x = x.contiguous()
-    dev = x.device
-    bank = _resample_bank(dev, orig_sr, target_sr)
-    y = torch.empty((b, n_out), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check(_capi.load_library().l3ac_resample(
-            x.data_ptr(), b, t, x.stride(0) if b > 1 else t, orig_sr, target_sr, None if bank is None else bank.data_ptr(),
-            y.data_ptr(), n_out, torch.cuda.current_stream(dev).cuda_stream))
-    return y
+    return int_list(lengths, batch, 1, limit, what, f"a batch of {batch}")
 
 
 def stream_resampler(streams: int, orig_sr: int, target_sr: int) -> StreamResampler:

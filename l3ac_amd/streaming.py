@@ -16,13 +16,15 @@ Last, streaming sample-rate conversion: its geometry (`
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _capi
+from ._rows import (check_codec_input, contiguous_rows, decode_rows, encode_rows, end_flags, int_list, refuse_grn_exact, row_stride, validated,
+                    window_args)
+from .resampling import _resample_bank
 
 
 # ---- 1. geometry -------------------------------------------------------------------------------------------------------------
@@ -172,59 +174,20 @@ def resample_advance(state: ResampleState, new_frames: int, end: bool, geo: Resa
 
 
 # ---- 2. sessions -------------------------------------------------------------------------------------------------------------
-def _check_streams(streams) -> int:
-    if isinstance(streams, bool) or int(streams) != streams or int(streams) < 1:
-        raise ValueError(f"streams must be a positive integer, got {streams!r}")
-    return int(streams)
+class _Streams:
+    """What all five sessions share: the per-stream host state and the parsing of a push's ``lengths`` / ``end``."""
+    _fresh = None  # the state of a fresh stream
 
-
-class _PushPlan(NamedTuple):
-    rows: list       # (slot, round, StreamRow), in row order of the whole push: shortest first
-    groups: list     # lists of indices into rows: one ragged call each
-    appends: list    # (slot, held, off, take)
-    after: list      # StreamState per slot
-    rounds: int
-
-
-class _Session:
-    """What StreamEncoder and StreamDecoder share: the per-stream host state, the device state buffer and the kernels that move it."""
-    _what = "stream"
-
-    def __init__(self, codec, streams: int, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int], in_tokens: bool):
-        mc = codec.network.mc
-        hop = mc.hop_length
-        _check_streams(streams)
-        if int(process_window) != process_window or int(process_window) < hop:
-            raise ValueError(f"process_window ({process_window} samples) must be at least one hop ({hop} samples)")
-        prefix_tokens = mc.en_coder_window_size if prefix_tokens is None else prefix_tokens
-        if int(prefix_tokens) != prefix_tokens or int(prefix_tokens) < 0:
-            raise ValueError(f"prefix_tokens must be a non-negative integer, got {prefix_tokens!r}")
-        self.codec = codec
+    def __init__(self, streams: int):
+        if isinstance(streams, bool) or int(streams) != streams or int(streams) < 1:
+            raise ValueError(f"streams must be a positive integer, got {streams!r}")
         self.streams = int(streams)
-        self.hop = hop
-        self.step_tokens = int(process_window) // hop
-        self.prefix_tokens = int(prefix_tokens)
-        unit = 1 if in_tokens else hop  # frames per token on the input side
-        self.round_to = unit
-        self.step = self.step_tokens * unit
-        self.lookback = self.prefix_tokens * unit
-        check_geometry(self.step, self.lookback, self.round_to)
-        if chunks_per_call is None:
-            chunks_per_call = max(1, (512 * codec.config.sample_rate) // ((self.step_tokens + self.prefix_tokens) * hop))
-        if int(chunks_per_call) < 1:
-            raise ValueError(f"chunks_per_call must be at least 1, got {chunks_per_call}")
-        self.chunks_per_call = min(int(chunks_per_call), 65535)
-        self.state_frames = round4(self.lookback + self.step)
-        self._states = [StreamState() for _ in range(self.streams)]
-        self._ctx = codec.network.context()  # raises when the network is not on a GPU
-        self._device = codec.network.device
-        self._lib = _capi.load_library()
-        self._buf, self._c = None, 0  # [streams][state_frames][c], allocated at the first push (a decoder learns c there)
+        self._states = [self._fresh] * self.streams
 
-    # ---- host side ------------------------------------------------------------------------------------------------------
     @property
-    def states(self) -> List[StreamState]:
-        """The streams' host state (a copy): look-back held, frames pending, frames seen since the stream began."""
+    def states(self) -> list:
+        """The streams' host state (a copy), one tuple of the session's state type each (``StreamState``, ``ResampleState``,
+        ``wire.PackState`` / ``UnpackState``): what the stream holds on the device and what it has seen and emitted since it began."""
         return list(self._states)
 
     def reset(self, streams=None) -> None:
@@ -235,50 +198,109 @@ class _Session:
         if bad:
             raise ValueError(f"stream {bad[0]} of {self.streams}")
         for i in which:
-            self._states[i] = StreamState()
+            self._states[i] = self._fresh
 
     def _lengths(self, lengths, n: int, what: str) -> List[int]:
-        if lengths is None:
-            return [n] * self.streams
-        if isinstance(lengths, torch.Tensor):
-            lengths = lengths.detach().cpu().reshape(-1).tolist()
-        try:
-            seq = list(lengths)
-            vals = [int(v) for v in seq]
-        except (TypeError, ValueError):
-            raise ValueError(f"{what} must be a sequence of {self.streams} ints") from None
-        if any(float(v) != int(v) for v in seq):
-            raise ValueError(f"{what} must be integers")
-        if len(vals) != self.streams:
-            raise ValueError(f"{what}: {len(vals)} entries for {self.streams} streams")
-        bad = [v for v in vals if not 0 <= v <= n]
-        if bad:
-            raise ValueError(f"{what}: {bad[0]} outside [0, {n}]")
-        return vals
+        return [n] * self.streams if lengths is None else int_list(lengths, self.streams, 0, n, what, f"{self.streams} streams")
 
     def _ends(self, end) -> List[bool]:
-        if end is None or isinstance(end, bool):
-            return [bool(end)] * self.streams
-        if isinstance(end, torch.Tensor):
-            end = end.detach().cpu().reshape(-1).tolist()
-        vals = [bool(v) for v in end]
-        if len(vals) != self.streams:
-            raise ValueError(f"end: {len(vals)} entries for {self.streams} streams")
-        return vals
+        return end_flags(end, self.streams)
 
+
+class _CarrySession(_Streams):
+    """The sessions of one launch per push (StreamResampler, wire.StreamPacker / StreamUnpacker): the carried state lives on the device of
+    the first push, in two buffers read and written alternately.  A push cannot be captured: ``_phase`` names the host value that moves."""
+    _what = "session"
+    _elements = "elements"
+    _phase = ""
+
+    def __init__(self, streams: int):
+        super().__init__(streams)
+        self._lib = _capi.load_library()
+        self._device = None
+        self._bufs = None  # allocated at the first push
+
+    def _check_device(self, t: torch.Tensor, what: str) -> None:
+        if not t.is_cuda:
+            raise RuntimeError(f"{self._what}: {what} is on {t.device}: l3ac_amd has no CPU path")
+        if self._device is not None and t.device != self._device:
+            raise RuntimeError(f"{self._what}: {what} is on {t.device} but the session's state is on {self._device}")
+        if t.shape[1] >= 2 ** 31:
+            raise ValueError(f"{self._what}: a push of {t.shape[1]} {self._elements}")
+        with torch.cuda.device(t.device):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._what}: a push cannot be captured into a graph: {self._phase} is a host value that "
+                                   "advances with every push")
+
+    def _take(self, new: torch.Tensor, what: str, dtype, lengths, lengths_what: str, end, advance, *geometry):
+        """The host half of a push of (S, n) ``new``: every check, then ``advance(state, lengths[i], end[i], *geometry)`` per stream ->
+        (new as ``dtype`` with unit-stride rows, the plan [(push, state afterwards)], the outputs per stream, their maximum)."""
+        lens = self._lengths(lengths, new.shape[1], lengths_what)
+        ends = self._ends(end)
+        self._check_device(new, what)
+        plan = [advance(st, m, e, *geometry) for st, m, e in zip(self._states, lens, ends)]
+        total = [p.count for p, _ in plan]
+        return contiguous_rows(new.to(dtype)), plan, total, max(total)
+
+    def _buffers(self, dev, shape, dtype):
+        """(read, written) pointers of the two state buffers, zeroed on ``dev`` at the first push; ``shape`` None: a session without any."""
+        if self._device is None:
+            self._device = dev
+            self._bufs = shape and [torch.zeros(shape, dtype=dtype, device=dev) for _ in range(2)]
+        return (self._bufs[0].data_ptr(), self._bufs[1].data_ptr()) if self._bufs else (None, None)
+
+    def _commit(self, plan) -> None:
+        """After the launch: what was written is what the next push reads, and every stream is in its state afterwards."""
+        if self._bufs:
+            self._bufs.reverse()
+        self._states = [after for _, after in plan]
+
+
+class _PushPlan(NamedTuple):
+    rows: list       # (slot, round, StreamRow), in row order of the whole push: shortest first
+    groups: list     # lists of indices into rows: one ragged call each
+    appends: list    # (slot, held, off, take)
+    after: list      # StreamState per slot
+    rounds: int
+
+
+def _stream_window(hop: int, process_window, prefix_tokens):
+    """``window_args``' geometry for a session: a step of at least one hop and any look-back, at, above or below it."""
+    if int(process_window) != process_window or int(process_window) < hop:
+        raise ValueError(f"process_window ({process_window} samples) must be at least one hop ({hop} samples)")
+    if int(prefix_tokens) != prefix_tokens or int(prefix_tokens) < 0:
+        raise ValueError(f"prefix_tokens must be a non-negative integer, got {prefix_tokens!r}")
+    return int(process_window) // hop * hop, int(prefix_tokens) * hop
+
+
+class _Session(_Streams):
+    """What StreamEncoder and StreamDecoder share: the per-stream host state, the device state buffer and the kernels that move it."""
+    _what = "stream"
+    _fresh = StreamState()
+
+    def __init__(self, codec, streams: int, process_window: int, prefix_tokens: Optional[int], chunks_per_call: Optional[int], in_tokens: bool):
+        super().__init__(streams)
+        hop = codec.network.mc.hop_length
+        chunk_len, self.prefix_tokens, self.chunks_per_call = window_args(codec.network.mc, codec.config.sample_rate, process_window,
+                                                                          prefix_tokens, chunks_per_call, _stream_window)
+        self.codec = codec
+        self.hop = hop
+        self.step_tokens = chunk_len // hop
+        unit = 1 if in_tokens else hop  # frames per token on the input side
+        self.round_to = unit
+        self.step = self.step_tokens * unit
+        self.lookback = self.prefix_tokens * unit
+        check_geometry(self.step, self.lookback, self.round_to)
+        self.state_frames = round4(self.lookback + self.step)
+        self._ctx = codec.network.context()  # raises when the network is not on a GPU
+        self._device = codec.network.device
+        self._lib = _capi.load_library()
+        self._buf, self._c = None, 0  # [streams][state_frames][c], allocated at the first push (a decoder learns c there)
+
+    # ---- host side ------------------------------------------------------------------------------------------------------
     def _check_network(self, t, what: str) -> None:
-        net = self.codec.network
-        if net.training:
-            raise RuntimeError("call codec.network.eval() first: the training-mode quantiser injects noise "
-                               "(reference vq/fsq.py:31,40-43), which this inference path does not implement")
-        if net._ctx is not self._ctx or self._ctx.handle is None:
-            raise RuntimeError(f"{self._what}: the network was moved to another device or reloaded after this session was created; its "
-                               "state belongs to the context it was created on: create a new session")
-        if not t.is_cuda or t.device != self._device:
-            raise RuntimeError(f"{what} is on {t.device} but the network is on {self._device}")
-        if net.grn_exact:
-            raise _capi.L3acError(f"{self._what}: this network evaluates the GRN normaliser per clip (grn_exact = True); ragged calls "
-                                  f"would include their padding: use {self._offline} per recording")
+        check_codec_input(self.codec.network, self._ctx, t, what, self._what)
+        refuse_grn_exact(self.codec.network, self._what, self._offline)
 
     def _plan(self, lens: List[int], ends: List[bool]) -> _PushPlan:
         per, after, appends = [], [], []
@@ -424,42 +446,26 @@ class StreamEncoder(_Session):
         ends = self._ends(end)
         self._check_network(audio, "audio")
         self._check_capture(lens, ends)
-        codec, mc, hop, dev = self.codec, self.codec.network.mc, self.hop, self._device
+        mc, hop, dev = self.codec.network.mc, self.hop, self._device
         plan = self._plan(lens, ends)
-        new = audio.to(torch.float32)
-        if new.stride(-1) != 1 and new.numel():
-            new = new.contiguous()
+        new = contiguous_rows(audio.to(torch.float32))
         descs, total, width = self._emit_plan(plan, 1, hop)
         q_feature = torch.empty((self.streams, width, mc.feature_dim), dtype=torch.float32, device=dev)
         indices = torch.empty((self.streams, width), dtype=torch.int32, device=dev)
         level_indices = torch.empty((self.streams, width, len(mc.levels)), dtype=torch.float32, device=dev)
-        ctx = self._ctx
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), validated(self._ctx, "stream_encoder.push", validate):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            if validate:
-                codec._coop_check_before(ctx, "stream_encoder.push")
             self._state_buffer(new, 1)
-            rows_t = self._move(plan, new, new.stride(0) if self.streams > 1 and new.shape[1] else max(new.shape[1], 1), 1, stream)
+            rows_t = self._move(plan, new, row_stride(new), 1, stream)
             self._states = plan.after
             for group, rows, desc in zip(plan.groups, rows_t, descs):
-                g = len(group)
                 samples = [plan.rows[k][2].frames for k in group]
                 longest = max(samples)
-                g_tok = longest // hop
-                q = torch.empty((g, g_tok, mc.feature_dim), dtype=torch.float32, device=dev)
-                idx = torch.empty((g, g_tok), dtype=torch.int32, device=dev)
-                li = torch.empty((g, g_tok, len(mc.levels)), dtype=torch.float32, device=dev)
-                if min(samples) == longest:  # rows of one length (every steady push): the plain call, the same bits
-                    _capi.check(ctx.lib.l3ac_encode(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), q.data_ptr(), idx.data_ptr(),
-                                                    li.data_ptr(), stream))
-                else:
-                    _capi.check(ctx.lib.l3ac_encode_ragged(ctx.handle, rows.data_ptr(), g, longest, rows.stride(0), (ctypes.c_int32 * g)(*samples),
-                                                           q.data_ptr(), idx.data_ptr(), li.data_ptr(), stream))
+                # rows of one length (every steady push): the plain call, the same bits
+                q, idx, li = encode_rows(self._ctx, rows, len(group), longest, rows.stride(0), None if min(samples) == longest else samples, stream)
                 self._emit(q, desc, q_feature, stream)
                 self._emit(idx, desc, indices, stream)
                 self._emit(li, desc, level_indices, stream)
-            if validate:
-                codec._raise_on_coop_timeout(ctx, "stream_encoder.push")
         return q_feature, {"indices": indices, "level_indices": level_indices, "lengths": torch.tensor(total, dtype=torch.int32)}
 
 
@@ -515,38 +521,25 @@ class StreamDecoder(_Session):
             new = new.contiguous()
         descs, total, width = self._emit_plan(plan, hop, 1)
         wave = torch.empty((self.streams, width), dtype=torch.float32, device=dev)
-        ctx = self._ctx
-        with torch.cuda.device(dev):
+        bad_indices = None if audio_feature is not None else lambda bad: (
+            f"{bad} index occurrences in the chunk rows (a token in a look-back counts each time it is decoded) "
+            f"lie outside [0, {mc.codebook_size}): corrupted token stream")
+        with torch.cuda.device(dev), validated(self._ctx, "stream_decoder.push", validate, bad_indices):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            before = ctx.bad_index_count() if validate and audio_feature is None else 0
-            if validate:
-                self.codec._coop_check_before(ctx, "stream_decoder.push")
             self._state_buffer(new, c)
             rows_t = self._move(plan, new, max(new.shape[1], 1), c, stream)
             self._states = plan.after
             for group, rows, desc in zip(plan.groups, rows_t, descs):
-                g = len(group)
                 toks = [plan.rows[k][2].frames for k in group]
                 longest = max(toks)
-                out = torch.empty((g, longest * hop), dtype=torch.float32, device=dev)
-                f_ptr, i_ptr = (rows.data_ptr(), None) if audio_feature is not None else (None, rows.data_ptr())
-                if min(toks) == longest:  # rows of one length: the plain call, the same bits
-                    _capi.check(ctx.lib.l3ac_decode(ctx.handle, f_ptr, i_ptr, g, longest, out.data_ptr(), stream))
-                else:
-                    _capi.check(ctx.lib.l3ac_decode_ragged(ctx.handle, f_ptr, i_ptr, g, longest, (ctypes.c_int32 * g)(*toks), out.data_ptr(), stream))
+                # rows of one length: the plain call, the same bits
+                out = decode_rows(self._ctx, rows, audio_feature is not None, len(group), longest, None if min(toks) == longest else toks, stream)
                 self._emit(out, desc, wave, stream)
-            if validate:
-                self.codec._raise_on_coop_timeout(ctx, "stream_decoder.push")
-            if validate and audio_feature is None:
-                bad = ctx.bad_index_count() - before
-                if bad:
-                    raise ValueError(f"{bad} index occurrences in the chunk rows (a token in a look-back counts each time it is decoded) "
-                                     f"lie outside [0, {mc.codebook_size}): corrupted token stream")
         return wave, torch.tensor([n // hop for n in total], dtype=torch.int32)
 
 
 # ---- 3. streaming sample-rate conversion: the session -------------------------------------------------------------
-class StreamResampler:
+class StreamResampler(_CarrySession):
     """``l3ac_amd.stream_resampler(streams, orig_sr, target_sr)``: S concurrent live streams converted from ``orig_sr`` to ``target_sr``
     packet by packet, with ``resample``'s bits; see ``push``.  Needs no codec and no context, as ``resample`` needs none.  In front of a
     ``stream_encoder``, or behind a ``stream_decoder``, it makes a live stream at another rate give ``encode_long(..., sample_rate=)``'s /
@@ -561,12 +554,16 @@ class StreamResampler:
         out, n_out = rs_out.push(wave, lengths=n_tok * hop, end=finished)  # decode_long(..., sample_rate=44100)'s bits
     """
 
+    _what = "stream_resampler"
+    _fresh = ResampleState()
+    _elements = "samples"
+    _phase = "the position of every stream in the filter's phase cycle"
+
     def __init__(self, streams: int, orig_sr: int, target_sr: int):
-        self.streams = _check_streams(streams)
+        super().__init__(streams)
         if isinstance(orig_sr, bool) or isinstance(target_sr, bool) or int(orig_sr) != orig_sr or int(target_sr) != target_sr:
             raise ValueError(f"rates must be integers, got {orig_sr!r} -> {target_sr!r}")
         self.orig_sr, self.target_sr = int(orig_sr), int(target_sr)
-        self._lib = _capi.load_library()
         if not (0 < self.orig_sr < 2 ** 31 and 0 < self.target_sr < 2 ** 31):
             raise ValueError(f"resample: rates must be positive 32-bit integers (got {self.orig_sr} -> {self.target_sr})")
         state = self._lib.l3ac_resample_stream_state(self.orig_sr, self.target_sr)
@@ -575,34 +572,13 @@ class StreamResampler:
         self.geometry = resample_geometry(self.orig_sr, self.target_sr)
         self.state_frames = int(state)
         assert self.state_frames == round4(self.geometry.K - 1)
-        self._states = [ResampleState() for _ in range(self.streams)]
-        self._device = None
-        self._bufs = None  # two [streams][state_frames] buffers, read and written alternately: allocated at the first push
         self._bank = None
-
-    _lengths = _Session._lengths
-    _ends = _Session._ends
-
-    @property
-    def states(self) -> List[ResampleState]:
-        """The streams' host state (a copy): inputs held on the device, inputs seen and outputs emitted since the stream began."""
-        return list(self._states)
 
     @property
     def delay(self) -> float:
         """How far the output lags the input, in input samples: half_len / up (0 at equal rates).  ``end`` flushes it."""
         geo = self.geometry
         return 0.0 if geo.up == geo.down else geo.half_len / geo.up
-
-    def reset(self, streams=None) -> None:
-        """Make the given streams (an index, a sequence of them; absent: all) fresh: what they hold is dropped, nothing is emitted."""
-        which = range(self.streams) if streams is None else [streams] if isinstance(streams, int) else list(streams)
-        which = [int(i) for i in which]
-        bad = [i for i in which if not 0 <= i < self.streams]
-        if bad:
-            raise ValueError(f"stream {bad[0]} of {self.streams}")
-        for i in which:
-            self._states[i] = ResampleState()
 
     @torch.no_grad()
     def push(self, audio, lengths=None, end=None):
@@ -623,45 +599,20 @@ class StreamResampler:
         a captured push would replay one position for ever."""
         if not isinstance(audio, torch.Tensor) or audio.dim() != 2 or audio.shape[0] != self.streams:
             raise ValueError(f"audio must be a ({self.streams}, samples) tensor, got {tuple(getattr(audio, 'shape', ()))}")
-        n = audio.shape[1]
-        lens = self._lengths(lengths, n, "lengths")
-        ends = self._ends(end)
-        if not audio.is_cuda:
-            raise RuntimeError(f"stream_resampler: audio is on {audio.device}: l3ac_amd has no CPU path")
-        if self._device is not None and audio.device != self._device:
-            raise RuntimeError(f"stream_resampler: audio is on {audio.device} but the session's state is on {self._device}")
-        if n >= 2 ** 31:
-            raise ValueError(f"stream_resampler: a push of {n} samples")
-        dev = audio.device
-        with torch.cuda.device(dev):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("stream_resampler: a push cannot be captured into a graph: the position of every stream in the filter's "
-                                   "phase cycle is a host value that advances with every push")
-        from . import _resample_bank
-        geo = self.geometry
-        plan = [resample_advance(st, m, e, geo) for st, m, e in zip(self._states, lens, ends)]
-        total = [p.count for p, _ in plan]
-        width = max(total)
-        new = audio.to(torch.float32)
-        if new.stride(-1) != 1 and new.numel():
-            new = new.contiguous()
+        new, plan, total, width = self._take(audio, "audio", torch.float32, lengths, "lengths", end, resample_advance, self.geometry)
+        dev, n = new.device, new.shape[1]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            copy = geo.up == geo.down
             if self._device is None:
-                bank = _resample_bank(dev, self.orig_sr, self.target_sr)
-                bufs = None if copy else [torch.zeros((self.streams, self.state_frames), dtype=torch.float32, device=dev) for _ in range(2)]
-                self._device, self._bank, self._bufs = dev, bank, bufs
+                self._bank = _resample_bank(dev, self.orig_sr, self.target_sr)
+            # equal rates: a copy, with no state to carry
+            src, dst = self._buffers(dev, None if self.geometry.up == self.geometry.down else (self.streams, self.state_frames), torch.float32)
             y = torch.empty((self.streams, width), dtype=torch.float32, device=dev)
             desc = (_capi.ResampleStreamDesc * self.streams)(*[_capi.ResampleStreamDesc(i, p.held, p.take, p.count, p.keep, p.q0)
                                                                 for i, (p, _) in enumerate(plan)])
-            src, dst = (None, None) if copy else (self._bufs[0].data_ptr(), self._bufs[1].data_ptr())
             _capi.check(self._lib.l3ac_resample_stream(
-                src, dst, self.streams, self.state_frames, new.data_ptr() if new.numel() else None, n,
-                new.stride(0) if self.streams > 1 and n else max(n, 1), self.orig_sr, self.target_sr,
+                src, dst, self.streams, self.state_frames, new.data_ptr() if n else None, n, row_stride(new), self.orig_sr, self.target_sr,
                 None if self._bank is None else self._bank.data_ptr(), desc, self.streams, y.data_ptr() if width else None, width,
                 max(width, 1), stream))
-            if not copy:
-                self._bufs.reverse()
-            self._states = [after for _, after in plan]
+            self._commit(plan)
         return y, torch.tensor(total, dtype=torch.int32)

@@ -18,7 +18,8 @@ from typing import List, NamedTuple, Tuple
 import torch
 
 from . import _capi
-from .streaming import _Session, _check_streams, round4
+from ._rows import int_list, row_stride
+from .streaming import _CarrySession, round4
 
 
 # ---- 1. geometry -----------------------------------------------------------------------------------------------------------------------
@@ -96,54 +97,15 @@ def unpack_advance(state: UnpackState, new_bytes: int, end: bool, bits: int) -> 
 
 
 # ---- 2. sessions -----------------------------------------------------------------------------------------------------------------------
-class _WireSession:
-    """What StreamPacker and StreamUnpacker share: the per-stream host state and the two device state buffers."""
+class _WireSession(_CarrySession):
+    """What StreamPacker and StreamUnpacker share: ``bits``, and one uint32 of pending bits per stream as the carried state."""
     _what = "wire session"
-    _fresh = None  # the state of a fresh stream
+    _phase = "the bit phase of every stream"
 
     def __init__(self, streams: int, bits: int):
-        self.streams = _check_streams(streams)
+        super().__init__(streams)
         # 8..32: fewer than 8 padding bits can then never hold a token, so a stream's end is unambiguous
         self.bits = _check_bits(bits, lo=8)
-        self._lib = _capi.load_library()
-        self._states = [self._fresh] * self.streams
-        self._device = None
-        self._bufs = None  # two [streams] uint32 buffers, read and written alternately: allocated at the first push
-
-    _lengths = _Session._lengths
-    _ends = _Session._ends
-
-    @property
-    def states(self) -> list:
-        """The streams' host state (a copy): bits pending on the device, elements seen and emitted since the stream began."""
-        return list(self._states)
-
-    def reset(self, streams=None) -> None:
-        """Make the given streams (an index, a sequence of them; absent: all) fresh: what they hold is dropped, nothing is emitted."""
-        which = range(self.streams) if streams is None else [streams] if isinstance(streams, int) else list(streams)
-        which = [int(i) for i in which]
-        bad = [i for i in which if not 0 <= i < self.streams]
-        if bad:
-            raise ValueError(f"stream {bad[0]} of {self.streams}")
-        for i in which:
-            self._states[i] = self._fresh
-
-    def _check_device(self, t: torch.Tensor, what: str):
-        if not t.is_cuda:
-            raise RuntimeError(f"{self._what}: {what} is on {t.device}: l3ac_amd has no CPU path")
-        if self._device is not None and t.device != self._device:
-            raise RuntimeError(f"{self._what}: {what} is on {t.device} but the session's state is on {self._device}")
-        if t.shape[1] >= 2 ** 31:
-            raise ValueError(f"{self._what}: a push of {t.shape[1]} elements")
-        with torch.cuda.device(t.device):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"{self._what}: a push cannot be captured into a graph: the bit phase of every stream is a host value that "
-                                   "advances with every push")
-
-    def _buffers(self, dev):
-        if self._device is None:
-            self._device, self._bufs = dev, [torch.zeros((self.streams,), dtype=torch.int32, device=dev) for _ in range(2)]
-        return self._bufs[0].data_ptr(), self._bufs[1].data_ptr()
 
 
 class StreamPacker(_WireSession):
@@ -180,27 +142,16 @@ class StreamPacker(_WireSession):
                 or indices.dtype.is_complex or indices.dtype == torch.bool:
             raise ValueError(f"indices must be an integer ({self.streams}, tokens) tensor, got {getattr(indices, 'dtype', type(indices))} "
                              f"{tuple(getattr(indices, 'shape', ()))}")
-        n = indices.shape[1]
-        lens = self._lengths(lengths, n, "lengths")
-        ends = self._ends(end)
-        self._check_device(indices, "indices")
-        dev = indices.device
-        plan = [pack_advance(st, m, e, self.bits) for st, m, e in zip(self._states, lens, ends)]
-        total = [p.count for p, _ in plan]
-        width = max(total)
-        new = indices.to(torch.int32)
-        if new.stride(-1) != 1 and new.numel():
-            new = new.contiguous()
+        new, plan, total, width = self._take(indices, "indices", torch.int32, lengths, "lengths", end, pack_advance, self.bits)
+        dev, n = new.device, new.shape[1]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            src, dst = self._buffers(dev)
+            src, dst = self._buffers(dev, (self.streams,), torch.int32)
             out = torch.empty((self.streams, round4(width)), dtype=torch.uint8, device=dev)
             desc = (_capi.PackStreamDesc * self.streams)(*[_capi.PackStreamDesc(i, *p) for i, (p, _) in enumerate(plan)])
-            _capi.check(self._lib.l3ac_pack_stream(
-                src, dst, self.streams, new.data_ptr() if new.numel() else None, n, new.stride(0) if self.streams > 1 and n else max(n, 1),
-                self.bits, desc, self.streams, out.data_ptr() if width else None, width, out.shape[1], stream))
-            self._bufs.reverse()
-            self._states = [after for _, after in plan]
+            _capi.check(self._lib.l3ac_pack_stream(src, dst, self.streams, new.data_ptr() if n else None, n, row_stride(new), self.bits, desc,
+                                                   self.streams, out.data_ptr() if width else None, width, out.shape[1], stream))
+            self._commit(plan)
         return out[:, :width], torch.tensor(total, dtype=torch.int32)
 
 
@@ -227,71 +178,81 @@ class StreamUnpacker(_WireSession):
         if not isinstance(packed, torch.Tensor) or packed.dim() != 2 or packed.shape[0] != self.streams or packed.dtype != torch.uint8:
             raise ValueError(f"packed must be a uint8 ({self.streams}, bytes) tensor, got {getattr(packed, 'dtype', type(packed))} "
                              f"{tuple(getattr(packed, 'shape', ()))}")
-        n = packed.shape[1]
-        lens = self._lengths(lengths, n, "lengths (bytes)")
-        ends = self._ends(end)
-        self._check_device(packed, "packed")
-        dev = packed.device
-        plan = [unpack_advance(st, m, e, self.bits) for st, m, e in zip(self._states, lens, ends)]
-        total = [p.count for p, _ in plan]
-        width = max(total)
-        new = packed if packed.stride(-1) == 1 or not packed.numel() else packed.contiguous()
+        new, plan, total, width = self._take(packed, "packed", torch.uint8, lengths, "lengths (bytes)", end, unpack_advance, self.bits)
+        dev, n = new.device, new.shape[1]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            src, dst = self._buffers(dev)
+            src, dst = self._buffers(dev, (self.streams,), torch.int32)
             out = torch.empty((self.streams, width), dtype=torch.int32, device=dev)
             desc = (_capi.UnpackStreamDesc * self.streams)(*[_capi.UnpackStreamDesc(i, *p) for i, (p, _) in enumerate(plan)])
-            _capi.check(self._lib.l3ac_unpack_stream(
-                src, dst, self.streams, new.data_ptr() if new.numel() else None, n, new.stride(0) if self.streams > 1 and n else max(n, 1),
-                self.bits, desc, self.streams, out.data_ptr() if width else None, width, max(width, 1), stream))
-            self._bufs.reverse()
-            self._states = [after for _, after in plan]
+            _capi.check(self._lib.l3ac_unpack_stream(src, dst, self.streams, new.data_ptr() if n else None, n, row_stride(new), self.bits, desc,
+                                                     self.streams, out.data_ptr() if width else None, width, max(width, 1), stream))
+            self._commit(plan)
         return out, torch.tensor(total, dtype=torch.int32)
 
 
-# ---- 3. the ragged forms of pack_indices / unpack_indices ------------------------------------------------------------------------------
+# ---- 3. pack_indices / unpack_indices, plain and ragged --------------------------------------------------------------------------------
 def token_lengths(lengths, batch: int, limit: int, what: str = "lengths") -> List[int]:
     """``lengths=`` of pack_indices / unpack_indices as B Python ints in 0..limit: ``ragged_lengths``' checks, but a row may be empty."""
-    if isinstance(lengths, torch.Tensor):
-        lengths = lengths.detach().cpu().reshape(-1).tolist()
-    try:
-        seq = list(lengths)
-        vals = [int(v) for v in seq]
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} must be a sequence of {batch} ints") from None
-    if any(float(v) != int(v) for v in seq):
-        raise ValueError(f"{what} must be integers")
-    if len(vals) != batch:
-        raise ValueError(f"{what}: {len(vals)} entries for a batch of {batch}")
-    bad = [v for v in vals if not 0 <= v <= limit]
-    if bad:
-        raise ValueError(f"{what}: {bad[0]} outside [0, {limit}]")
-    return vals
+    return int_list(lengths, batch, 0, limit, what, f"a batch of {batch}")
 
 
-def pack_ragged(idx: torch.Tensor, bits: int, lens: List[int]):
-    """int32 (B, T_tok) contiguous CUDA, row i holding ``lens[i]`` tokens -> (uint8 (B, 4 * ceil(T_tok * bits / 32)), bytes per row int32
-    CPU): every row a stream of its own, ended, with no held state (one l3ac_pack_stream call)."""
+def pack_indices(indices: torch.Tensor, bits: int, lengths=None):
+    """int indices (B, T_tok) on the GPU -> little-endian bit stream, one row of whole 32-bit words per clip, as
+    uint8 (B, 4 * ceil(T_tok * bits / 32)).  The reference has no wire format (it keeps int32 tensors).
+    ``lengths`` (B token counts in 0..T_tok; a sequence, an array or a tensor, checked as ``ragged_lengths`` checks but a row may be
+    empty): the ragged form, ``(packed, nbytes)``: row i is the stream of its first ``lengths[i]`` tokens alone, ``nbytes[i] =
+    packed_bytes(lengths[i], bits)`` bytes (int32, CPU) followed by zeros; tokens at or after ``lengths[i]`` are ignored, whatever they
+    hold (``encode_audio(..., lengths=)`` and ``encode_long`` return such rows)."""
+    if not indices.is_cuda or indices.dim() != 2:
+        raise ValueError("indices must be a (batch, tokens) CUDA tensor")
+    if lengths is not None:
+        lens = token_lengths(lengths, indices.shape[0], indices.shape[1])
+        if not 1 <= int(bits) <= 32 or int(bits) != bits or indices.shape[0] == 0 or indices.shape[1] == 0:
+            raise ValueError(f"pack_indices: {tuple(indices.shape)} indices of {bits!r} bits")
+        bits = int(bits)
+    idx = indices.to(torch.int32).contiguous()
     b, n_tok = idx.shape
-    row_bytes = 4 * (-(-n_tok * bits // 32))
-    nbytes = [packed_bytes(n, bits) for n in lens]
-    out = torch.empty((b, row_bytes), dtype=torch.uint8, device=idx.device)
-    desc = (_capi.PackStreamDesc * b)(*[_capi.PackStreamDesc(i, 0, n, k, 0) for i, (n, k) in enumerate(zip(lens, nbytes))])
+    words = -(-n_tok * bits // 32)
+    lib = _capi.load_library()
     with torch.cuda.device(idx.device):
-        _capi.check(_capi.load_library().l3ac_pack_stream(None, None, b, idx.data_ptr(), n_tok, n_tok, bits, desc, b, out.data_ptr(), row_bytes,
-                                                          row_bytes, torch.cuda.current_stream(idx.device).cuda_stream))
+        stream = torch.cuda.current_stream(idx.device).cuda_stream
+        if lengths is None:
+            out = torch.empty((b, words), dtype=torch.int32, device=idx.device)
+            _capi.check(lib.l3ac_pack_indices(idx.data_ptr(), b, n_tok, bits, out.data_ptr(), words, stream))
+            return out.view(torch.uint8)
+        # every row a stream of its own, ended, with no held state: one l3ac_pack_stream call
+        nbytes = [packed_bytes(n, bits) for n in lens]
+        out = torch.empty((b, 4 * words), dtype=torch.uint8, device=idx.device)
+        desc = (_capi.PackStreamDesc * b)(*[_capi.PackStreamDesc(i, 0, n, k, 0) for i, (n, k) in enumerate(zip(lens, nbytes))])
+        _capi.check(lib.l3ac_pack_stream(None, None, b, idx.data_ptr(), n_tok, n_tok, bits, desc, b, out.data_ptr(), 4 * words, 4 * words, stream))
     return out, torch.tensor(nbytes, dtype=torch.int32)
 
 
-def unpack_ragged(packed: torch.Tensor, n_tok: int, bits: int, lens: List[int]) -> torch.Tensor:
-    """uint8 (B, row_bytes) contiguous CUDA, row i holding the ``packed_bytes(lens[i], bits)`` bytes of ``lens[i]`` tokens -> int32
-    (B, n_tok), zero after each row's own tokens (one l3ac_unpack_stream call; bytes after a row's own are never read)."""
-    b, row_bytes = packed.shape
-    out = torch.empty((b, n_tok), dtype=torch.int32, device=packed.device)
-    desc = (_capi.UnpackStreamDesc * b)(*[_capi.UnpackStreamDesc(i, 0, packed_bytes(n, bits), n, 0) for i, n in enumerate(lens)])
-    with torch.cuda.device(packed.device):
-        _capi.check(_capi.load_library().l3ac_unpack_stream(None, None, b, packed.data_ptr(), row_bytes, row_bytes, bits, desc, b, out.data_ptr(),
-                                                            n_tok, n_tok, torch.cuda.current_stream(packed.device).cuda_stream))
+def unpack_indices(packed: torch.Tensor, n_tok: int, bits: int, lengths=None) -> torch.Tensor:
+    """Inverse of `pack_indices`: uint8 (B, 4 * words) -> int32 (B, n_tok).  ``lengths`` (B token counts in 0..n_tok): the ragged form:
+    row i is zero after its own ``lengths[i]`` tokens, and bytes beyond its ``packed_bytes(lengths[i], bits)`` are never read."""
+    if not packed.is_cuda or packed.dim() != 2 or packed.dtype != torch.uint8 or packed.shape[1] % 4:
+        raise ValueError("packed must be a (batch, 4 * words) uint8 CUDA tensor")
+    words = packed.shape[1] // 4
+    if words * 32 < n_tok * bits:
+        raise ValueError("packed stream too short for n_tok tokens")
+    if lengths is not None:
+        lens = token_lengths(lengths, packed.shape[0], n_tok)
+        if not 1 <= int(bits) <= 32 or int(bits) != bits or packed.shape[0] == 0 or n_tok < 1:
+            raise ValueError(f"unpack_indices: {packed.shape[0]} rows of {n_tok} tokens of {bits!r} bits")
+        n_tok, bits = int(n_tok), int(bits)
+    src = packed.contiguous()
+    b, row_bytes = src.shape
+    out = torch.empty((b, n_tok), dtype=torch.int32, device=src.device)
+    lib = _capi.load_library()
+    with torch.cuda.device(src.device):
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        if lengths is None:
+            _capi.check(lib.l3ac_unpack_indices(src.view(torch.int32).data_ptr(), b, n_tok, bits, words, out.data_ptr(), stream))
+        else:  # every row a stream of its own, ended, with no held state: one l3ac_unpack_stream call
+            desc = (_capi.UnpackStreamDesc * b)(*[_capi.UnpackStreamDesc(i, 0, packed_bytes(n, bits), n, 0) for i, n in enumerate(lens)])
+            _capi.check(lib.l3ac_unpack_stream(None, None, b, src.data_ptr(), row_bytes, row_bytes, bits, desc, b, out.data_ptr(), n_tok, n_tok, stream))
     return out
 
 
@@ -310,14 +271,15 @@ class Frame(NamedTuple):
     payload: bytes
 
 
-def _mc_bits(mc) -> int:
-    return max(1, (mc.codebook_size - 1).bit_length())  # bits_per_token
+def bits_per_token(mc) -> int:
+    """ceil(log2(codebook size)): 17 at 1kbps (117 649 codes), 18 at 3kbps (250 047)."""
+    return max(1, (mc.codebook_size - 1).bit_length())
 
 
 def frame_header(mc, sample_rate: int, n_tok: int, n_samples: int) -> bytes:
     """The 24-byte little-endian header of one recording's frame: ``b"L3AC"``, u8 format version (1), u8 bits per token, u16 hop,
     u32 codebook size, u32 codec sample rate, u32 token count, u32 sample count at the codec's rate.  ``mc``: the codec's ModelConfig."""
-    return _HEADER.pack(FRAME_MAGIC, FRAME_VERSION, _mc_bits(mc), mc.hop_length, mc.codebook_size, int(sample_rate), int(n_tok), int(n_samples))
+    return _HEADER.pack(FRAME_MAGIC, FRAME_VERSION, bits_per_token(mc), mc.hop_length, mc.codebook_size, int(sample_rate), int(n_tok), int(n_samples))
 
 
 def parse_frame(blob, mc, sample_rate: int) -> Frame:
@@ -334,8 +296,8 @@ def parse_frame(blob, mc, sample_rate: int) -> Frame:
         raise ValueError(f"frame: bad magic {magic!r}, not {FRAME_MAGIC!r}")
     if version != FRAME_VERSION:
         raise ValueError(f"frame: unknown format version {version} (this package reads version {FRAME_VERSION})")
-    if bits != _mc_bits(mc):
-        raise ValueError(f"frame: {bits} bits per token, but this codec's tokens have {_mc_bits(mc)} bits")
+    if bits != bits_per_token(mc):
+        raise ValueError(f"frame: {bits} bits per token, but this codec's tokens have {bits_per_token(mc)} bits")
     if hop != mc.hop_length:
         raise ValueError(f"frame: a hop of {hop} samples, but this codec's hop is {mc.hop_length}")
     if codebook != mc.codebook_size:
