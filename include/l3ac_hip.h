@@ -359,6 +359,64 @@ int l3ac_resample_stream(const float* state_in, float* state_out, int32_t stream
                          int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
                          int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream);
 
+/* ---- quality metrics: STFT, log-mel, log-mel distance, MSE / SNR / SI-SDR ------------------------------
+ * No reference counterpart: the reference's demo ends with ((sample_audio - generated_audio) ** 2).mean() on the host.
+ * Spec (fp64): a clip of n >= 1 samples has F(n) = 1 + n / hop frames; frame f covers samples [f hop - n_fft/2, f hop + n_fft/2), zeros
+ * outside [0, n); w[j] = 0.5 - 0.5 cos(2 pi j / n_fft) (periodic Hann); X[f][k] = sum_j w[j] x_f[j] exp(-2 pi i j k / n_fft), k = 0 .. n_fft/2:
+ * torch.stft(x, n_fft, hop, n_fft, hann_window(n_fft), center=True, pad_mode="constant", onesided=True).  Mel weights: HTK scale
+ * mel(f) = 2595 log10(1 + f / 700), no normalisation, n_mels + 2 points p equally spaced in mel from 0 to sample_rate / 2, triangles on the
+ * bin frequencies f_k = k sample_rate / n_fft: W[m][k] = max(0, min((f_k - p_m) / (p_m+1 - p_m), (p_m+2 - f_k) / (p_m+2 - p_m+1))).
+ * Log-mel: L[f][m] = log10(max(sum_k W[m][k] (re^2 + im^2), 1e-10)).  Distance of a pair at one scale: the mean of |L_ref - L_est| over
+ * the clip's F(n) n_mels cells.  Time domain, per clip over its own n samples, in fp64: mse = sum (r - e)^2 / n,
+ * snr_db = 10 log10(sum r^2 / sum (r - e)^2), si_sdr_db = 10 log10(a^2 sum (r - mu_r)^2 / sum ((e - mu_e) - a (r - mu_r))^2) with
+ * a = cov(r, e) / var(r) (Le Roux et al., zero-mean form); a zero denominator gives +inf and 0 / 0 gives nan, as IEEE division does.
+ * Supported: n_fft a multiple of 16 in 16..2048, hop a multiple of 4 in 4..n_fft, n_mels in 1..256, sample_rate > 0, batch <= 65535;
+ * anything else returns L3AC_EINVAL (or a negative count) before any device work.  Context-free, like l3ac_resample.
+ *   l3ac_stft_frames:       HOST only: F(samples) = 1 + samples / hop; < 0 for samples < 1 or hop < 1.
+ *   l3ac_stft_basis:        HOST only: the window-folded DFT basis, (n_fft + 2) * n_fft floats as [n_fft + 2][n_fft]: row 2k holds
+ *                           w[j] cos(2 pi (j k mod n_fft) / n_fft), row 2k + 1 holds -w[j] sin(...), designed in fp64 with the phase reduced in
+ *                           integers, each entry rounded once to fp32.  Returns the length; fills `basis` (host memory) when it is non-null
+ *                           and cap >= that length.  The caller copies it to the device once per n_fft (16-byte aligned there).
+ *   l3ac_mel_weights:       HOST only: W as [n_mels][n_fft/2 + 1] floats, designed in fp64, each entry rounded once to fp32; same protocol.
+ *                           The two fp32 tables are part of the spec: the bit guarantees below are stated on them.
+ *   l3ac_mel_scratch_bytes: the minimum scratch of the three calls below for these shapes (n_mels is validated, the size does not depend
+ *                           on it): the clips' lengths, both signals staged as zero-padded rows (2 batch (max_samples + 2 n_fft) floats at
+ *                           most), one fp64 per frame, and the spectra of 128 frames of both signals.  < 0 for unsupported parameters.
+ *   l3ac_stft:              audio [batch][audio_stride] -> spec [batch][F(max_samples)][n_fft/2 + 1][2] (re, im).  `samples`: HOST array of
+ *                           batch lengths in 1..max_samples, or NULL (every clip has max_samples); samples at or after a clip's length are
+ *                           never read into a result, and the rows of `spec` after a clip's own F(samples[i]) frames are zero.  `basis` is
+ *                           the DEVICE copy of l3ac_stft_basis' output.  Every real and imaginary part is one exact-fp32 chain of fused
+ *                           multiply-adds over j in the fixed k order of l3ac_gemm_f32 from +0.
+ *   l3ac_log_mel:           the same arguments plus `weights` (the DEVICE copy of l3ac_mel_weights' output) -> out
+ *                           [batch][F(max_samples)][n_mels], zero after a clip's own frames.  Power = fma(re, re, im im); each cell is one
+ *                           fmaf chain over its filter's run of bins (first to last non-zero weight) in increasing k from +0, then
+ *                           log10f, and exactly -10 when the sum is <= 1e-10f (every cell of an empty filter, every cell of silence).
+ *   l3ac_mel_distance:      ref and est [batch][*_stride] with common lengths -> out [batch] fp64: per cell |L_ref - L_est| in fp64 from
+ *                           the fp32 cells l3ac_log_mel computes, summed per frame and then per clip in a fixed order, divided by
+ *                           F(samples[i]) n_mels.  No floating-point atomics.
+ *   l3ac_signal_metrics:    ref and est as above -> out [batch][3] fp64 = mse, snr_db, si_sdr_db.  Samples converted exactly to fp64; one
+ *                           workgroup per clip, two passes with fixed per-thread strides (1024) and a fixed tree: pass 1 the sums (the
+ *                           means, a, and sum (r - e)^2 directly), pass 2 sum (r - mu_r)^2 and the residual energy directly, never by
+ *                           expanding the square.  `scratch` holds the clips' lengths only: batch int32, unused (may be NULL) when
+ *                           `samples` is NULL.
+ * Bit guarantee: a clip's results do not depend on the batch it is in, on its row, on the row strides, or on the scratch size (a scratch
+ * above the minimum lets one product take more frames; the frames that straddle two staged clips are computed and never stored).
+ * `samples` is handed to the device as kernel arguments (248 per launch): graph-safe.  `scratch` is a caller-owned, 256-byte aligned
+ * device buffer: the calls allocate nothing, do not synchronise, and can be captured into a hipGraph.  Enqueue only. */
+int64_t l3ac_stft_frames(int64_t samples, int32_t hop);
+int64_t l3ac_stft_basis(int32_t n_fft, float* basis, int64_t cap);
+int64_t l3ac_mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap);
+int64_t l3ac_mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels);
+int l3ac_stft(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, float* spec, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_log_mel(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+                 const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_mel_distance(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis, const float* weights, double* out,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                        const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

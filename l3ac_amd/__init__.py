@@ -37,6 +37,8 @@ from . import weights as _weights
 from ._rows import (check_codec_input, contiguous_rows, decode_rows, encode_rows, int_list, refuse_grn_exact, row_stride, validated, window_args,
                     zero_after as _zero_after)
 from .chunking import ChunkData, _chunk_cut, _chunk_groups, _chunk_merge, _group_desc, chunk_plan, plan as _chunk_plan
+from .metrics import (DEFAULT_SCALES, _check_params as _check_metric_params, _scales as _metric_scales, log_mel, mel_distance, mel_weights,
+                      signal_metrics, stft, stft_basis, stft_frames)
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -46,7 +48,8 @@ from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_co
 __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gemm_split_routes", "list_models", "get_model", "get_model_info", "L3AC", "L3ACConfig", "ModelConfig", "Network",
            "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder",
            "StreamResampler", "stream_resampler", "StreamPacker", "StreamUnpacker", "stream_packer", "stream_unpacker", "packed_bytes", "pack_advance",
-           "unpack_advance", "frame_header", "parse_frame"]
+           "unpack_advance", "frame_header", "parse_frame", "stft", "log_mel", "mel_distance", "signal_metrics", "stft_frames", "stft_basis",
+           "mel_weights", "DEFAULT_SCALES"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -531,6 +534,35 @@ class L3AC:
                                  chunks_per_call=chunks_per_call, validate=validate)
         samples = [f.n_samples if rate is None else resample_length(self.config.sample_rate, rate, f.n_samples) for f in parsed]
         return _zero_after(audio[:, :max(samples)], samples), torch.tensor(samples, dtype=torch.int32)
+
+    # ---- quality of the round trip (l3ac_amd/metrics.py) ---------------------------------------
+    @torch.no_grad()
+    def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
+                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None) -> dict:
+        """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
+        and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
+        ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
+        be alone).  Returns ``mel_distance``'s and ``signal_metrics``' entries plus ``"tokens"`` (int32, CPU) and ``"bps"`` (fp64, CPU:
+        ``bits_per_token * tokens / seconds``).  Every value equals composing those public calls by hand, bit for bit."""
+        scales = _metric_scales(scales)
+        for n_fft, hop, n_mels in scales:  # unsupported scales raise before any device work
+            _check_metric_params(self.config.sample_rate, n_fft, hop, n_mels)
+        _, info, lens = self._encode_long(audio_data, lengths, process_window, prefix_tokens, sample_rate, chunks_per_call, False)
+        rate = self._rate(sample_rate)
+        reference = audio_data.to(torch.float32)
+        if rate is not None:
+            given = ragged_lengths([audio_data.shape[1]] * audio_data.shape[0] if lengths is None else lengths, audio_data.shape[0],
+                                   audio_data.shape[1], "lengths")
+            reference = resample(_zero_after(reference, given), rate, self.config.sample_rate)
+        decoded = self.decode_long(indices=info["indices"], lengths=info["lengths"], process_window=process_window, prefix_tokens=prefix_tokens,
+                                   chunks_per_call=chunks_per_call)[:, :reference.shape[1]]
+        out = mel_distance(reference, decoded, sample_rate=self.config.sample_rate, scales=scales, lengths=lens)
+        out.update(signal_metrics(reference, decoded, lengths=lens))
+        tokens = info["lengths"]
+        seconds = torch.tensor(lens, dtype=torch.float64) / self.config.sample_rate
+        out["tokens"] = tokens
+        out["bps"] = bits_per_token(self.network.mc) * tokens.to(torch.float64) / seconds
+        return out
 
     # ---- streaming sessions (DESIGN.md section 3.9; l3ac_amd/streaming.py) -------------------------------------------
     def stream_encoder(self, streams: int, process_window: int = 16000, prefix_tokens: Optional[int] = None,

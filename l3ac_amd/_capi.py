@@ -142,6 +142,14 @@ SIGNATURES = {
     "l3ac_packed_bytes": (_I64, [_I64, _I32]),
     "l3ac_pack_stream": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _I32, C.POINTER(PackStreamDesc), _I32, _P, _I64, _I64, _P]),
     "l3ac_unpack_stream": (C.c_int, [_P, _P, _I32, _P, _I64, _I64, _I32, C.POINTER(UnpackStreamDesc), _I32, _P, _I64, _I64, _P]),
+    "l3ac_stft_frames": (_I64, [_I64, _I32]),
+    "l3ac_stft_basis": (_I64, [_I32, _P, _I64]),
+    "l3ac_mel_weights": (_I64, [_I32, _I32, _I32, _P, _I64]),
+    "l3ac_mel_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32]),
+    "l3ac_stft": (C.c_int, [_P, _I32, _I64, _I64, C.POINTER(_I32), _I32, _I32, _P, _P, _P, _I64, _P]),
+    "l3ac_log_mel": (C.c_int, [_P, _I32, _I64, _I64, C.POINTER(_I32), _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
+    "l3ac_mel_distance": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_signal_metrics": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

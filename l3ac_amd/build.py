@@ -47,6 +47,7 @@ SOURCES = [
     "kernels/resample_stream.hip",
     "kernels/chunk.hip",
     "kernels/stream.hip",
+    "kernels/metrics.hip",
 ]
 
 

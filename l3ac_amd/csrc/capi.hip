@@ -788,6 +788,42 @@ int l3ac_resample_stream(const float* state_in, float* state_out, int32_t stream
                                   out_rate, bank, desc, count, out, out_frames, out_stride);
 }
 
+// ---- quality metrics -------------------------------------------------------------------
+int64_t l3ac_stft_frames(int64_t samples, int32_t hop) { return stft_frames(samples, hop); }
+
+int64_t l3ac_stft_basis(int32_t n_fft, float* basis, int64_t cap) { return stft_basis(n_fft, basis, cap); }
+
+int64_t l3ac_mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap) {
+    return mel_weights(sample_rate, n_fft, n_mels, w, cap);
+}
+
+int64_t l3ac_mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels) {
+    return mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
+}
+
+int l3ac_stft(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, float* spec, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_stft((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, spec, scratch, scratch_bytes);
+}
+
+int l3ac_log_mel(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+                 const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_log_mel((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, out, scratch,
+                          scratch_bytes);
+}
+
+int l3ac_mel_distance(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis, const float* weights, double* out,
+                      void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_mel_distance((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, n_fft, hop, n_mels, basis, weights,
+                               out, scratch, scratch_bytes);
+}
+
+int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                        const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_signal_metrics((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, out, scratch, scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

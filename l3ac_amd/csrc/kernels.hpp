@@ -256,6 +256,21 @@ int launch_pack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_
 int launch_unpack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const uint8_t* fresh, int64_t fresh_bytes,
                          int64_t fresh_stride, int bits, const l3ac_unpack_stream_desc* desc, int count, int32_t* out, int64_t out_tokens,
                          int64_t out_stride);
+// quality metrics (kernels/metrics.hip): STFT as one exact-fp32 GEMM over staged clip rows, log-mel, log-mel
+// distance and the time-domain metrics; `samples` is a host array (null: every clip has max_samples), handed over as kernel arguments
+int64_t stft_frames(int64_t samples, int32_t hop);                          // HOST: 1 + samples / hop, L3AC_EINVAL for samples or hop < 1
+int64_t stft_basis(int32_t n_fft, float* basis, int64_t cap);               // HOST: [n_fft + 2][n_fft] fp32, each entry rounded once from fp64
+int64_t mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap);  // HOST: [n_mels][n_fft / 2 + 1]
+int64_t mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels);
+int launch_stft(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
+                int32_t hop, const float* basis, float* spec, void* scratch, int64_t scratch_bytes);
+int launch_log_mel(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
+                   int32_t hop, const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes);
+int launch_mel_distance(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
+                        int64_t max_samples, const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis,
+                        const float* weights, double* out, void* scratch, int64_t scratch_bytes);
+int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
+                          int64_t max_samples, const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)
