@@ -417,6 +417,42 @@ int l3ac_mel_distance(const float* ref, int64_t ref_stride, const float* est, in
 int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                         const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- speech intelligibility: STOI and ESTOI --------------------------------------------------------------
+ * STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) of clip pairs AT 10 kHz, with the constants of the published implementations:
+ * frames of 256 samples at hop 128 zero-padded to n_fft 512, 15 third-octave bands from 150 Hz, segments of 30 frames, clipping at
+ * -15 dB, 40 dB of dynamic range, eps = 2^-52.  A clip of L samples has A(L) analysis frames: 0 for L <= 256, else
+ * ceil((L - 256) / 128); frame f starts at 128 f < L - 256.  Spec (fp64, on the two fp32 tables below; DESIGN.md section 3.13 in full):
+ * the reference's frame energies e_f = sum_j (w[j] x[128 f + j])^2 decide which frames stay, 20 log10(sqrt(e_f) + eps) > max_f(...) - 40,
+ * the same frames in both signals; each signal is rebuilt from its K kept frames by overlap-add of w[j] x[128 f_q + j] (fp32 on the
+ * device, at most two terms per sample in the order of q); the T = K - 1 spectra of the rebuilt signal are the basis applied to
+ * s[128 t .. 128 t + 256); bands[t][i] = sqrt(sum of re^2 + im^2 over the band's run of bins) is an fp32 cell; every m = 30 .. T gives
+ * one d_m from the 15 x 30 blocks of frames m - 30 .. m - 1 (STOI: rows scaled to the reference's norm, clipped at (1 + 10^(15/20)) x,
+ * centred, normalised, sum x y' / 15;  ESTOI: rows, then columns centred and normalised, sum x y / 30), in fp64; the value is the mean
+ * of the d_m.  T < 30: both values are exactly 1e-5 (the published implementations' convention) and frames_out tells.
+ *   l3ac_stoi_frames:        HOST only: A(samples); < 0 for samples < 1.
+ *   l3ac_stoi_window:        HOST only: w[j] = hanning(258)[1 + j], 256 floats, designed in fp64 and rounded once; the size-query protocol
+ *                            of l3ac_stft_basis (returns the length; fills the buffer when it is non-null and cap >= that length).
+ *   l3ac_stoi_basis:         HOST only: the window-folded basis [514][256]: row 2k = w[j] cos(2 pi (j k mod 512) / 512), row 2k + 1 =
+ *                            -w[j] sin(...), k = 0 .. 256; same protocol.  Row 0 is the window.  The caller copies it to the device once.
+ *   l3ac_stoi_bands:         HOST only: runs[2 i], runs[2 i + 1] = the bins [lo, hi) of band i = 0 .. 14 (30 ints): lo = the bin nearest to
+ *                            150 * 2^((2 i - 1) / 6) Hz, hi = the bin nearest to 150 * 2^((2 i + 1) / 6) Hz, bin k at k * 10000 / 512 Hz.
+ *   l3ac_stoi_scratch_bytes: the minimum scratch of l3ac_stoi for these shapes; < 0 for batch outside 1..65535 or clips too long.
+ *   l3ac_stoi:               ref and est [batch][*_stride] at 10 kHz with common lengths (`samples`: HOST array of batch lengths in
+ *                            1..max_samples, or NULL) -> out [batch][2] fp64 = stoi, estoi; frames_out [batch] int32 (device) = T;
+ *                            bands_out (device, or NULL) [2][batch][A(max_samples) - 1][15] fp32: the reference's, then the estimate's
+ *                            band cells, zero at and after a clip's own T frames.  `basis` is the DEVICE copy of l3ac_stoi_basis' output.
+ *                            Every bad argument (batch 0 or above 65535, a length outside 1..max_samples, a row stride below
+ *                            max_samples, a null buffer, a scratch below the minimum, clips too long) is L3AC_EINVAL before any device work.
+ * Bit guarantee and calling convention: as the quality metrics above (a clip's results do not depend on the batch, its row, the strides
+ * or the scratch size; no atomics; enqueue only, nothing allocated, no synchronisation, capturable). */
+int64_t l3ac_stoi_frames(int64_t samples);
+int64_t l3ac_stoi_basis(float* basis, int64_t cap);
+int64_t l3ac_stoi_window(float* window, int64_t cap);
+int l3ac_stoi_bands(int32_t* runs);
+int64_t l3ac_stoi_scratch_bytes(int32_t batch, int64_t max_samples);
+int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+              const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

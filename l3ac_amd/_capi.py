@@ -150,6 +150,12 @@ SIGNATURES = {
     "l3ac_log_mel": (C.c_int, [_P, _I32, _I64, _I64, C.POINTER(_I32), _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "l3ac_mel_distance": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "l3ac_signal_metrics": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _P, _I64, _P]),
+    "l3ac_stoi_frames": (_I64, [_I64]),
+    "l3ac_stoi_basis": (_I64, [_P, _I64]),
+    "l3ac_stoi_window": (_I64, [_P, _I64]),
+    "l3ac_stoi_bands": (C.c_int, [C.POINTER(_I32)]),
+    "l3ac_stoi_scratch_bytes": (_I64, [_I32, _I64]),
+    "l3ac_stoi": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _P, _P, _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

@@ -48,6 +48,7 @@ SOURCES = [
     "kernels/chunk.hip",
     "kernels/stream.hip",
     "kernels/metrics.hip",
+    "kernels/stoi.hip",
 ]
 
 

@@ -824,6 +824,23 @@ int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, 
     return launch_signal_metrics((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, out, scratch, scratch_bytes);
 }
 
+// ---- speech intelligibility ----------------------------------------------------------
+int64_t l3ac_stoi_frames(int64_t samples) { return stoi_frames(samples); }
+
+int64_t l3ac_stoi_basis(float* basis, int64_t cap) { return stoi_basis(basis, cap); }
+
+int64_t l3ac_stoi_window(float* window, int64_t cap) { return stoi_window(window, cap); }
+
+int l3ac_stoi_bands(int32_t* runs) { return stoi_bands(runs); }
+
+int64_t l3ac_stoi_scratch_bytes(int32_t batch, int64_t max_samples) { return stoi_scratch_bytes(batch, max_samples); }
+
+int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+              const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_stoi((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, basis, out, frames_out, bands_out, scratch,
+                       scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

@@ -271,6 +271,15 @@ int launch_mel_distance(hipStream_t s, const float* ref, int64_t ref_stride, con
                         const float* weights, double* out, void* scratch, int64_t scratch_bytes);
 int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
                           int64_t max_samples, const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes);
+// speech intelligibility (kernels/stoi.hip; include/l3ac_hip.h "speech intelligibility"): STOI and ESTOI of pairs at 10 kHz
+int64_t stoi_frames(int64_t samples);               // HOST: A(samples), L3AC_EINVAL for samples < 1
+int64_t stoi_basis(float* basis, int64_t cap);      // HOST: [514][256] fp32, each entry rounded once from fp64
+int64_t stoi_window(float* w, int64_t cap);         // HOST: [256] fp32 = row 0 of the basis
+int stoi_bands(int32_t* runs);                      // HOST: 15 x (lo, hi)
+int64_t stoi_scratch_bytes(int32_t batch, int64_t max_samples);
+int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                const int32_t* samples, const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch,
+                int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

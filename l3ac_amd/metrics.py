@@ -1,5 +1,6 @@
 """Quality metrics on the GPU (csrc/kernels/metrics.hip): ``stft``, ``log_mel``, ``mel_distance`` and
-``signal_metrics``, and the per-device cache of the library's two fp32 tables (the window-folded DFT basis and the mel weights)."""
+``signal_metrics``, and the per-device cache of the library's two fp32 tables (the window-folded DFT basis and the mel weights); and
+speech intelligibility (csrc/kernels/stoi.hip, section 3.13): ``stoi`` and its host accessors."""
 from __future__ import annotations
 
 import ctypes
@@ -8,7 +9,8 @@ from typing import Optional
 import torch
 
 from . import _capi
-from ._rows import contiguous_rows, int_list, row_stride
+from ._rows import contiguous_rows, int_list, row_stride, zero_after
+from .resampling import resample, resample_length
 
 DEFAULT_SCALES = ((256, 64, 20), (512, 128, 40), (1024, 256, 80), (2048, 512, 80))  # (n_fft, hop, n_mels) at 16 kHz
 
@@ -211,3 +213,82 @@ def signal_metrics(reference: torch.Tensor, estimate: torch.Tensor, lengths=None
                                                              out.data_ptr(), scratch.data_ptr(), scratch.numel(),
                                                              torch.cuda.current_stream(dev).cuda_stream))
     return {"mse": out[:, 0].contiguous(), "snr_db": out[:, 1].contiguous(), "si_sdr_db": out[:, 2].contiguous()}
+
+
+# ---- speech intelligibility (csrc/kernels/stoi.hip) -----------------------------------------------------------
+STOI_RATE = 10000  # the rate STOI and ESTOI are defined at
+
+
+def stoi_frames(samples: int) -> int:
+    """Analysis frames of a clip of ``samples`` samples at 10 kHz: 0 up to 256 samples, else ceil((samples - 256) / 128); ``stoi``
+    then has one spectral frame fewer than the frames it keeps.  Raises ValueError for samples < 1."""
+    n = _capi.load_library().l3ac_stoi_frames(int(samples))
+    if n < 0:
+        raise ValueError(_capi.load_library().l3ac_last_error().decode())
+    return int(n)
+
+
+def stoi_basis() -> torch.Tensor:
+    """The library's window-folded STOI basis (514, 256) fp32 on the CPU: row 2k = w cos, row 2k + 1 = -w sin of bin k of a 512-point
+    DFT, w = hanning(258)[1:-1]; row 0 is the window."""
+    lib = _capi.load_library()
+    n = lib.l3ac_stoi_basis(None, 0)
+    host = torch.empty(n, dtype=torch.float32)
+    lib.l3ac_stoi_basis(host.data_ptr(), n)
+    return host.view(514, 256)
+
+
+def stoi_bands() -> list:
+    """The 15 third-octave bands as runs of bins ``[(lo, hi), ...]`` (hi exclusive) of the 512-point DFT at 10 kHz."""
+    runs = (ctypes.c_int32 * 30)()
+    _capi.check(_capi.load_library().l3ac_stoi_bands(runs))
+    return [(int(runs[2 * i]), int(runs[2 * i + 1])) for i in range(15)]
+
+
+@torch.no_grad()
+def stoi(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: int = 16000, lengths=None, return_bands: bool = False,
+         extra_scratch=None) -> dict:
+    """STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) of (B, T) fp32 CUDA pairs -> ``{"stoi": (B,) fp64 CUDA, "estoi": (B,) fp64
+    CUDA, "frames": (B,) int32 CUDA}``, with the published implementations' constants (10 kHz, frames of 256 at hop 128, 15
+    third-octave bands from 150 Hz, segments of 30 frames, -15 dB clipping, 40 dB range).  ``frames`` is the number of spectral
+    frames left after the reference's silent frames are removed; below 30 there is no segment and both values are exactly 1e-5, the
+    published convention.  When ``sample_rate`` is not 10000 both signals go through this library's ``resample`` first (each clip as
+    it would be alone), not through the Matlab-style resampler of ``pystoi``: for such inputs the values differ from that package's
+    in the later digits.  ``lengths``: the pairs' common lengths at ``sample_rate``, as in ``stft``.  ``return_bands`` adds
+    ``"bands_reference"`` and ``"bands_estimate"``, (B, stoi_frames(T at 10 kHz) - 1, 15) fp32, zero after a clip's own frames.
+    A clip's bits do not depend on the batch it is in; ``extra_scratch`` as in ``stft``.  No CPU path: CPU tensors raise."""
+    sample_rate = int(sample_rate)
+    if sample_rate != STOI_RATE:
+        resample_length(sample_rate, STOI_RATE, 1)  # unsupported rates raise before any device work
+    r, e = _pair(reference, estimate, "stoi")
+    b, t = r.shape
+    lens, c_lens = _lengths(lengths, b, t)
+    if sample_rate != STOI_RATE:
+        given = [t] * b if lens is None else lens
+        r = resample(zero_after(r, given), sample_rate, STOI_RATE)
+        e = resample(zero_after(e, given), sample_rate, STOI_RATE)
+        t = r.shape[1]
+        lens, c_lens = _lengths([resample_length(sample_rate, STOI_RATE, n) for n in given], b, t)
+    dev = r.device
+    lib = _capi.load_library()
+    basis = _table(dev, ("stoi_basis",), stoi_basis)
+    need = lib.l3ac_stoi_scratch_bytes(b, t)
+    if need < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    t_max = max(stoi_frames(t) - 1, 0)
+    if extra_scratch is None:  # the default, never more than the spectra of every frame row of both signals
+        extra = min(_EXTRA_SCRATCH, 2 * b * (t_max + 3) * 516 * 4)
+    else:
+        extra = max(0, int(extra_scratch))
+    out = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    frames = torch.empty(b, dtype=torch.int32, device=dev)
+    bands = torch.empty((2, b, t_max, 15), dtype=torch.float32, device=dev) if return_bands else None
+    with torch.cuda.device(dev):
+        scratch = torch.empty(int(need) + extra, dtype=torch.uint8, device=dev)
+        _capi.check(lib.l3ac_stoi(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, basis.data_ptr(), out.data_ptr(),
+                                  frames.data_ptr(), None if bands is None or not t_max else bands.data_ptr(), scratch.data_ptr(),
+                                  scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    result = {"stoi": out[:, 0].contiguous(), "estoi": out[:, 1].contiguous(), "frames": frames}
+    if return_bands:
+        result["bands_reference"], result["bands_estimate"] = bands[0], bands[1]
+    return result
