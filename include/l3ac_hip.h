@@ -453,6 +453,45 @@ int64_t l3ac_stoi_scratch_bytes(int32_t batch, int64_t max_samples);
 int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
               const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- loudness: BS.1770-4 integrated loudness and loudness normalisation ---------------------------------------
+ * Integrated loudness of MONO clips (one channel of weight 1.0) after ITU-R BS.1770-4, in fp64 throughout: K-weighting (two biquads in
+ * cascade, designed on the host by De Man's closed forms evaluated AT the sample rate, the choice pyloudnorm makes; at 48 kHz they are
+ * the standard's table), blocks of 400 ms at 75 % overlap, the absolute gate at -70 LKFS and the relative gate 10 LU below the loudness
+ * of the absolutely gated blocks.  A rate fs is supported iff fs % 10 == 0 and 8000 <= fs <= 192000; step = fs / 10.  A clip of n samples
+ * has S = n / step whole steps and J(n) = max(S - 3, 0) blocks; samples at or after S step enter nothing but the peak.  The filter
+ * starts from rest at sample 0.  L = -inf exactly when no block passes both gates (J = 0 and digital silence included).  The recursion
+ * runs in parallel over the steps (a zero-state pass, a per-clip scan of the 4-value state, an energy pass).
+ *   l3ac_loudness_coeffs:        HOST only: out[0..11] = the two stages' b0 b1 b2 a0 a1 a2 (a0 = 1), out[12..27] = M [4][4] row-major, the
+ *                                matrix that advances the cascade's state (s1, s2 of stage 1, s1, s2 of stage 2; transposed direct form II)
+ *                                over one step of zero input.  The size-query protocol of l3ac_stft_basis (returns 28; fills the buffer
+ *                                when it is non-null and cap >= 28).  < 0 with a message for an unsupported rate.
+ *   l3ac_loudness_blocks:        HOST only: J(samples); < 0 for samples < 1 or an unsupported rate.
+ *   l3ac_loudness_scratch_bytes: the minimum scratch of l3ac_loudness for these shapes; < 0 for batch outside 1..65535, max_samples outside
+ *                                1..2^31 - 1 or an unsupported rate.
+ *   l3ac_loudness:               audio [batch][audio_stride] (`samples`: HOST array of batch lengths in 1..max_samples, or NULL) -> stats
+ *                                [batch][2] fp64 = L in LKFS, the sample peak max |x| over the clip's own samples; counts [batch][2] int32 =
+ *                                J, the blocks that pass both gates; momentary (device, or NULL) [batch][J(max_samples)] fp64 = the blocks'
+ *                                loudness l_j, -inf at and after a clip's own J.  All outputs are device buffers.
+ *   l3ac_loudness_gain:          stats [batch][2] (device, as written by l3ac_loudness) -> gain [batch][2] fp64 (device) = g_db, 10^(g_db/20):
+ *                                g_db = target_lufs - L, with a peak_limit_db (NaN: none) and peak > 0 at most peak_limit_db -
+ *                                20 log10(peak), and exactly 0 when L = -inf.  No host synchronisation.
+ *   l3ac_apply_gain:             out[b][i] = (float)((double)audio[b][i] * gain[b * gain_stride]) for i below the clip's length, 0 from there
+ *                                to max_samples.  out == audio is allowed.  16-byte accesses when both pointers are 16-byte aligned and
+ *                                both strides multiples of 4 (the bits are the same either way).
+ * Every bad argument (batch 0 or above 65535, a length outside 1..max_samples, a row stride below max_samples, a null buffer, a scratch
+ * below the minimum, an unsupported rate, a non-finite target) is L3AC_EINVAL before any device work, with a message naming it.
+ * Bit guarantee and calling convention: as the quality metrics above (a clip's results do not depend on the batch, its row, the strides
+ * or the scratch size; no atomics; enqueue only, nothing allocated, no synchronisation, capturable).  There is no device table: the
+ * coefficients and M travel as kernel arguments, so nothing needs a warm-up before a capture. */
+int64_t l3ac_loudness_coeffs(int32_t sample_rate, double* out, int64_t cap);
+int64_t l3ac_loudness_blocks(int64_t samples, int32_t sample_rate);
+int64_t l3ac_loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate);
+int l3ac_loudness(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                  double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain, void* stream);
+int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
+                    const int32_t* samples, const double* gain, int64_t gain_stride, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -39,6 +39,8 @@ from ._rows import (check_codec_input, contiguous_rows, decode_rows, encode_rows
 from .chunking import ChunkData, _chunk_cut, _chunk_groups, _chunk_merge, _group_desc, chunk_plan, plan as _chunk_plan
 from .metrics import (DEFAULT_SCALES, _check_params as _check_metric_params, _scales as _metric_scales, log_mel, mel_distance, mel_weights,
                       signal_metrics, stft, stft_basis, stft_frames, stoi, stoi_bands, stoi_basis, stoi_frames)
+from .loudness import (_check_rate as _check_loudness_rate, apply_gain, loudness, loudness as _loudness, loudness_blocks, loudness_coeffs, loudness_gain,
+                       normalize_loudness)
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -49,7 +51,8 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "bits_per_token", "pack_indices", "unpack_indices", "ChunkData", "resample", "resample_length", "ragged_lengths", "chunk_plan", "StreamEncoder", "StreamDecoder",
            "StreamResampler", "stream_resampler", "StreamPacker", "StreamUnpacker", "stream_packer", "stream_unpacker", "packed_bytes", "pack_advance",
            "unpack_advance", "frame_header", "parse_frame", "stft", "log_mel", "mel_distance", "signal_metrics", "stft_frames", "stft_basis",
-           "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands"]
+           "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands", "loudness", "loudness_gain", "apply_gain",
+           "normalize_loudness", "loudness_coeffs", "loudness_blocks"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -538,15 +541,18 @@ class L3AC:
     # ---- quality of the round trip (l3ac_amd/metrics.py) ---------------------------------------
     @torch.no_grad()
     def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
-                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False) -> dict:
+                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False) -> dict:
         """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
         and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
         ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
         be alone).  Returns ``mel_distance``'s and ``signal_metrics``' entries plus ``"tokens"`` (int32, CPU) and ``"bps"`` (fp64, CPU:
         ``bits_per_token * tokens / seconds``).  ``intelligibility=True`` adds ``"stoi"``, ``"estoi"`` and ``"stoi_frames"``: ``stoi``
-        of the same pairs at the codec's rate.  Every value equals composing those public calls by hand, bit
-        for bit."""
+        of the same pairs at the codec's rate.  ``loudness=True`` adds ``"loudness_reference"``,
+        ``"loudness_decoded"`` and ``"loudness_shift"`` (decoded - reference, in LU): ``l3ac_amd.loudness`` of each side at the codec's
+        rate (section 3.14).  Every value equals composing those public calls by hand, bit for bit."""
         scales = _metric_scales(scales)
+        if loudness:  # a rate the K-weighting is not defined for raises before any device work
+            _check_loudness_rate(self.config.sample_rate)
         if intelligibility and self.config.sample_rate != 10000:  # a rate that cannot be taken to 10 kHz raises before any device work
             resample_length(self.config.sample_rate, 10000, 1)
         for n_fft, hop, n_mels in scales:  # unsupported scales raise before any device work
@@ -565,6 +571,10 @@ class L3AC:
         if intelligibility:
             si = stoi(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
             out.update({"stoi": si["stoi"], "estoi": si["estoi"], "stoi_frames": si["frames"]})
+        if loudness:
+            l_ref = _loudness(reference, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
+            l_dec = _loudness(decoded, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
+            out.update({"loudness_reference": l_ref, "loudness_decoded": l_dec, "loudness_shift": l_dec - l_ref})
         tokens = info["lengths"]
         seconds = torch.tensor(lens, dtype=torch.float64) / self.config.sample_rate
         out["tokens"] = tokens

@@ -49,6 +49,7 @@ SOURCES = [
     "kernels/stream.hip",
     "kernels/metrics.hip",
     "kernels/stoi.hip",
+    "kernels/loudness.hip",
 ]
 
 

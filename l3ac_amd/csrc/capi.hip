@@ -841,6 +841,30 @@ int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t es
                        scratch_bytes);
 }
 
+// ---- loudness ---------------------------------------------------------------------------
+int64_t l3ac_loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) { return loudness_coeffs(sample_rate, out, cap); }
+
+int64_t l3ac_loudness_blocks(int64_t samples, int32_t sample_rate) { return loudness_blocks(samples, sample_rate); }
+
+int64_t l3ac_loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
+    return loudness_scratch_bytes(batch, max_samples, sample_rate);
+}
+
+int l3ac_loudness(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                  double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_loudness((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, stats, counts, momentary, scratch,
+                           scratch_bytes);
+}
+
+int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain, void* stream) {
+    return launch_loudness_gain((hipStream_t)stream, stats, batch, target_lufs, peak_limit_db, gain);
+}
+
+int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
+                    const int32_t* samples, const double* gain, int64_t gain_stride, void* stream) {
+    return launch_apply_gain((hipStream_t)stream, audio, audio_stride, out, out_stride, batch, max_samples, samples, gain, gain_stride);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

@@ -280,6 +280,16 @@ int64_t stoi_scratch_bytes(int32_t batch, int64_t max_samples);
 int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                 const int32_t* samples, const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch,
                 int64_t scratch_bytes);
+// loudness (kernels/loudness.hip; include/l3ac_hip.h "loudness"): BS.1770-4 integrated loudness of mono clips in fp64,
+// the K-weighting recursion parallel over 100 ms steps (zero-state pass, per-clip scan of the 4-value state, energy pass), and the gain
+int64_t loudness_coeffs(int32_t sample_rate, double* out, int64_t cap);     // HOST: [2][6] b0 b1 b2 a0 a1 a2, then M [4][4]
+int64_t loudness_blocks(int64_t samples, int32_t sample_rate);              // HOST: J(samples)
+int64_t loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate);
+int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                    int32_t sample_rate, double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes);
+int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain);
+int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, const double* gain, int64_t gain_stride);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -1,0 +1,475 @@
+// ITU-R BS.1770-4 integrated loudness of mono clips, and loudness normalisation (include/l3ac_hip.h, "loudness").  No
+// reference counterpart.  Everything here is fp64; the fp32 samples convert exactly.
+//
+// K-weighting is two biquads in cascade (transposed direct form II), a linear recurrence with a 4-value state (s1, s2 of the shelf, s1, s2
+// of the high-pass).  It runs in parallel over time with one step (100 ms, fs / 10 samples) as the segment:
+//   1. loudness_pass_kernel<false>  every (clip, step) filters its samples from a ZERO state and writes its 4-value end state; the same
+//                                   pass takes the step's max |x|
+//   2. loudness_scan_kernel         one thread per clip walks the steps in order: start_{s+1} = M start_s + end_s, M the 4x4 matrix that
+//                                   advances the cascade's state over one step of zero input (the response is linear: from a true start
+//                                   state the end state is the zero-input part M start plus the zero-state part); start_s replaces end_s.
+//                                   M and the running state are pairs of doubles (hi + lo), see Pair below
+//   3. loudness_pass_kernel<true>   every (clip, step) reruns the recursion from its true start state and sums y^2 in sample order: e_s
+//   4. loudness_gate_kernel         one workgroup per clip: z_j, l_j, the absolute and the relative gate, L, the sample peak, the counts
+// The coefficients and M are designed on the host in fp64 (loudness_coeffs) and travel as kernel arguments: no device table, nothing to
+// warm up before a capture.  A step's values depend on its own samples and on the steps before it in its own clip only — never on the
+// batch, the clip's row, the row stride or the scratch size; no atomics; the sums of the gate kernel run over fixed strides and a fixed tree.
+//
+// One lane per step reads rows `step` floats apart, so a wave's 64 steps are staged through LDS 32 samples at a time: the loads run
+// along the rows (128 contiguous bytes per half wave, any alignment, any step), the recursion reads its own row of the tile at an odd
+// pitch (no bank conflicts), and the next round's loads are in flight while the current one is filtered.
+//
+// The product of a multiply must not be fused into the add that follows it differently in the two passes or on the host: contraction is
+// off for this whole file, host code included (M is designed by the same recursion).
+#include "../kernels.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int LD_STEPS = 64;              // steps per workgroup: one wave, one lane per step
+constexpr int LD_CHUNK = 32;              // samples of every step staged per round
+constexpr int LD_PITCH = LD_CHUNK + 1;    // odd: lane l reads bank (l + j) % 32
+constexpr int LD_GATE_THREADS = 256;
+constexpr int LD_GAIN_THREADS = 256;
+constexpr int LD_MIN_RATE = 8000, LD_MAX_RATE = 192000;
+
+struct LoudFilter {  // b0 b1 b2 a1 a2 of the two stages (a0 = 1), M row-major as hi + lo, the step in samples
+    double c[2][5];
+    double m[4][4], m_lo[4][4];
+    int step;
+};
+
+struct LoudScratch {  // byte offsets into the caller's scratch
+    int64_t lens, state, energy, step_max, total_min;
+};
+
+int64_t align256(int64_t v) { return round_up64(v, 256); }
+
+bool rate_ok(int32_t fs) { return fs % 10 == 0 && fs >= LD_MIN_RATE && fs <= LD_MAX_RATE; }
+
+#define LD_REQUIRE_RATE(fs) \
+    L3AC_REQUIRE(rate_ok(fs), "loudness: sample_rate %d must be a multiple of 10 in %d..%d", fs, LD_MIN_RATE, LD_MAX_RATE)
+
+// one sample through one biquad, transposed direct form II: the order of scipy.signal.sosfilt
+template <typename T>
+__host__ __device__ __forceinline__ T biquad(const T (&c)[5], T x, T& s1, T& s2) {
+    const T y = c[0] * x + s1;
+    s1 = c[1] * x - c[3] * y + s2;
+    s2 = c[2] * x - c[4] * y;
+    return y;
+}
+
+// An unevaluated sum hi + lo of two doubles (Dekker / Knuth): what the scan carries.  M's entries are some 1e4 times its eigenvalues (a
+// near-double pole: n p^n), so a matrix rounded to fp64, or a product summed in fp64, moves the decay of a free tail by 1e-9 a step;
+// with pairs the scan adds nothing to what the passes' own fp64 recursion costs.  The one fma here is spelled out.
+struct Pair {
+    double hi, lo;
+};
+__device__ __forceinline__ Pair fast_two_sum(double a, double b) {  // |a| >= |b|
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+__device__ __forceinline__ Pair pair_add(Pair a, Pair b) {
+    const double s = a.hi + b.hi, bb = s - a.hi;
+    const double err = (a.hi - (s - bb)) + (b.hi - bb);
+    return fast_two_sum(s, err + (a.lo + b.lo));
+}
+__device__ __forceinline__ Pair pair_mul(Pair a, Pair b) {
+    const double p = a.hi * b.hi;
+    const double err = fma(a.hi, b.hi, -p);
+    return fast_two_sum(p, err + (a.hi * b.lo + a.lo * b.hi));
+}
+
+int loud_geom(int32_t batch, int64_t max_samples, int32_t sample_rate, int64_t* s_max, LoudScratch* sc) {
+    LD_REQUIRE_RATE(sample_rate);
+    L3AC_REQUIRE(batch > 0 && batch <= 65535, "loudness: batch %d outside 1..65535", batch);
+    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "loudness: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
+    *s_max = max_samples / (sample_rate / 10);
+    int64_t off = 0;
+    sc->lens = off;
+    off += align256((int64_t)batch * 4);
+    sc->state = off;
+    off += align256((int64_t)batch * *s_max * 4 * 8);
+    sc->energy = off;
+    off += align256((int64_t)batch * *s_max * 8);
+    sc->step_max = off;
+    off += align256((int64_t)batch * *s_max * 4);
+    sc->total_min = off;
+    return L3AC_OK;
+}
+
+int check_lengths(const int32_t* samples, int batch, int64_t max_samples) {
+    if (!samples) return L3AC_OK;
+    for (int i = 0; i < batch; ++i)
+        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "loudness: samples[%d] = %d outside [1, %lld]", i, samples[i],
+                     (long long)max_samples);
+    return L3AC_OK;
+}
+
+// ---- phases 1 and 3: grid (groups of 64 steps, batch), one wave ----------------------------------------------------------------------
+// ENERGY = false: from a zero state; writes state[clip][s][4] = the end state and step_max[clip][s].
+// ENERGY = true:  from state[clip][s] (the scan's true start state); writes energy[clip][s] = sum y^2 in the order of the samples.
+template <bool ENERGY>
+__global__ __launch_bounds__(LD_STEPS) void loudness_pass_kernel(const float* __restrict__ audio, int64_t stride, int64_t max_samples,
+                                                                const int* __restrict__ lens, LoudFilter f, int64_t s_max,
+                                                                double* __restrict__ state, double* __restrict__ energy,
+                                                                float* __restrict__ step_max) {
+    __shared__ float tile[LD_STEPS * LD_PITCH];
+    const int b = blockIdx.y;
+    const int64_t n = lens ? lens[b] : max_samples;
+    const int64_t steps = n / f.step;  // every sample of a whole step lies inside the clip: (s + 1) step <= n
+    const int64_t s0 = (int64_t)blockIdx.x * LD_STEPS;
+    if (s0 >= steps) return;  // (the whole workgroup)
+    const float* x = audio + (int64_t)b * stride;
+    const int lane = threadIdx.x;
+    const int64_t s = s0 + lane;
+    const bool active = s < steps;
+    // round r of the loads: row 2 i + (lane >> 5) of the tile, column lane & 31, i = 0 .. 31
+    const int col = lane & (LD_CHUNK - 1), half = lane >> 5;
+    float pre[LD_CHUNK];
+    auto fetch = [&](int c0) {
+        const bool col_ok = c0 + col < f.step;
+#pragma unroll
+        for (int i = 0; i < LD_CHUNK; ++i) {
+            const int64_t row = s0 + 2 * i + half;
+            pre[i] = (col_ok && row < steps) ? x[row * f.step + c0 + col] : 0.f;
+        }
+    };
+    double s1a = 0.0, s2a = 0.0, s1b = 0.0, s2b = 0.0, e = 0.0;
+    float mx = 0.f;
+    double* st = state + ((int64_t)b * s_max + s) * 4;
+    if (ENERGY && active) s1a = st[0], s2a = st[1], s1b = st[2], s2b = st[3];
+    fetch(0);
+    for (int c0 = 0; c0 < f.step; c0 += LD_CHUNK) {
+        __syncthreads();  // the previous round's reads are over
+#pragma unroll
+        for (int i = 0; i < LD_CHUNK; ++i) tile[(2 * i + half) * LD_PITCH + col] = pre[i];
+        __syncthreads();
+        if (c0 + LD_CHUNK < f.step) fetch(c0 + LD_CHUNK);
+        const int count = min(LD_CHUNK, f.step - c0);
+        for (int j = 0; j < count; ++j) {
+            const float xf = tile[lane * LD_PITCH + j];
+            const double y = biquad(f.c[1], biquad(f.c[0], (double)xf, s1a, s2a), s1b, s2b);
+            if (ENERGY) e = e + y * y;
+            else mx = fmaxf(mx, fabsf(xf));
+        }
+    }
+    if (!active) return;
+    if (ENERGY) {
+        energy[(int64_t)b * s_max + s] = e;
+    } else {
+        st[0] = s1a, st[1] = s2a, st[2] = s1b, st[3] = s2b;
+        step_max[(int64_t)b * s_max + s] = mx;
+    }
+}
+
+// ---- phase 2: one thread per clip; state[clip][s] = the end state from zero -> the true start state -------------------------------------
+__global__ __launch_bounds__(64) void loudness_scan_kernel(int batch, int64_t max_samples, const int* __restrict__ lens, LoudFilter f, int64_t s_max,
+                                                         double* __restrict__ state) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    const int64_t steps = (lens ? lens[b] : max_samples) / f.step;
+    double* st = state + (int64_t)b * s_max * 4;
+    Pair cur[4] = {};
+    for (int64_t s = 0; s < steps; ++s, st += 4) {
+        const double end[4] = {st[0], st[1], st[2], st[3]};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[k] = cur[k].hi;  // the passes start from the pair rounded to fp64
+        Pair nxt[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            Pair acc = pair_mul({f.m[k][0], f.m_lo[k][0]}, cur[0]);
+#pragma unroll
+            for (int i = 1; i < 4; ++i) acc = pair_add(acc, pair_mul({f.m[k][i], f.m_lo[k][i]}, cur[i]));
+            nxt[k] = pair_add(acc, {end[k], 0.0});
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+    }
+}
+
+// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order; every thread gets the result
+__device__ __forceinline__ double ld_block_sum(double v, double* lds) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();  // the previous use of lds is over
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < LD_GATE_THREADS / 64; ++w) s += lds[w];
+    return s;
+}
+
+__device__ __forceinline__ double ld_block_max(double v, double* lds) {  // (a maximum does not depend on the order)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = lds[0];
+#pragma unroll
+    for (int w = 1; w < LD_GATE_THREADS / 64; ++w) s = fmax(s, lds[w]);
+    return s;
+}
+
+// ---- phase 4: blocks, gates, L; one workgroup per clip ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(LD_GATE_THREADS) void loudness_gate_kernel(const float* __restrict__ audio, int64_t stride, int64_t max_samples,
+                                                                      const int* __restrict__ lens, int step, int64_t s_max, int64_t j_max,
+                                                                      const double* __restrict__ energy, const float* __restrict__ step_max,
+                                                                      double* __restrict__ stats, int* __restrict__ counts,
+                                                                      double* __restrict__ momentary) {
+    __shared__ double lds[LD_GATE_THREADS / 64];
+    const int b = blockIdx.x;
+    const int64_t n = lens ? lens[b] : max_samples;
+    const int64_t steps = n / step;
+    const int64_t blocks = steps > 3 ? steps - 3 : 0;
+    const double* e = energy + (int64_t)b * s_max;
+    const double norm = 4.0 * (double)step;
+    const double ninf = -__builtin_huge_val();
+    auto mean_square = [&](int64_t j) { return (((e[j] + e[j + 1]) + e[j + 2]) + e[j + 3]) / norm; };
+    auto lkfs = [&](double z) { return -0.691 + 10.0 * log10(z); };  // (-inf for z = 0)
+
+    // the absolute gate; the l_j row on request
+    double sum = 0.0, cnt = 0.0;
+    for (int64_t j = threadIdx.x; j < blocks; j += LD_GATE_THREADS) {
+        const double z = mean_square(j), l = lkfs(z);
+        if (momentary) momentary[(int64_t)b * j_max + j] = l;
+        if (l > -70.0) sum += z, cnt += 1.0;
+    }
+    if (momentary)
+        for (int64_t j = blocks + threadIdx.x; j < j_max; j += LD_GATE_THREADS) momentary[(int64_t)b * j_max + j] = ninf;
+    sum = ld_block_sum(sum, lds);
+    cnt = ld_block_sum(cnt, lds);  // (whole numbers below 2^31: exact)
+    // the relative gate, 10 LU below the loudness of the absolutely gated blocks (no such block: nothing passes)
+    const double gamma = lkfs(sum / cnt) - 10.0;
+    double sum2 = 0.0, cnt2 = 0.0;
+    if (cnt > 0.0) {
+        for (int64_t j = threadIdx.x; j < blocks; j += LD_GATE_THREADS) {
+            const double z = mean_square(j), l = lkfs(z);
+            if (l > -70.0 && l > gamma) sum2 += z, cnt2 += 1.0;
+        }
+    }
+    sum2 = ld_block_sum(sum2, lds);
+    cnt2 = ld_block_sum(cnt2, lds);
+
+    // the sample peak over the clip's own n samples: the whole steps' maxima, then the samples after the last whole step
+    double peak = 0.0;
+    for (int64_t s = threadIdx.x; s < steps; s += LD_GATE_THREADS) peak = fmax(peak, (double)step_max[(int64_t)b * s_max + s]);
+    const float* x = audio + (int64_t)b * stride;
+    for (int64_t i = steps * step + threadIdx.x; i < n; i += LD_GATE_THREADS) peak = fmax(peak, (double)fabsf(x[i]));
+    peak = ld_block_max(peak, lds);
+
+    if (threadIdx.x == 0) {
+        stats[2 * (int64_t)b] = cnt2 > 0.0 ? lkfs(sum2 / cnt2) : ninf;
+        stats[2 * (int64_t)b + 1] = peak;
+        counts[2 * (int64_t)b] = (int)blocks;
+        counts[2 * (int64_t)b + 1] = (int)cnt2;
+    }
+}
+
+// ---- stats [batch][2] (L, peak) -> gain [batch][2] (g_db, gain) -----------------------------------------------------------------------------
+__global__ __launch_bounds__(LD_GAIN_THREADS) void loudness_gain_kernel(const double* __restrict__ stats, int batch, double target, double limit,
+                                                                      int has_limit, double* __restrict__ gain) {
+    const int b = blockIdx.x * LD_GAIN_THREADS + threadIdx.x;
+    if (b >= batch) return;
+    const double l = stats[2 * (int64_t)b], peak = stats[2 * (int64_t)b + 1];
+    double g_db = target - l;
+    if (has_limit && peak > 0.0) g_db = fmin(g_db, limit - 20.0 * log10(peak));
+    if (l == -__builtin_huge_val()) g_db = 0.0;
+    gain[2 * (int64_t)b] = g_db;
+    gain[2 * (int64_t)b + 1] = pow(10.0, g_db / 20.0);
+}
+
+// ---- out = (float)((double)x gain), zeros at and after the clip's length; grid (quads of a row / 256, batch) ----------------------------
+// The lengths of the launch's clips (at most RaggedUpload::CAP, clips lens.offset ...) are kernel arguments: the entry takes no scratch.
+// VEC: both rows are 16-byte aligned (the host checked the pointers and the strides); the quad that straddles max_samples goes one by one.
+template <bool VEC>
+__global__ __launch_bounds__(LD_GAIN_THREADS) void apply_gain_kernel(const float* audio, int64_t stride, float* out, int64_t out_stride,
+                                                                   int64_t max_samples, int has_lens, RaggedUpload lens,
+                                                                   const double* __restrict__ gain, int64_t gain_stride) {
+    const int b = lens.offset + blockIdx.y;
+    const float* x = audio + (int64_t)b * stride;  // (out may be audio: every thread reads its own quad before it writes it)
+    float* y = out + (int64_t)b * out_stride;
+    const int64_t n = has_lens ? lens.vals[blockIdx.y] : max_samples;
+    const double g = gain[(int64_t)b * gain_stride];
+    const int64_t i0 = 4 * ((int64_t)blockIdx.x * LD_GAIN_THREADS + threadIdx.x);
+    if (i0 >= max_samples) return;
+    if (VEC && i0 + 4 <= max_samples) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i0 < n) v = *reinterpret_cast<const float4*>(x + i0);  // (a quad that starts inside the clip lies inside the row)
+        v.x = i0 < n ? (float)((double)v.x * g) : 0.f;
+        v.y = i0 + 1 < n ? (float)((double)v.y * g) : 0.f;
+        v.z = i0 + 2 < n ? (float)((double)v.z * g) : 0.f;
+        v.w = i0 + 3 < n ? (float)((double)v.w * g) : 0.f;
+        *reinterpret_cast<float4*>(y + i0) = v;
+        return;
+    }
+    for (int64_t i = i0; i < min(i0 + 4, max_samples); ++i) y[i] = i < n ? (float)((double)x[i] * g) : 0.f;
+}
+
+int filter_design(int32_t fs, LoudFilter* f) {
+    LD_REQUIRE_RATE(fs);
+    // De Man's parametrisation of the two K-weighting stages, evaluated at fs
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(M_PI * f0 / fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        f->c[0][0] = (Vh + Vb * K / Q + K * K) / a0;
+        f->c[0][1] = 2.0 * (K * K - Vh) / a0;
+        f->c[0][2] = (Vh - Vb * K / Q + K * K) / a0;
+        f->c[0][3] = 2.0 * (K * K - 1.0) / a0;
+        f->c[0][4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(M_PI * f0 / fs);
+        const double a0 = 1.0 + K / Q + K * K;
+        f->c[1][0] = 1.0;
+        f->c[1][1] = -2.0;
+        f->c[1][2] = 1.0;
+        f->c[1][3] = 2.0 * (K * K - 1.0) / a0;
+        f->c[1][4] = (1.0 - K / Q + K * K) / a0;
+    }
+    f->step = fs / 10;
+    // M: column k is where the unit state e_k is after one step of zero input, by the passes' own recursion on the fp64 coefficients,
+    // run in the host's long double (64 mantissa bits on x86) and kept as hi + lo; where long double is double, lo is zero
+    long double c[2][5];
+    for (int s = 0; s < 2; ++s)
+        for (int i = 0; i < 5; ++i) c[s][i] = f->c[s][i];
+    for (int k = 0; k < 4; ++k) {
+        long double st[4] = {0.0L, 0.0L, 0.0L, 0.0L};
+        st[k] = 1.0L;
+        for (int i = 0; i < f->step; ++i) biquad(c[1], biquad(c[0], 0.0L, st[0], st[1]), st[2], st[3]);
+        for (int r = 0; r < 4; ++r) {
+            f->m[r][k] = (double)st[r];
+            f->m_lo[r][k] = (double)(st[r] - (long double)f->m[r][k]);
+        }
+    }
+    return L3AC_OK;
+}
+
+}  // namespace
+
+int64_t loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) {
+    LoudFilter f;
+    L3AC_TRY(filter_design(sample_rate, &f));
+    const int64_t need = 2 * 6 + 16;
+    if (!out || cap < need) return need;
+    for (int s = 0; s < 2; ++s) {
+        double* row = out + 6 * s;
+        row[0] = f.c[s][0], row[1] = f.c[s][1], row[2] = f.c[s][2], row[3] = 1.0, row[4] = f.c[s][3], row[5] = f.c[s][4];
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) out[12 + 4 * r + k] = f.m[r][k];
+    return need;
+}
+
+int64_t loudness_blocks(int64_t samples, int32_t sample_rate) {
+    LD_REQUIRE_RATE(sample_rate);
+    L3AC_REQUIRE(samples >= 1, "loudness_blocks: samples %lld must be positive", (long long)samples);
+    return std::max<int64_t>(samples / (sample_rate / 10) - 3, 0);
+}
+
+int64_t loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
+    int64_t s_max;
+    LoudScratch sc;
+    L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
+    return sc.total_min;
+}
+
+int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                    int32_t sample_rate, double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes) {
+    int64_t s_max;
+    LoudScratch sc;
+    L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
+    L3AC_REQUIRE(audio && stats && counts, "loudness: null buffer");
+    L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "loudness: row stride %lld below max_samples %lld", (long long)audio_stride,
+                 (long long)max_samples);
+    L3AC_TRY(check_lengths(samples, batch, max_samples));
+    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "loudness: scratch must be a 256-byte aligned device buffer");
+    L3AC_REQUIRE(scratch_bytes >= sc.total_min, "loudness: scratch of %lld bytes is below l3ac_loudness_scratch_bytes = %lld",
+                 (long long)scratch_bytes, (long long)sc.total_min);
+    LoudFilter f;
+    L3AC_TRY(filter_design(sample_rate, &f));
+    char* base = static_cast<char*>(scratch);
+    int* lens = samples ? reinterpret_cast<int*>(base + sc.lens) : nullptr;
+    double* state = reinterpret_cast<double*>(base + sc.state);
+    double* energy = reinterpret_cast<double*>(base + sc.energy);
+    float* step_max = reinterpret_cast<float*>(base + sc.step_max);
+    const int64_t j_max = std::max<int64_t>(s_max - 3, 0);
+
+    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
+    if (s_max > 0) {
+        const dim3 grid((unsigned)ceil_div64(s_max, LD_STEPS), (unsigned)batch);
+        const double flops = 22.0 * batch * (double)max_samples, bytes = 4.0 * batch * (double)max_samples;
+        {
+            ProfScope prof(s, "loudness_pass_kernel<state>", flops, bytes);
+            hipLaunchKernelGGL(loudness_pass_kernel<false>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
+                               step_max);
+            L3AC_LAUNCH_CHECK();
+        }
+        {
+            ProfScope prof(s, "loudness_scan_kernel", 32.0 * batch * (double)s_max, 64.0 * batch * (double)s_max);
+            hipLaunchKernelGGL(loudness_scan_kernel, dim3((unsigned)ceil_div64(batch, 64)), dim3(64), 0, s, batch, max_samples, lens, f, s_max, state);
+            L3AC_LAUNCH_CHECK();
+        }
+        {
+            ProfScope prof(s, "loudness_pass_kernel<energy>", flops, bytes);
+            hipLaunchKernelGGL(loudness_pass_kernel<true>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
+                               step_max);
+            L3AC_LAUNCH_CHECK();
+        }
+    }
+    ProfScope prof(s, "loudness_gate_kernel", 0.0, 12.0 * batch * (double)s_max);
+    hipLaunchKernelGGL(loudness_gate_kernel, dim3((unsigned)batch), dim3(LD_GATE_THREADS), 0, s, audio, audio_stride, max_samples, lens, f.step, s_max,
+                       j_max, energy, step_max, stats, counts, j_max > 0 ? momentary : nullptr);
+    L3AC_LAUNCH_CHECK();
+    return L3AC_OK;
+}
+
+int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain) {
+    L3AC_REQUIRE(batch > 0 && batch <= 65535, "loudness_gain: batch %d outside 1..65535", batch);
+    L3AC_REQUIRE(std::isfinite(target_lufs), "loudness_gain: target_lufs must be finite");
+    L3AC_REQUIRE(stats && gain, "loudness_gain: null buffer");
+    const bool has_limit = !std::isnan(peak_limit_db);
+    ProfScope prof(s, "loudness_gain_kernel", 0.0, 32.0 * batch);
+    hipLaunchKernelGGL(loudness_gain_kernel, dim3((unsigned)ceil_div64(batch, LD_GAIN_THREADS)), dim3(LD_GAIN_THREADS), 0, s, stats, batch, target_lufs,
+                       has_limit ? peak_limit_db : 0.0, has_limit ? 1 : 0, gain);
+    L3AC_LAUNCH_CHECK();
+    return L3AC_OK;
+}
+
+int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, const double* gain, int64_t gain_stride) {
+    L3AC_REQUIRE(batch > 0 && batch <= 65535, "apply_gain: batch %d outside 1..65535", batch);
+    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "apply_gain: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
+    L3AC_REQUIRE(audio && out && gain, "apply_gain: null buffer");
+    L3AC_REQUIRE(batch == 1 || (audio_stride >= max_samples && out_stride >= max_samples), "apply_gain: row stride below max_samples %lld",
+                 (long long)max_samples);
+    L3AC_REQUIRE(gain_stride >= 1, "apply_gain: gain_stride %lld must be positive", (long long)gain_stride);
+    L3AC_TRY(check_lengths(samples, batch, max_samples));
+    const bool vec = (((uintptr_t)audio | (uintptr_t)out) & 15) == 0 && (batch == 1 || ((audio_stride | out_stride) & 3) == 0);
+    const int group = samples ? RaggedUpload::CAP : batch;  // without lengths one launch takes the whole batch
+    for (int off = 0; off < batch; off += group) {
+        RaggedUpload blk{};
+        blk.offset = off;
+        blk.n = std::min(group, batch - off);
+        for (int i = 0; samples && i < blk.n; ++i) blk.vals[i] = samples[off + i];
+        const dim3 grid((unsigned)ceil_div64(ceil_div64(max_samples, 4), LD_GAIN_THREADS), (unsigned)blk.n);
+        ProfScope prof(s, "apply_gain_kernel", 1.0 * blk.n * (double)max_samples, 8.0 * blk.n * (double)max_samples);
+        if (vec)
+            hipLaunchKernelGGL(apply_gain_kernel<true>, grid, dim3(LD_GAIN_THREADS), 0, s, audio, audio_stride, out, out_stride, max_samples,
+                               samples ? 1 : 0, blk, gain, gain_stride);
+        else
+            hipLaunchKernelGGL(apply_gain_kernel<false>, grid, dim3(LD_GAIN_THREADS), 0, s, audio, audio_stride, out, out_stride, max_samples,
+                               samples ? 1 : 0, blk, gain, gain_stride);
+        L3AC_LAUNCH_CHECK();
+    }
+    return L3AC_OK;
+}

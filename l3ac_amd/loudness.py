@@ -1,0 +1,165 @@
+"""Loudness on the GPU (csrc/kernels/loudness.hip): ITU-R BS.1770-4 integrated loudness of mono clips
+(``loudness``), the gain to a target (``loudness_gain``), its application (``apply_gain``) and the three composed
+(``normalize_loudness``); and the host accessors of the K-weighting design."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from . import _capi
+from ._rows import row_stride
+from .metrics import _audio, _lengths
+
+
+def loudness_coeffs(sample_rate: int):
+    """The library's K-weighting at ``sample_rate`` -> ``(sos (2, 6), M (4, 4))`` fp64 on the CPU: the two biquads as rows
+    ``b0 b1 b2 a0 a1 a2`` (``scipy.signal.sosfilt``'s layout), and the matrix that advances the cascade's state over one 100 ms step of
+    zero input.  Raises ValueError for an unsupported rate (a multiple of 10 in 8000..192000 is supported)."""
+    lib = _capi.load_library()
+    n = lib.l3ac_loudness_coeffs(int(sample_rate), None, 0)
+    if n < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    host = torch.empty(n, dtype=torch.float64)
+    lib.l3ac_loudness_coeffs(int(sample_rate), host.data_ptr(), n)
+    return host[:12].view(2, 6).clone(), host[12:].view(4, 4).clone()
+
+
+def loudness_blocks(samples: int, sample_rate: int) -> int:
+    """Gating blocks (400 ms, every 100 ms) of a clip of ``samples`` samples: ``max(samples // (sample_rate // 10) - 3, 0)``.  Raises
+    ValueError for samples < 1 or an unsupported rate."""
+    lib = _capi.load_library()
+    n = lib.l3ac_loudness_blocks(int(samples), int(sample_rate))
+    if n < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    return int(n)
+
+
+def _check_rate(sample_rate: int) -> None:
+    lib = _capi.load_library()
+    if lib.l3ac_loudness_blocks(1, sample_rate) < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+
+
+def _finite(value, what: str) -> float:
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number") from None
+    if not math.isfinite(value):
+        raise ValueError(f"{what} must be finite, got {value}")
+    return value
+
+
+def _limit(peak_limit_db) -> float:
+    """``peak_limit_db=`` as the library takes it: NaN for none."""
+    if peak_limit_db is None:
+        return math.nan
+    value = float(peak_limit_db)
+    if math.isnan(value):
+        raise ValueError("peak_limit_db must be a number of dB or None")
+    return value
+
+
+@torch.no_grad()
+def loudness(audio: torch.Tensor, sample_rate: int = 16000, lengths=None, return_momentary: bool = False) -> dict:
+    """ITU-R BS.1770-4 integrated loudness of (B, T) fp32 CUDA mono clips, in fp64 -> ``{"lufs": (B,) fp64, "peak": (B,) fp64,
+    "blocks": (B,) int32, "gated": (B,) int32}``, all on the device.  K-weighting by De Man's closed forms evaluated at ``sample_rate``
+    (the standard's table at 48 kHz; the choice ``pyloudnorm`` makes elsewhere), blocks of 400 ms every 100 ms, the absolute gate at
+    -70 LKFS and the relative gate 10 LU below.  ``sample_rate``: a multiple of 10 in 8000..192000.  ``blocks`` is the clip's number of
+    blocks, ``gated`` how many pass both gates; ``lufs`` is -inf exactly when none does (clips below 400 ms and digital silence
+    included).  ``peak`` is the sample peak ``max |x|`` over the clip's own samples (not the true peak).  ``lengths``: B ints in 1..T;
+    samples at or after a clip's length are ignored, whatever they hold.  ``return_momentary`` adds ``"momentary"``: (B,
+    loudness_blocks(T)) fp64, the blocks' own loudness, -inf at and after a clip's own blocks.  A clip's bits do not depend on the batch
+    it is in.  No table is uploaded: the call can be captured without a warm-up.  No CPU path: CPU tensors raise."""
+    sample_rate = int(sample_rate)
+    _check_rate(sample_rate)
+    x = _audio(audio, "loudness")
+    b, t = x.shape
+    lens, c_lens = _lengths(lengths, b, t)
+    dev = x.device
+    lib = _capi.load_library()
+    need = lib.l3ac_loudness_scratch_bytes(b, t, sample_rate)
+    if need < 0:
+        raise ValueError(lib.l3ac_last_error().decode())
+    stats = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    counts = torch.empty((b, 2), dtype=torch.int32, device=dev)
+    momentary = torch.empty((b, loudness_blocks(t, sample_rate)), dtype=torch.float64, device=dev) if return_momentary else None
+    with torch.cuda.device(dev):
+        scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)  # (the caching allocator hands out 512-byte aligned blocks)
+        _capi.check(lib.l3ac_loudness(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, stats.data_ptr(), counts.data_ptr(),
+                                      momentary.data_ptr() if return_momentary and momentary.numel() else None, scratch.data_ptr(),
+                                      scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    out = {"lufs": stats[:, 0].contiguous(), "peak": stats[:, 1].contiguous(), "blocks": counts[:, 0].contiguous(),
+           "gated": counts[:, 1].contiguous()}
+    if return_momentary:
+        out["momentary"] = momentary
+    return out
+
+
+def _stat(stats: dict, key: str) -> torch.Tensor:
+    v = stats.get(key) if isinstance(stats, dict) else None
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        raise RuntimeError(f"loudness_gain needs a CUDA tensor stats[{key!r}] (what loudness returns): l3ac_amd has no CPU path")
+    if v.dim() != 1 or v.shape[0] == 0:
+        raise ValueError(f"stats[{key!r}] must be (batch,), got {tuple(v.shape)}")
+    return v.to(torch.float64)
+
+
+@torch.no_grad()
+def loudness_gain(stats: dict, target_lufs: float = -23.0, peak_limit_db: Optional[float] = None) -> dict:
+    """What ``loudness`` returned -> ``{"gain_db": (B,) fp64, "gain": (B,) fp64}`` on the device, without a host synchronisation:
+    ``gain_db = target_lufs - lufs``; with ``peak_limit_db`` and a non-zero peak at most ``peak_limit_db - 20 log10(peak)``, so that the
+    scaled clip's sample peak stays at or below the limit; exactly 0 dB for a clip whose loudness is -inf.  ``gain = 10^(gain_db / 20)``."""
+    target = _finite(target_lufs, "target_lufs")
+    limit = _limit(peak_limit_db)
+    lufs, peak = _stat(stats, "lufs"), _stat(stats, "peak")
+    if lufs.shape != peak.shape or lufs.device != peak.device:
+        raise ValueError("stats['lufs'] and stats['peak'] differ in shape or device")
+    b = lufs.shape[0]
+    dev = lufs.device
+    packed = torch.stack((lufs, peak), dim=1).contiguous()
+    gain = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.load_library().l3ac_loudness_gain(packed.data_ptr(), b, target, limit, gain.data_ptr(),
+                                                            torch.cuda.current_stream(dev).cuda_stream))
+    return {"gain_db": gain[:, 0].contiguous(), "gain": gain[:, 1].contiguous()}
+
+
+@torch.no_grad()
+def apply_gain(audio: torch.Tensor, gain: torch.Tensor, lengths=None) -> torch.Tensor:
+    """(B, T) fp32 CUDA audio times a per-clip linear ``gain`` (B,) fp64 CUDA (``loudness_gain(...)["gain"]``, or its reciprocal to
+    undo it after decoding) -> a new (B, T) fp32: ``float(double(x) * gain)``, one rounding.  ``lengths``: samples at or after a clip's
+    length come out as zero."""
+    x = _audio(audio, "apply_gain")
+    b, t = x.shape
+    if not isinstance(gain, torch.Tensor) or not gain.is_cuda:
+        raise RuntimeError("apply_gain needs a CUDA tensor gain: l3ac_amd has no CPU path")
+    if gain.shape != (b,):
+        raise ValueError(f"gain must be ({b},), got {tuple(gain.shape)}")
+    if gain.device != x.device:
+        raise RuntimeError(f"apply_gain: audio is on {x.device} but gain is on {gain.device}")
+    lens, c_lens = _lengths(lengths, b, t)
+    g = gain.to(torch.float64)
+    out = torch.empty((b, t), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.load_library().l3ac_apply_gain(x.data_ptr(), row_stride(x), out.data_ptr(), row_stride(out), b, t, c_lens, g.data_ptr(),
+                                                         g.stride(0) if b > 1 else 1, torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+@torch.no_grad()
+def normalize_loudness(audio: torch.Tensor, target_lufs: float = -23.0, sample_rate: int = 16000, lengths=None,
+                       peak_limit_db: Optional[float] = -1.0):
+    """(B, T) fp32 CUDA audio brought to ``target_lufs`` -> ``(audio_out, {"lufs", "peak", "gain_db", "gain"})``: ``loudness``,
+    ``loudness_gain`` and ``apply_gain`` composed, bit for bit.  ``lufs`` and ``peak`` are the INPUT's.  The gain never reaches the host;
+    hand ``1 / info["gain"]`` to ``apply_gain`` after decoding to restore the level.  ``peak_limit_db=None``: no peak limit."""
+    sample_rate = int(sample_rate)
+    _check_rate(sample_rate)
+    _finite(target_lufs, "target_lufs")
+    _limit(peak_limit_db)
+    stats = loudness(audio, sample_rate=sample_rate, lengths=lengths)
+    gain = loudness_gain(stats, target_lufs=target_lufs, peak_limit_db=peak_limit_db)
+    out = apply_gain(audio, gain["gain"], lengths=lengths)
+    return out, {"lufs": stats["lufs"], "peak": stats["peak"], "gain_db": gain["gain_db"], "gain": gain["gain"]}
