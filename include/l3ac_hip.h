@@ -492,6 +492,39 @@ int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, d
 int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
                     const int32_t* samples, const double* gain, int64_t gain_stride, void* stream);
 
+/* ---- pitch: YIN F0 tracking and the pairwise F0 metrics (which states every formula) ------------------------------
+ * A deterministic YIN tracker (de Cheveigne & Kawahara 2002, steps 1-5) of MONO clips.  Parameters: sample_rate fs, fmin, fmax, window W
+ * (-1: tau_max), hop (-1: fs / 100), threshold.  tau_min = floor(fs / fmax), tau_max = ceil(fs / fmin), T = tau_max + 1, span = W + T.
+ * Supported iff 8000 <= fs <= 192000, 0 < fmin < fmax <= fs / 4, tau_max > tau_min, hop >= 1, W >= 1, 0 < threshold < 1 and span <= 4000
+ * (one frame's samples with its d and c rows in 64,000 bytes of LDS).  A clip of n samples has F(n) = 0 frames for n < span, else
+ * 1 + (n - span) / hop; frame t reads samples [t hop, t hop + span) and nothing else (no padding, no centring).  The difference function
+ * d(tau), tau = 0 .. T, is summed in fp32 in the direct form; the cumulative-mean-normalised c(tau), the pick, the parabolic refinement
+ * and f0 = fs / (tau* + shift) are fp64.
+ *   l3ac_pitch_lags:          HOST only: out[0..4] = tau_min, tau_max, W, hop, span, the defaults resolved.
+ *   l3ac_pitch_frames:        HOST only: F(samples); < 0 for samples < 0 or unsupported parameters.
+ *   l3ac_pitch_scratch_bytes: the minimum scratch of l3ac_pitch for these shapes; < 0 for batch outside 1..65535, max_samples outside
+ *                             1..2^31 - 1 or unsupported parameters.
+ *   l3ac_pitch:               audio [batch][audio_stride] (`samples`: HOST array of batch lengths in 1..max_samples, or NULL) -> f0
+ *                             [batch][F(max_samples)] fp64 in Hz, voiced [batch][F(max_samples)] int32 (1: a lag fell below the threshold),
+ *                             aperiodicity [batch][F(max_samples)] fp64 = c(tau*); rows at and after a clip's own F hold NaN / 0 / NaN.
+ *                             cmnd (or NULL) [batch][F(max_samples)][T + 1] fp64 = c, NaN rows after a clip's own F.  frames (or NULL)
+ *                             [batch] int32 = the clips' F.  All outputs are device buffers.
+ *   l3ac_pitch_metrics:       two tracks of equal geometry, as written by l3ac_pitch, [batch][max_frames] each (`frames`: HOST array of
+ *                             batch frame counts in 0..max_frames, or NULL) -> out [batch][4] fp64 = f0_rmse_cents, gpe, vde, ffe; counts
+ *                             [batch][4] int32 = frames, voiced_ref, voiced_est, voiced_both.  A ratio whose denominator is 0 is NaN.
+ * Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee and calling convention: as the
+ * quality metrics above (a clip's results do not depend on the batch, its row, the stride, the scratch size or what lies after its
+ * length; no atomics; enqueue only, nothing allocated, no synchronisation, capturable).  There is no device table: nothing needs a
+ * warm-up before a capture.  Non-finite samples leave the frames that read them unspecified and disturb nothing else. */
+int l3ac_pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out);
+int64_t l3ac_pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);
+int64_t l3ac_pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);
+int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+               double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced, double* aperiodicity,
+               double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
+                       int64_t max_frames, const int32_t* frames, double* out, int32_t* counts, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

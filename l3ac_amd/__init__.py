@@ -41,6 +41,7 @@ from .metrics import (DEFAULT_SCALES, _check_params as _check_metric_params, _sc
                       signal_metrics, stft, stft_basis, stft_frames, stoi, stoi_bands, stoi_basis, stoi_frames)
 from .loudness import (_check_rate as _check_loudness_rate, apply_gain, loudness, loudness as _loudness, loudness_blocks, loudness_coeffs, loudness_gain,
                        normalize_loudness)
+from .pitch import _check_params as _check_pitch_params, pitch, pitch_frames, pitch_lags, pitch_metrics, pitch_metrics as _pitch_metrics
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -52,7 +53,7 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "StreamResampler", "stream_resampler", "StreamPacker", "StreamUnpacker", "stream_packer", "stream_unpacker", "packed_bytes", "pack_advance",
            "unpack_advance", "frame_header", "parse_frame", "stft", "log_mel", "mel_distance", "signal_metrics", "stft_frames", "stft_basis",
            "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands", "loudness", "loudness_gain", "apply_gain",
-           "normalize_loudness", "loudness_coeffs", "loudness_blocks"]
+           "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -541,7 +542,8 @@ class L3AC:
     # ---- quality of the round trip (l3ac_amd/metrics.py) ---------------------------------------
     @torch.no_grad()
     def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
-                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False) -> dict:
+                 prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False,
+                 pitch: bool = False) -> dict:
         """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
         and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
         ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
@@ -549,8 +551,12 @@ class L3AC:
         ``bits_per_token * tokens / seconds``).  ``intelligibility=True`` adds ``"stoi"``, ``"estoi"`` and ``"stoi_frames"``: ``stoi``
         of the same pairs at the codec's rate.  ``loudness=True`` adds ``"loudness_reference"``,
         ``"loudness_decoded"`` and ``"loudness_shift"`` (decoded - reference, in LU): ``l3ac_amd.loudness`` of each side at the codec's
-        rate (section 3.14).  Every value equals composing those public calls by hand, bit for bit."""
+        rate (section 3.14).  ``pitch=True`` adds ``"f0_rmse_cents"``, ``"gpe"``, ``"vde"``, ``"ffe"``, ``"pitch_frames"`` and
+        ``"pitch_voiced"`` (the frames voiced on both sides): ``l3ac_amd.pitch_metrics`` of the same pairs at the codec's rate with its
+        default parameters (section 3.15).  Every value equals composing those public calls by hand, bit for bit."""
         scales = _metric_scales(scales)
+        if pitch:  # a rate the tracker's defaults do not fit raises before any device work
+            _check_pitch_params(self.config.sample_rate)
         if loudness:  # a rate the K-weighting is not defined for raises before any device work
             _check_loudness_rate(self.config.sample_rate)
         if intelligibility and self.config.sample_rate != 10000:  # a rate that cannot be taken to 10 kHz raises before any device work
@@ -575,6 +581,10 @@ class L3AC:
             l_ref = _loudness(reference, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
             l_dec = _loudness(decoded, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
             out.update({"loudness_reference": l_ref, "loudness_decoded": l_dec, "loudness_shift": l_dec - l_ref})
+        if pitch:
+            pm = _pitch_metrics(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
+            out.update({"f0_rmse_cents": pm["f0_rmse_cents"], "gpe": pm["gpe"], "vde": pm["vde"], "ffe": pm["ffe"], "pitch_frames": pm["frames"],
+                        "pitch_voiced": pm["voiced_both"]})
         tokens = info["lengths"]
         seconds = torch.tensor(lens, dtype=torch.float64) / self.config.sample_rate
         out["tokens"] = tokens

@@ -162,6 +162,12 @@ SIGNATURES = {
     "l3ac_loudness": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _P, _I64, _P]),
     "l3ac_loudness_gain": (C.c_int, [_P, _I32, C.c_double, C.c_double, _P, _P]),
     "l3ac_apply_gain": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _I64, _P]),
+    "l3ac_pitch_lags": (C.c_int, [_I32, C.c_double, C.c_double, _I32, _I32, C.POINTER(_I32)]),
+    "l3ac_pitch_frames": (_I64, [_I64, _I32, C.c_double, C.c_double, _I32, _I32]),
+    "l3ac_pitch_scratch_bytes": (_I64, [_I32, _I64, _I32, C.c_double, C.c_double, _I32, _I32]),
+    "l3ac_pitch": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, C.c_double, _I32, _I32, C.c_double, _P, _P, _P, _P, _P, _P,
+                             _I64, _P]),
+    "l3ac_pitch_metrics": (C.c_int, [_P, _P, _P, _P, _I32, _I64, C.POINTER(_I32), _P, _P, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

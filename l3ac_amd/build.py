@@ -50,6 +50,7 @@ SOURCES = [
     "kernels/metrics.hip",
     "kernels/stoi.hip",
     "kernels/loudness.hip",
+    "kernels/pitch.hip",
 ]
 
 

@@ -865,6 +865,31 @@ int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_
     return launch_apply_gain((hipStream_t)stream, audio, audio_stride, out, out_stride, batch, max_samples, samples, gain, gain_stride);
 }
 
+// ---- pitch ------------------------------------------------------------------------------
+int l3ac_pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out) {
+    return pitch_lags(sample_rate, fmin, fmax, window, hop, out);
+}
+
+int64_t l3ac_pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
+    return pitch_frames(samples, sample_rate, fmin, fmax, window, hop);
+}
+
+int64_t l3ac_pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
+    return pitch_scratch_bytes(batch, max_samples, sample_rate, fmin, fmax, window, hop);
+}
+
+int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+               double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced, double* aperiodicity,
+               double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_pitch((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, fmin, fmax, window, hop, threshold, f0,
+                        voiced, aperiodicity, cmnd, frames, scratch, scratch_bytes);
+}
+
+int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
+                       int64_t max_frames, const int32_t* frames, double* out, int32_t* counts, void* stream) {
+    return launch_pitch_metrics((hipStream_t)stream, f0_ref, voiced_ref, f0_est, voiced_est, batch, max_frames, frames, out, counts);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

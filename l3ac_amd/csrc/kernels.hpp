@@ -290,6 +290,16 @@ int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int
 int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain);
 int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
                       const int32_t* samples, const double* gain, int64_t gain_stride);
+// pitch (kernels/pitch.hip; include/l3ac_hip.h "pitch"): YIN over groups of frames staged in LDS (fp32 difference
+// function, one lane per lag; fp64 from the prefix on), and the pairwise F0 metrics; window / hop -1: the defaults
+int pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out);  // HOST: tau_min tau_max W hop span
+int64_t pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);  // HOST: F(samples)
+int64_t pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);
+int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                 int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced,
+                 double* aperiodicity, double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes);
+int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
+                         int64_t max_frames, const int32_t* frames, double* out, int32_t* counts);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)
