@@ -525,6 +525,36 @@ int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t 
 int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
                        int64_t max_frames, const int32_t* frames, double* out, int32_t* counts, void* stream);
 
+/* ---- time alignment: cross-correlation delay, polarity and shift of clip pairs (which states every formula) ------
+ * A pair ref, est of fp32 rows with a common per-clip length n, and a lag range L = max_lag, 0 <= L <= 16384.  For d = -L .. L,
+ * r(d) = sum_j ref[j] est[j + d] over the j with 0 <= j < n and 0 <= j + d < n (an empty overlap gives exactly 0): a positive d means the
+ * estimate is late by d samples.  r is computed per segment of 4096 samples as a matrix product on the fp32 matrix pipe (an fp32 fmaf
+ * chain over 128 terms in a fixed order) and from there in fp64 in a fixed order; the energies E_ref, E_est are fp64 sums of exact
+ * squares.  lag d* maximises |r(d)| (ties: the smaller |d|, then the smaller d); polarity = -1 where r(d*) < 0, else +1; correlation =
+ * r(d*) / sqrt(E_ref E_est); delay = d* + the vertex of the parabola through s r(d* - 1), s r(d*), s r(d* + 1), s = polarity, where
+ * -L < d* < L and the parabola opens downwards, else d*.  E_ref E_est = 0 gives lag 0, polarity 0, delay 0 and correlation NaN.
+ *   l3ac_xcorr_scratch_bytes: the minimum scratch of l3ac_xcorr for these shapes, 256 ceil(4 batch / 256) + 8 batch ceil(max_samples / 4096)
+ *                             (2 max_lag + 1) bytes; < 0 for batch outside 1..65535, max_samples outside 1..2^31 - 1 or max_lag outside
+ *                             0..16384.  With max_lag = 0 it covers l3ac_align_apply, which needs the first term only.
+ *   l3ac_xcorr:               ref [batch][ref_stride], est [batch][est_stride] (`samples`: HOST array of batch lengths in 1..max_samples, or
+ *                             NULL) -> lag [batch] int32, polarity [batch] int32, delay [batch] fp64, correlation [batch] fp64, and
+ *                             xcorr (or NULL) [batch][2 max_lag + 1] fp64 = r(-L) .. r(L).  All outputs are device buffers.
+ *   l3ac_align_apply:         lag [batch] int32 is a DEVICE buffer (any values).  With m = max(0, n - |d|): out_ref[j] = ref[j + max(0, -d)]
+ *                             and out_est[j] = est[j + max(0, d)] for j < m, exact zeros for m <= j < max_samples; out_samples [batch]
+ *                             int32 (device) = m.  The outputs must not overlap the inputs.  polarity is not applied.
+ * Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee and calling convention: as the
+ * quality metrics above (a clip's results do not depend on the batch, its row, the stride, the scratch size or what lies after its
+ * length; no atomics; enqueue only, nothing allocated, no synchronisation, capturable).  There is no device table: nothing needs a
+ * warm-up before a capture.  Non-finite samples inside a clip leave that clip's results unspecified (its lag stays inside [-L, L]) and
+ * disturb nothing else. */
+int64_t l3ac_xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag);
+int l3ac_xcorr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+               int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr, void* scratch,
+               int64_t scratch_bytes, void* stream);
+int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
+                     int32_t* out_samples, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -42,6 +42,7 @@ from .metrics import (DEFAULT_SCALES, _check_params as _check_metric_params, _sc
 from .loudness import (_check_rate as _check_loudness_rate, apply_gain, loudness, loudness as _loudness, loudness_blocks, loudness_coeffs, loudness_gain,
                        normalize_loudness)
 from .pitch import _check_params as _check_pitch_params, pitch, pitch_frames, pitch_lags, pitch_metrics, pitch_metrics as _pitch_metrics
+from .align import align, apply_delay, delay
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -53,7 +54,8 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "StreamResampler", "stream_resampler", "StreamPacker", "StreamUnpacker", "stream_packer", "stream_unpacker", "packed_bytes", "pack_advance",
            "unpack_advance", "frame_header", "parse_frame", "stft", "log_mel", "mel_distance", "signal_metrics", "stft_frames", "stft_basis",
            "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands", "loudness", "loudness_gain", "apply_gain",
-           "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags"]
+           "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags", "delay",
+           "apply_delay", "align"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")

@@ -168,6 +168,9 @@ SIGNATURES = {
     "l3ac_pitch": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, C.c_double, _I32, _I32, C.c_double, _P, _P, _P, _P, _P, _P,
                              _I64, _P]),
     "l3ac_pitch_metrics": (C.c_int, [_P, _P, _P, _P, _I32, _I64, C.POINTER(_I32), _P, _P, _P]),
+    "l3ac_xcorr_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_xcorr": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_align_apply": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _P, _I64, _P, _I64, _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

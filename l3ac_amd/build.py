@@ -51,6 +51,7 @@ SOURCES = [
     "kernels/stoi.hip",
     "kernels/loudness.hip",
     "kernels/pitch.hip",
+    "kernels/align.hip",
 ]
 
 

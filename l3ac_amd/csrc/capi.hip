@@ -890,6 +890,23 @@ int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const do
     return launch_pitch_metrics((hipStream_t)stream, f0_ref, voiced_ref, f0_est, voiced_est, batch, max_frames, frames, out, counts);
 }
 
+// ---- time alignment -----------------------------------------------------------------------
+int64_t l3ac_xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag) { return xcorr_scratch_bytes(batch, max_samples, max_lag); }
+
+int l3ac_xcorr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+               int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr, void* scratch,
+               int64_t scratch_bytes, void* stream) {
+    return launch_xcorr((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, max_lag, lag, polarity, delay, correlation,
+                        xcorr, scratch, scratch_bytes);
+}
+
+int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
+                     int32_t* out_samples, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_align_apply((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, lag, out_ref, out_ref_stride, out_est,
+                              out_est_stride, out_samples, scratch, scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

@@ -300,6 +300,16 @@ int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_
                  double* aperiodicity, double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes);
 int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
                          int64_t max_frames, const int32_t* frames, double* out, int32_t* counts);
+// time alignment (kernels/align.hip; include/l3ac_hip.h "time alignment"): the cross-correlation of clip pairs over
+// lags -max_lag .. max_lag as a GEMM on the fp32 matrix pipe with fp64 diagonal sums, the pick of lag / polarity / delay / correlation,
+// and the shift by per-clip lags read from device memory
+int64_t xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag);
+int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                 const int32_t* samples, int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr,
+                 void* scratch, int64_t scratch_bytes);
+int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                       const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
+                       int32_t* out_samples, void* scratch, int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -115,7 +115,7 @@ def pitch_metrics(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: 
     voicing decision error ``vde`` (frames voiced on one side only / frames), the gross pitch error ``gpe`` (frames voiced on both
     sides whose f0 differ by more than 20 % / frames voiced on both), the F0 frame error ``ffe`` (either / frames) and the RMS of
     ``1200 log2(f_estimate / f_reference)`` over the frames voiced on both sides, in fp64 in a fixed order.  A ratio whose denominator
-    is zero is NaN.  There is no time alignment of the pair.  ``lengths``: the pairs' common lengths.  Parameters as ``pitch``."""
+    is zero is NaN.  There is no time alignment of the pair (``align`` makes one first).  ``lengths``: the pairs' common lengths.  Parameters as ``pitch``."""
     args, threshold, lags = _check_params(sample_rate, fmin, fmax, threshold, hop, window)
     r, e = _pair(reference, estimate, "pitch_metrics")
     b, t = r.shape
