@@ -555,6 +555,51 @@ int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int
                      const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
                      int32_t* out_samples, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- mel-cepstral distortion along a dynamic-time-warping path (which states every formula) -----------------------
+ * Cepstra: c[f][q] = sum_m D[q][m] L[f][m], q = 0 .. K = n_coeffs, where L are exactly the fp32 cells of l3ac_log_mel for the same
+ * arguments (M = n_mels of them per frame) and D is the orthonormal DCT-II, D[0][m] = sqrt(1 / M), D[q][m] = sqrt(2 / M) cos(pi q (m + 1/2)
+ * / M), designed in fp64 with the phase q (2m + 1) mod 4M reduced in integers and rounded once to fp32.  Each c[f][q] is one fp32 fmaf
+ * chain over m = 0 .. M - 1 in increasing m from +0.  n_coeffs in 1..min(n_mels - 1, 64); the other parameters as l3ac_log_mel.
+ * DTW: a pair of feature sequences a [Fa][dim], b [Fb][dim] (fp32; Fa, Fb in 1..4096, dim in 1..64).  delta(i, j) = sqrt(sum_q (a[i][q] -
+ * b[j][q])^2) in fp64 from the fp32 values, difference, square and sum in the order of q, no contraction.  Dacc[0][0] = delta(0, 0),
+ * Dacc[i][j] = delta(i, j) + min(Dacc[i-1][j-1], Dacc[i-1][j], Dacc[i][j-1]) over the predecessors inside the matrix, ties to the
+ * diagonal, then to (i-1, j), then to (i, j-1): one fp64 addition per cell.  The path is the backtrace of these choices from (Fa-1, Fb-1),
+ * reported from (0, 0) forward; its length P lies in max(Fa, Fb) .. Fa + Fb - 1; cost = Dacc[Fa-1][Fb-1], the sequential fp64 sum of
+ * delta along the path.  With diagonal_only (every pair's Fa = Fb = F): cost = sum_f delta(f, f) in the order of f, P = F, the path
+ * is (f, f).  The mel-cepstral distortion of a pair is 5 sqrt(2) cost / P dB on the cepstra q = 1 .. K (l3ac_amd/mcd.py).
+ *   l3ac_dct_table:          HOST only: D as [n_coeffs + 1][n_mels] floats; same protocol as l3ac_mel_weights (returns the float count;
+ *                            nothing is written when out is NULL or cap is below it; < 0 for unsupported parameters).
+ *   l3ac_mfcc_scratch_bytes: the minimum scratch of l3ac_mfcc: 256 ceil(4 batch / 256) + 256 ceil(4 batch F(max_samples) n_mels / 256) +
+ *                            l3ac_mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels); < 0 for unsupported parameters.
+ *   l3ac_mfcc:               l3ac_log_mel's arguments, then `dct` (the DEVICE copy of l3ac_dct_table's output) and n_coeffs -> out
+ *                            [batch][F(max_samples)][n_coeffs + 1] fp32 (device); the rows after a clip's own F(n) frames are zero.
+ *                            A larger scratch lets log_mel take more frames per product; the bits do not depend on it.
+ *   l3ac_dtw_scratch_bytes:  the minimum scratch of l3ac_dtw: 2 * 256 ceil(4 batch / 256) + 256 ceil(batch max_frames_a max_frames_b /
+ *                            256) bytes (the two sides' frame counts, one choice byte per cell); < 0 for batch outside 1..65535 or a
+ *                            max_frames outside 1..4096.
+ *   l3ac_dtw:                a: pair p's frame i at a + p a_row_stride + i a_frame_stride, dim floats; b alike.  The strides count floats
+ *                            (a_frame_stride >= dim, a_row_stride >= (max_frames_a - 1) a_frame_stride + dim), so a view that skips
+ *                            a leading coefficient needs no copy.  frames_a, frames_b: HOST arrays of batch counts in 1..max_frames_a /
+ *                            1..max_frames_b, or NULL (every pair has the maximum).  -> cost [batch] fp64, path_len [batch] int32, path
+ *                            (or NULL) [batch][max_frames_a + max_frames_b - 1][2] int32 = (i, j) from (0, 0) forward, -1 after P, and
+ *                            delta (or NULL; a test hook) [batch][max_frames_a][max_frames_b] fp64, of which the cells the call
+ *                            evaluates are written (all Fa x Fb of a pair, with diagonal_only its diagonal) and nothing else.  All
+ *                            outputs are device buffers.  diagonal_only with unequal counts in a pair is L3AC_EINVAL.
+ * Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee and calling convention: as the
+ * quality metrics above (a pair's results depend on its own frames only — not on the batch, its row, the strides, the scratch size or
+ * what lies at or after its frame counts, which is never read; no atomics; enqueue only, nothing allocated, no synchronisation,
+ * capturable).  l3ac_dtw has no device table: nothing needs a warm-up before a capture.  A non-finite feature inside a pair leaves that
+ * pair's results unspecified (its path stays inside its matrix) and disturbs nothing else. */
+int64_t l3ac_dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap);
+int64_t l3ac_mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs);
+int l3ac_mfcc(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
+              int64_t scratch_bytes, void* stream);
+int64_t l3ac_dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b);
+int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride, int32_t batch,
+             int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b, int32_t diagonal_only,
+             double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

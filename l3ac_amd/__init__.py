@@ -43,6 +43,7 @@ from .loudness import (_check_rate as _check_loudness_rate, apply_gain, loudness
                        normalize_loudness)
 from .pitch import _check_params as _check_pitch_params, pitch, pitch_frames, pitch_lags, pitch_metrics, pitch_metrics as _pitch_metrics
 from .align import align, apply_delay, delay
+from .mcd import _check_mfcc_params, _mfcc_hop, dct_table, dtw, mcd, mcd as _mcd, mfcc
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -55,7 +56,7 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "unpack_advance", "frame_header", "parse_frame", "stft", "log_mel", "mel_distance", "signal_metrics", "stft_frames", "stft_basis",
            "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands", "loudness", "loudness_gain", "apply_gain",
            "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags", "delay",
-           "apply_delay", "align"]
+           "apply_delay", "align", "mfcc", "dtw", "mcd", "dct_table"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -545,7 +546,7 @@ class L3AC:
     @torch.no_grad()
     def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
                  prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False,
-                 pitch: bool = False) -> dict:
+                 pitch: bool = False, mcd: bool = False) -> dict:
         """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
         and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
         ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
@@ -555,8 +556,17 @@ class L3AC:
         ``"loudness_decoded"`` and ``"loudness_shift"`` (decoded - reference, in LU): ``l3ac_amd.loudness`` of each side at the codec's
         rate (section 3.14).  ``pitch=True`` adds ``"f0_rmse_cents"``, ``"gpe"``, ``"vde"``, ``"ffe"``, ``"pitch_frames"`` and
         ``"pitch_voiced"`` (the frames voiced on both sides): ``l3ac_amd.pitch_metrics`` of the same pairs at the codec's rate with its
-        default parameters (section 3.15).  Every value equals composing those public calls by hand, bit for bit."""
+        default parameters (section 3.15).  ``mcd=True`` adds ``"mcd_db"``, ``l3ac_amd.mcd`` of the same pairs at the codec's rate with its
+        default parameters (along the DTW path), and ``"mcd_plain_db"``, the same with ``dtw=False`` (frame f against frame f; both
+        sides have the same lengths here) (section 3.17); a recording may then have at most 4096 frames of 160 samples.  Every value
+        equals composing those public calls by hand, bit for bit."""
         scales = _metric_scales(scales)
+        if mcd:  # a rate the defaults do not fit, or a batch too long for a DTW pair, raises before any device work
+            _check_mfcc_params(self.config.sample_rate, 512, _mfcc_hop(512, None), 40, 13)
+            longest = audio_data.shape[-1] if self._rate(sample_rate) is None else resample_length(int(sample_rate), self.config.sample_rate,
+                                                                                                  max(audio_data.shape[-1], 1))
+            if 1 + longest // _mfcc_hop(512, None) > 4096:
+                raise ValueError(f"evaluate(mcd=True): {longest} samples are more than the 4096 frames of a DTW pair")
         if pitch:  # a rate the tracker's defaults do not fit raises before any device work
             _check_pitch_params(self.config.sample_rate)
         if loudness:  # a rate the K-weighting is not defined for raises before any device work
@@ -587,6 +597,9 @@ class L3AC:
             pm = _pitch_metrics(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
             out.update({"f0_rmse_cents": pm["f0_rmse_cents"], "gpe": pm["gpe"], "vde": pm["vde"], "ffe": pm["ffe"], "pitch_frames": pm["frames"],
                         "pitch_voiced": pm["voiced_both"]})
+        if mcd:
+            out["mcd_db"] = _mcd(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)["mcd_db"]
+            out["mcd_plain_db"] = _mcd(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens, dtw=False)["mcd_db"]
         tokens = info["lengths"]
         seconds = torch.tensor(lens, dtype=torch.float64) / self.config.sample_rate
         out["tokens"] = tokens

@@ -171,6 +171,12 @@ SIGNATURES = {
     "l3ac_xcorr_scratch_bytes": (_I64, [_I32, _I64, _I32]),
     "l3ac_xcorr": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "l3ac_align_apply": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _P, _I64, _P, _I64, _P, _P, _I64, _P]),
+    "l3ac_dct_table": (_I64, [_I32, _I32, _P, _I64]),
+    "l3ac_mfcc_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32, _I32]),
+    "l3ac_mfcc": (C.c_int, [_P, _I32, _I64, _I64, C.POINTER(_I32), _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I64, _P]),
+    "l3ac_dtw_scratch_bytes": (_I64, [_I32, _I32, _I32]),
+    "l3ac_dtw": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, _I64,
+                           _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

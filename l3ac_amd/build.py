@@ -52,6 +52,7 @@ SOURCES = [
     "kernels/loudness.hip",
     "kernels/pitch.hip",
     "kernels/align.hip",
+    "kernels/mcd.hip",
 ]
 
 

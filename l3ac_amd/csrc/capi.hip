@@ -907,6 +907,31 @@ int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int
                               out_est_stride, out_samples, scratch, scratch_bytes);
 }
 
+// ---- mel-cepstral distortion with DTW alignment ---------------------------------------------
+int64_t l3ac_dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) { return dct_table(n_mels, n_coeffs, out, cap); }
+
+int64_t l3ac_mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs) {
+    return mfcc_scratch_bytes(batch, max_samples, n_fft, hop, n_mels, n_coeffs);
+}
+
+int l3ac_mfcc(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
+              int64_t scratch_bytes, void* stream) {
+    return launch_mfcc((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, dct, n_coeffs, out,
+                       scratch, scratch_bytes);
+}
+
+int64_t l3ac_dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
+    return dtw_scratch_bytes(batch, max_frames_a, max_frames_b);
+}
+
+int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride, int32_t batch,
+             int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b, int32_t diagonal_only,
+             double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_dtw((hipStream_t)stream, a, a_frame_stride, a_row_stride, b, b_frame_stride, b_row_stride, batch, dim, max_frames_a, max_frames_b,
+                      frames_a, frames_b, diagonal_only, cost, path_len, path, delta, scratch, scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

@@ -310,6 +310,18 @@ int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const floa
 int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                        const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
                        int32_t* out_samples, void* scratch, int64_t scratch_bytes);
+// mel-cepstral distortion (kernels/mcd.hip; include/l3ac_hip.h "mel-cepstral distortion"): the orthonormal DCT-II
+// table (host), the cepstra of log_mel's cells as one fp32 fmaf chain per coefficient, and the batched DTW over rows of fp32 features
+// (fp64 frame distances and accumulation, one workgroup per pair, the backtrace in the same kernel)
+int64_t dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap);
+int64_t mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs);
+int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
+                int32_t hop, const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
+                int64_t scratch_bytes);
+int64_t dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b);
+int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride,
+               int32_t batch, int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b,
+               int32_t diagonal_only, double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -48,7 +48,8 @@ def mel_weights(sample_rate: int, n_fft: int, n_mels: int) -> torch.Tensor:
     return host.view(int(n_mels), int(n_fft) // 2 + 1)
 
 
-_tables = {}  # (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) -> device copy of the library's table
+# (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "dct", n_mels, n_coeffs: mcd.py) -> device copy of the table
+_tables = {}
 
 
 def _table(device: torch.device, key: tuple, make) -> torch.Tensor:
@@ -87,14 +88,18 @@ def _lengths(lengths, b: int, t: int):
     return lens, (ctypes.c_int32 * b)(*lens)
 
 
+def _extra_bytes(b: int, t: int, n_fft: int, hop: int, extra_scratch) -> int:
+    """Bytes a call allocates above the minimum scratch."""
+    if extra_scratch is None:  # the default, never more than the spectra of every frame row of both signals
+        return min(_EXTRA_SCRATCH, 2 * b * (t // hop + n_fft // hop + 2) * (n_fft + 4) * 4)
+    return max(0, int(extra_scratch))
+
+
 def _scratch(dev, b: int, t: int, n_fft: int, hop: int, n_mels: int, extra_scratch) -> torch.Tensor:
     need = _capi.load_library().l3ac_mel_scratch_bytes(b, t, n_fft, hop, n_mels)
     if need < 0:
         raise ValueError(_capi.load_library().l3ac_last_error().decode())
-    if extra_scratch is None:  # the default, never more than the spectra of every frame row of both signals
-        extra = min(_EXTRA_SCRATCH, 2 * b * (t // hop + n_fft // hop + 2) * (n_fft + 4) * 4)
-    else:
-        extra = max(0, int(extra_scratch))
+    extra = _extra_bytes(b, t, n_fft, hop, extra_scratch)
     return torch.empty(int(need) + extra, dtype=torch.uint8, device=dev)  # (the caching allocator hands out 512-byte aligned blocks)
 
 
