@@ -600,6 +600,59 @@ int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const
              int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b, int32_t diagonal_only,
              double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- linear prediction and the spectral-envelope measures: LLR, Itakura-Saito, cepstral distance, segmental SNR (DESIGN.md section 3.18,
+ * which states every formula and summation order) -------------------------------------------------------------------------------------------
+ * Framing: sample_rate in 8000..192000 (it selects nothing but l3ac_lpc_defaults' values), order p in 1..32, frame N in p + 1..8192, hop >=
+ * 1.  A clip of n samples has F(n) = 0 frames for n < N, else 1 + (n - N) / hop; frame t reads samples [t hop, t hop + N) and nothing else
+ * (no padding, no centring).  xw[i] = (double)x[i] (double)w[i] with w the fp32 window: `window` is the DEVICE copy of l3ac_lpc_window's
+ * output, w[i] = 0.5 (1 - cos(2 pi (i + 1) / (N + 1))) designed in fp64 and rounded once, or NULL for the rectangular window.
+ * Per frame, all fp64 with contraction off: r[k] = sum_{i=0}^{N-1-k} xw[i] xw[i+k], k = 0..p, as 64 interleaved partial sums (partial l
+ * takes the terms i = l mod 64 in increasing i from +0) folded s[l] += s[l+h] for h = 32, 16, .., 1.  Levinson-Durbin: a[0] = 1, E_0 = r[0];
+ * for m = 1..p: acc = r[m] + sum_{i=1}^{m-1} a[i] r[m-i] in increasing i, k_m = -acc / E_{m-1}, a'[i] = a[i] + k_m a[m-i], a'[m] = k_m, E_m =
+ * E_{m-1} (1 - k_m k_m).  A frame is valid iff r[0] > 0 and every E_m > 0.  q(a, r) = sum_i a[i] (sum_j r[|i-j|] a[j]), both sums from +0 in
+ * increasing index.  Cepstrum of 1/A: c_1 = -a_1, c_m = -a_m - sum_{k=1}^{m-1} ((k / m) c_k) a_{m-k}, the sum from +0 in increasing k.
+ * For a pair (reference r, estimate e; a frame needs both sides valid): num = q(a_e, r_r), g_r = q(a_r, r_r), g_e = q(a_e, r_e);
+ * LLR = ln(num / g_r) clamped to [0, llr_max]; IS = ((g_r / g_e) (num / g_r) + ln(g_e / g_r)) - 1 clamped to [0, is_max]; CD = (10 / ln 10)
+ * sqrt(2 sum_{m=1}^{p} (c_r[m] - c_e[m])^2) clamped to [0, cd_max].  Segmental SNR on the same windowed frames: sig = r_r[0], noise =
+ * sum (xw_r[i] - xw_e[i])^2 in the autocorrelation's order; 10 log10(sig / noise) clamped to [-10, 35], 35 where noise == 0; a frame
+ * counts iff sig > 0.  Per pair: seg_snr_db is the mean of the counted frames' values summed in frame order; for each of LLR, IS, CD the V
+ * valid frames' values are sorted ascending, the first k = floor(trim V + 0.5) summed in that order from +0 and divided by k; V = 0 or k = 0
+ * gives NaN.  A pair has at most 16384 frames.
+ *   l3ac_lpc_window:                HOST only: w as `frame` floats; same protocol as l3ac_mel_weights (returns the float count; nothing is
+ *                                   written when out is NULL or cap is below it; < 0 for frame outside 2..8192).
+ *   l3ac_lpc_defaults:              HOST only: out[3] = order (10 below 10 kHz, else 16), frame ((30 fs + 500) / 1000), hop (frame / 4).
+ *   l3ac_lpc_frames:                HOST only: F(samples); < 0 for samples < 0, frame outside 2..8192 or hop < 1.
+ *   l3ac_lpc_scratch_bytes:         the minimum scratch of l3ac_lpc: 256 ceil(4 batch / 256) bytes; < 0 for unsupported parameters.
+ *   l3ac_lpc:                       audio [batch] rows of max_samples floats, audio_stride floats apart; samples: HOST array of batch
+ *                                   lengths in 1..max_samples, or NULL -> with F = F(max_samples): a [batch][F][p+1], reflection
+ *                                   [batch][F][p], error [batch][F] (E_p), autocorr [batch][F][p+1] fp64, valid [batch][F] and frames
+ *                                   [batch] (or NULL) int32, all device buffers.  Rows at and after a clip's own F(n) are NaN / 0; an
+ *                                   invalid frame has a, reflection and error NaN and keeps its autocorr.
+ *   l3ac_lpc_metrics_scratch_bytes: the minimum scratch of l3ac_lpc_metrics: 256 ceil(4 batch / 256) + 256 ceil(32 batch F / 256) + 256
+ *                                   ceil(4 batch F / 256) bytes (the lengths, the frames' four values, the frames' flags); < 0 for
+ *                                   unsupported parameters or F(max_samples) > 16384.
+ *   l3ac_lpc_metrics:               ref, est as audio above; trim in (0, 1]; llr_max, is_max, cd_max finite and >= 0 -> out [batch][4]
+ *                                   fp64 = llr, is_distance, cepstral_distance_db, seg_snr_db; counts [batch][3] int32 = frames, valid
+ *                                   frames V, frames counted for the SNR; frame_values (or NULL) [batch][F][4] fp64 = the frames' clamped
+ *                                   LLR, IS, CD, SNR, NaN where not counted; forms (or NULL; a test hook) [batch][F][5] fp64 = num, g_r, g_e,
+ *                                   sig, noise (the first three NaN where a side is invalid).  All device buffers.
+ * Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee and calling convention: as the
+ * quality metrics above (a pair's results depend on its own samples only — not on the batch, its row, the strides, the scratch size or
+ * what lies at or after its length, which is never read; no atomics; enqueue only, nothing allocated, no synchronisation, capturable).
+ * Non-finite samples leave the frames that read them, and their pair's means, unspecified and disturb nothing else. */
+int64_t l3ac_lpc_window(int32_t frame, float* out, int64_t cap);
+int l3ac_lpc_defaults(int32_t sample_rate, int32_t* out);
+int64_t l3ac_lpc_frames(int64_t samples, int32_t frame, int32_t hop);
+int64_t l3ac_lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
+int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate, int32_t order,
+             int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error, double* autocorr, int32_t* valid,
+             int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t l3ac_lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
+int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
+                     double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
+                     int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -53,6 +53,7 @@ SOURCES = [
     "kernels/pitch.hip",
     "kernels/align.hip",
     "kernels/mcd.hip",
+    "kernels/lpc.hip",
 ]
 
 

@@ -932,6 +932,36 @@ int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const
                       frames_a, frames_b, diagonal_only, cost, path_len, path, delta, scratch, scratch_bytes);
 }
 
+// ---- linear prediction, LLR, Itakura-Saito, cepstral distance, segmental SNR ----------------
+int64_t l3ac_lpc_window(int32_t frame, float* out, int64_t cap) { return lpc_window(frame, out, cap); }
+
+int l3ac_lpc_defaults(int32_t sample_rate, int32_t* out) { return lpc_defaults(sample_rate, out); }
+
+int64_t l3ac_lpc_frames(int64_t samples, int32_t frame, int32_t hop) { return lpc_frames(samples, frame, hop); }
+
+int64_t l3ac_lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
+    return lpc_scratch_bytes(batch, max_samples, sample_rate, order, frame, hop);
+}
+
+int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate, int32_t order,
+             int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error, double* autocorr, int32_t* valid,
+             int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_lpc((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, order, frame, hop, window, a, reflection, error,
+                      autocorr, valid, frames, scratch, scratch_bytes);
+}
+
+int64_t l3ac_lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
+    return lpc_metrics_scratch_bytes(batch, max_samples, sample_rate, order, frame, hop);
+}
+
+int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
+                     double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
+                     int64_t scratch_bytes, void* stream) {
+    return launch_lpc_metrics((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, sample_rate, order, frame, hop, window,
+                              trim, llr_max, is_max, cd_max, out, counts, frame_values, forms, scratch, scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

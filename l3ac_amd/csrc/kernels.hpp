@@ -322,6 +322,21 @@ int64_t dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frame
 int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride,
                int32_t batch, int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b,
                int32_t diagonal_only, double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes);
+// linear prediction and the envelope measures (kernels/lpc.hip; include/l3ac_hip.h "linear prediction"): the window
+// (host), the geometry (host), short-time autocorrelation + Levinson-Durbin of one side, and of a pair with the three quadratic forms, the
+// cepstra, LLR / IS / CD / segmental SNR per frame and the sorted, trimmed means per pair (one workgroup per pair)
+int64_t lpc_window(int32_t frame, float* out, int64_t cap);
+int lpc_defaults(int32_t sample_rate, int32_t* out);
+int64_t lpc_frames(int64_t samples, int32_t frame, int32_t hop);
+int64_t lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
+int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+               int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error,
+               double* autocorr, int32_t* valid, int32_t* frames, void* scratch, int64_t scratch_bytes);
+int64_t lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
+int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                       const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
+                       double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
+                       int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

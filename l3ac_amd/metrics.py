@@ -48,7 +48,8 @@ def mel_weights(sample_rate: int, n_fft: int, n_mels: int) -> torch.Tensor:
     return host.view(int(n_mels), int(n_fft) // 2 + 1)
 
 
-# (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "dct", n_mels, n_coeffs: mcd.py) -> device copy of the table
+# (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "dct", n_mels, n_coeffs: mcd.py) /
+# (device, "lpc_window", frame: lpc.py) -> device copy of the table
 _tables = {}
 
 
