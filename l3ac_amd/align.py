@@ -7,9 +7,8 @@ import operator
 
 import torch
 
-from . import _capi
+from . import _capi, _metric
 from ._rows import row_stride
-from .metrics import _lengths, _pair
 
 MAX_LAG = 16384  # the largest supported ``max_lag``
 
@@ -39,24 +38,21 @@ def delay(reference: torch.Tensor, estimate: torch.Tensor, max_lag: int, lengths
     A clip's bits do not depend on the batch it is in; ``extra_scratch``: bytes to allocate above the minimum scratch (the result does
     not depend on it).  No table is uploaded: the call can be captured without a warm-up.  No CPU path: CPU tensors raise."""
     max_lag = _max_lag(max_lag)
-    r, e = _pair(reference, estimate, "delay")
+    r, e = _metric.pair(reference, estimate, "delay")
     b, t = r.shape
-    _, c_lens = _lengths(lengths, b, t)
+    _, c_lens = _metric.lengths(lengths, b, t)
     dev = r.device
-    lib = _capi.load_library()
-    need = lib.l3ac_xcorr_scratch_bytes(b, t, max_lag)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    lag = torch.empty(b, dtype=torch.int32, device=dev)
+    need = _metric.lib_value("l3ac_xcorr_scratch_bytes", b, t, max_lag)
+    lag =torch.empty(b, dtype=torch.int32, device=dev)
     polarity = torch.empty(b, dtype=torch.int32, device=dev)
     dly = torch.empty(b, dtype=torch.float64, device=dev)
     corr = torch.empty(b, dtype=torch.float64, device=dev)
     xcorr = torch.empty((b, 2 * max_lag + 1), dtype=torch.float64, device=dev) if return_xcorr else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + (0 if extra_scratch is None else max(0, int(extra_scratch))), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_xcorr(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, max_lag, lag.data_ptr(),
-                                   polarity.data_ptr(), dly.data_ptr(), corr.data_ptr(), xcorr.data_ptr() if return_xcorr else None,
-                                   scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.scratch(dev, need, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_xcorr(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, max_lag, lag.data_ptr(),
+                                                    polarity.data_ptr(), dly.data_ptr(), corr.data_ptr(), xcorr.data_ptr() if return_xcorr else None,
+                                                    scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     out = {"lag": lag, "polarity": polarity, "delay": dly, "correlation": corr}
     if return_xcorr:
         out["xcorr"] = xcorr
@@ -74,27 +70,24 @@ def apply_delay(reference: torch.Tensor, estimate: torch.Tensor, lag: torch.Tens
     not; nor do ``mel_distance``, ``stoi`` and ``pitch_metrics``)."""
     if not isinstance(lag, torch.Tensor) or lag.dtype != torch.int32 or lag.dim() != 1:
         raise ValueError("apply_delay: lag must be a one-dimensional int32 tensor, one lag per clip")
-    r, e = _pair(reference, estimate, "apply_delay")
+    r, e = _metric.pair(reference, estimate, "apply_delay")
     b, t = r.shape
-    _, c_lens = _lengths(lengths, b, t)
+    _, c_lens = _metric.lengths(lengths, b, t)
     dev = r.device
     if lag.shape[0] != b:
         raise ValueError(f"apply_delay: {lag.shape[0]} lags for a batch of {b}")
     if lag.device != dev:
         raise RuntimeError(f"apply_delay: lag is on {lag.device} but the audio is on {dev}")
     lag = lag.contiguous()
-    lib = _capi.load_library()
-    need = lib.l3ac_xcorr_scratch_bytes(b, t, 0)  # (covers the lengths' upload, all this entry needs)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    need = _metric.lib_value("l3ac_xcorr_scratch_bytes", b, t, 0)  # (covers the lengths' upload, all this entry needs)
     out_r = torch.empty((b, t), dtype=torch.float32, device=dev)
     out_e = torch.empty((b, t), dtype=torch.float32, device=dev)
     m = torch.empty(b, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_align_apply(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, lag.data_ptr(), out_r.data_ptr(), t,
-                                         out_e.data_ptr(), t, m.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                         torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.scratch(dev, need)
+        _capi.check(_capi.load_library().l3ac_align_apply(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, lag.data_ptr(),
+                                                          out_r.data_ptr(), t, out_e.data_ptr(), t, m.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                          _metric.stream(dev)))
     return out_r, out_e, m
 
 

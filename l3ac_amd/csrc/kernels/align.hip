@@ -24,7 +24,7 @@
 // results unspecified; every index is bounded by the parameters, whatever the values.
 //
 // Contraction is off for this whole file: the only fused operations are those of the matrix instruction.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 
@@ -48,8 +48,6 @@ static_assert(32 * XC_COLS <= XC_S + XC_EST, "the block's 32 x XC_COLS result ti
 static_assert(XC_TILES % XC_WAVES == 0 && XC_DIAGS <= XC_THREADS, "two tiles per wave, one lane per lag");
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-int64_t align256(int64_t v) { return round_up64(v, 256); }
 
 int64_t segments_of(int64_t n) { return ceil_div64(n, XC_S); }
 
@@ -124,19 +122,6 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_kernel(const float* __restri
     }
 }
 
-// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order; every thread gets the result
-__device__ __forceinline__ double pk_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // the previous use of lds is over
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < PK_THREADS / 64; ++w) s += lds[w];
-    return s;
-}
-
 // whether lag index i with |r| = v comes before lag index j with |r| = w: the larger value, then the smaller |d|, then the smaller d
 __device__ __forceinline__ bool pk_before(double v, int i, double w, int j, int max_lag) {
     if (v != w) return v > w;
@@ -174,8 +159,8 @@ __global__ __launch_bounds__(PK_THREADS) void xcorr_pick_kernel(const float* __r
         e_ref += a * a;
         e_est += c * c;
     }
-    e_ref = pk_block_sum(e_ref, lds);
-    e_est = pk_block_sum(e_est, lds);
+    e_ref = block_sum<PK_THREADS>(e_ref, lds);
+    e_est = block_sum<PK_THREADS>(e_est, lds);
 
     // the pick: (-1, lag 0) stands where no |r| compares (NaN rows), so the lag stays inside [-L, L]
     double v = -1.0;
@@ -240,50 +225,41 @@ __global__ __launch_bounds__(AP_THREADS) void align_apply_kernel(const float* __
     }
 }
 
-int align_shape(const char* what, int32_t batch, int64_t max_samples) {
-    L3AC_REQUIRE(batch > 0 && batch <= 65535, "%s: batch %d outside 1..65535", what, batch);
-    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "%s: max_samples %lld outside 1..2^31 - 1", what, (long long)max_samples);
-    return L3AC_OK;
-}
+struct XcorrScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t seg_sums, need;
+};
 
-int align_lag(int32_t max_lag) {
+// the parameters checked, then r_g(d) [batch][segments][2L + 1] fp64 (the last region: not rounded up)
+int xcorr_scratch(int32_t batch, int64_t max_samples, int32_t max_lag, XcorrScratch* sc) {
     L3AC_REQUIRE(max_lag >= 0 && max_lag <= XC_MAX_LAG, "xcorr: max_lag %d outside 0..%d", max_lag, XC_MAX_LAG);
-    return L3AC_OK;
-}
-
-int align_lengths(const char* what, const int32_t* samples, int32_t batch, int64_t max_samples) {
-    for (int i = 0; samples && i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "%s: samples[%d] = %d outside [1, %lld]", what, i, samples[i],
-                     (long long)max_samples);
+    L3AC_TRY(check_clip_batch("xcorr", batch, max_samples));
+    ScratchPlan plan(batch);
+    sc->seg_sums = plan.last((int64_t)batch * segments_of(max_samples) * (2 * (int64_t)max_lag + 1) * 8);
+    sc->need = plan.bytes;
     return L3AC_OK;
 }
 
 }  // namespace
 
 int64_t xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag) {
-    L3AC_TRY(align_lag(max_lag));
-    L3AC_TRY(align_shape("xcorr", batch, max_samples));
-    // the clips' lengths, then r_g(d) [batch][segments][2L + 1] fp64
-    return align256((int64_t)batch * 4) + (int64_t)batch * segments_of(max_samples) * (2 * (int64_t)max_lag + 1) * 8;
+    XcorrScratch sc;
+    L3AC_TRY(xcorr_scratch(batch, max_samples, max_lag, &sc));
+    return sc.need;
 }
 
 int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                  const int32_t* samples, int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr,
                  void* scratch, int64_t scratch_bytes) {
-    L3AC_TRY(align_lag(max_lag));
-    L3AC_TRY(align_shape("xcorr", batch, max_samples));
+    XcorrScratch sc;
+    L3AC_TRY(xcorr_scratch(batch, max_samples, max_lag, &sc));
     L3AC_REQUIRE(ref && est, "xcorr: null audio");
     L3AC_REQUIRE(lag && polarity && delay && correlation, "xcorr: null output buffer");
     L3AC_REQUIRE(batch == 1 || (ref_stride >= max_samples && est_stride >= max_samples), "xcorr: row stride below max_samples %lld",
                  (long long)max_samples);
-    L3AC_TRY(align_lengths("xcorr", samples, batch, max_samples));
-    const int64_t need = xcorr_scratch_bytes(batch, max_samples, max_lag);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "xcorr: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "xcorr: scratch of %lld bytes is below l3ac_xcorr_scratch_bytes = %lld", (long long)scratch_bytes,
-                 (long long)need);
-    int* lens = samples ? static_cast<int*>(scratch) : nullptr;
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
-    double* seg_sums = reinterpret_cast<double*>(static_cast<char*>(scratch) + align256((int64_t)batch * 4));
+    L3AC_TRY(check_clip_lengths("xcorr", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "xcorr", "xcorr", samples, batch, scratch, scratch_bytes, sc.need, &lens));
+    double* seg_sums = reinterpret_cast<double*>(static_cast<char*>(scratch) + sc.seg_sums);
     const int64_t segs = segments_of(max_samples);
     const int lags = 2 * max_lag + 1;
     const double terms = (double)batch * (double)max_samples * lags;
@@ -303,19 +279,15 @@ int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const floa
 int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                        const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
                        int32_t* out_samples, void* scratch, int64_t scratch_bytes) {
-    L3AC_TRY(align_shape("align_apply", batch, max_samples));
+    L3AC_TRY(check_clip_batch("align_apply", batch, max_samples));
     L3AC_REQUIRE(ref && est, "align_apply: null audio");
     L3AC_REQUIRE(lag, "align_apply: null lag");
     L3AC_REQUIRE(out_ref && out_est && out_samples, "align_apply: null output buffer");
     L3AC_REQUIRE(batch == 1 || (ref_stride >= max_samples && est_stride >= max_samples && out_ref_stride >= max_samples && out_est_stride >= max_samples),
                  "align_apply: row stride below max_samples %lld", (long long)max_samples);
-    L3AC_TRY(align_lengths("align_apply", samples, batch, max_samples));
-    const int64_t need = align256((int64_t)batch * 4);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "align_apply: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "align_apply: scratch of %lld bytes is below the %lld of the clips' lengths", (long long)scratch_bytes,
-                 (long long)need);
-    int* lens = samples ? static_cast<int*>(scratch) : nullptr;
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
+    L3AC_TRY(check_clip_lengths("align_apply", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "align_apply", nullptr, samples, batch, scratch, scratch_bytes, ScratchPlan(batch).bytes, &lens));
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div64(max_samples, (int64_t)AP_THREADS * 4), 256);
     ProfScope prof(s, "align_apply_kernel", 0.0, 16.0 * batch * (double)max_samples);
     hipLaunchKernelGGL(align_apply_kernel, dim3(blocks, (unsigned)batch), dim3(AP_THREADS), 0, s, ref, ref_stride, est, est_stride, max_samples, lens,

@@ -21,7 +21,7 @@
 //
 // The product of a multiply must not be fused into the add that follows it differently in the two passes or on the host: contraction is
 // off for this whole file, host code included (M is designed by the same recursion).
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -44,11 +44,9 @@ struct LoudFilter {  // b0 b1 b2 a1 a2 of the two stages (a0 = 1), M row-major a
     int step;
 };
 
-struct LoudScratch {  // byte offsets into the caller's scratch
-    int64_t lens, state, energy, step_max, total_min;
+struct LoudScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t state, energy, step_max, total_min;
 };
-
-int64_t align256(int64_t v) { return round_up64(v, 256); }
 
 bool rate_ok(int32_t fs) { return fs % 10 == 0 && fs >= LD_MIN_RATE && fs <= LD_MAX_RATE; }
 
@@ -87,27 +85,13 @@ __device__ __forceinline__ Pair pair_mul(Pair a, Pair b) {
 
 int loud_geom(int32_t batch, int64_t max_samples, int32_t sample_rate, int64_t* s_max, LoudScratch* sc) {
     LD_REQUIRE_RATE(sample_rate);
-    L3AC_REQUIRE(batch > 0 && batch <= 65535, "loudness: batch %d outside 1..65535", batch);
-    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "loudness: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
+    L3AC_TRY(check_clip_batch("loudness", batch, max_samples));
     *s_max = max_samples / (sample_rate / 10);
-    int64_t off = 0;
-    sc->lens = off;
-    off += align256((int64_t)batch * 4);
-    sc->state = off;
-    off += align256((int64_t)batch * *s_max * 4 * 8);
-    sc->energy = off;
-    off += align256((int64_t)batch * *s_max * 8);
-    sc->step_max = off;
-    off += align256((int64_t)batch * *s_max * 4);
-    sc->total_min = off;
-    return L3AC_OK;
-}
-
-int check_lengths(const int32_t* samples, int batch, int64_t max_samples) {
-    if (!samples) return L3AC_OK;
-    for (int i = 0; i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "loudness: samples[%d] = %d outside [1, %lld]", i, samples[i],
-                     (long long)max_samples);
+    ScratchPlan plan(batch);
+    sc->state = plan.take((int64_t)batch * *s_max * 4 * 8);
+    sc->energy = plan.take((int64_t)batch * *s_max * 8);
+    sc->step_max = plan.take((int64_t)batch * *s_max * 4);
+    sc->total_min = plan.bytes;
     return L3AC_OK;
 }
 
@@ -193,31 +177,6 @@ __global__ __launch_bounds__(64) void loudness_scan_kernel(int batch, int64_t ma
     }
 }
 
-// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order; every thread gets the result
-__device__ __forceinline__ double ld_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // the previous use of lds is over
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < LD_GATE_THREADS / 64; ++w) s += lds[w];
-    return s;
-}
-
-__device__ __forceinline__ double ld_block_max(double v, double* lds) {  // (a maximum does not depend on the order)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = lds[0];
-#pragma unroll
-    for (int w = 1; w < LD_GATE_THREADS / 64; ++w) s = fmax(s, lds[w]);
-    return s;
-}
-
 // ---- phase 4: blocks, gates, L; one workgroup per clip ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(LD_GATE_THREADS) void loudness_gate_kernel(const float* __restrict__ audio, int64_t stride, int64_t max_samples,
                                                                       const int* __restrict__ lens, int step, int64_t s_max, int64_t j_max,
@@ -244,8 +203,8 @@ __global__ __launch_bounds__(LD_GATE_THREADS) void loudness_gate_kernel(const fl
     }
     if (momentary)
         for (int64_t j = blocks + threadIdx.x; j < j_max; j += LD_GATE_THREADS) momentary[(int64_t)b * j_max + j] = ninf;
-    sum = ld_block_sum(sum, lds);
-    cnt = ld_block_sum(cnt, lds);  // (whole numbers below 2^31: exact)
+    sum = block_sum<LD_GATE_THREADS>(sum, lds);
+    cnt = block_sum<LD_GATE_THREADS>(cnt, lds);  // (whole numbers below 2^31: exact)
     // the relative gate, 10 LU below the loudness of the absolutely gated blocks (no such block: nothing passes)
     const double gamma = lkfs(sum / cnt) - 10.0;
     double sum2 = 0.0, cnt2 = 0.0;
@@ -255,15 +214,15 @@ __global__ __launch_bounds__(LD_GATE_THREADS) void loudness_gate_kernel(const fl
             if (l > -70.0 && l > gamma) sum2 += z, cnt2 += 1.0;
         }
     }
-    sum2 = ld_block_sum(sum2, lds);
-    cnt2 = ld_block_sum(cnt2, lds);
+    sum2 = block_sum<LD_GATE_THREADS>(sum2, lds);
+    cnt2 = block_sum<LD_GATE_THREADS>(cnt2, lds);
 
     // the sample peak over the clip's own n samples: the whole steps' maxima, then the samples after the last whole step
     double peak = 0.0;
     for (int64_t s = threadIdx.x; s < steps; s += LD_GATE_THREADS) peak = fmax(peak, (double)step_max[(int64_t)b * s_max + s]);
     const float* x = audio + (int64_t)b * stride;
     for (int64_t i = steps * step + threadIdx.x; i < n; i += LD_GATE_THREADS) peak = fmax(peak, (double)fabsf(x[i]));
-    peak = ld_block_max(peak, lds);
+    peak = block_max<LD_GATE_THREADS>(peak, lds);
 
     if (threadIdx.x == 0) {
         stats[2 * (int64_t)b] = cnt2 > 0.0 ? lkfs(sum2 / cnt2) : ninf;
@@ -391,20 +350,17 @@ int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int
     L3AC_REQUIRE(audio && stats && counts, "loudness: null buffer");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "loudness: row stride %lld below max_samples %lld", (long long)audio_stride,
                  (long long)max_samples);
-    L3AC_TRY(check_lengths(samples, batch, max_samples));
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "loudness: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= sc.total_min, "loudness: scratch of %lld bytes is below l3ac_loudness_scratch_bytes = %lld",
-                 (long long)scratch_bytes, (long long)sc.total_min);
+    L3AC_TRY(check_clip_lengths("loudness", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "loudness", "loudness", samples, batch, scratch, scratch_bytes, sc.total_min, &lens));
     LoudFilter f;
     L3AC_TRY(filter_design(sample_rate, &f));
     char* base = static_cast<char*>(scratch);
-    int* lens = samples ? reinterpret_cast<int*>(base + sc.lens) : nullptr;
     double* state = reinterpret_cast<double*>(base + sc.state);
     double* energy = reinterpret_cast<double*>(base + sc.energy);
     float* step_max = reinterpret_cast<float*>(base + sc.step_max);
     const int64_t j_max = std::max<int64_t>(s_max - 3, 0);
 
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
     if (s_max > 0) {
         const dim3 grid((unsigned)ceil_div64(s_max, LD_STEPS), (unsigned)batch);
         const double flops = 22.0 * batch * (double)max_samples, bytes = 4.0 * batch * (double)max_samples;
@@ -447,20 +403,14 @@ int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, doub
 
 int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
                       const int32_t* samples, const double* gain, int64_t gain_stride) {
-    L3AC_REQUIRE(batch > 0 && batch <= 65535, "apply_gain: batch %d outside 1..65535", batch);
-    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "apply_gain: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
+    L3AC_TRY(check_clip_batch("apply_gain", batch, max_samples));
     L3AC_REQUIRE(audio && out && gain, "apply_gain: null buffer");
     L3AC_REQUIRE(batch == 1 || (audio_stride >= max_samples && out_stride >= max_samples), "apply_gain: row stride below max_samples %lld",
                  (long long)max_samples);
     L3AC_REQUIRE(gain_stride >= 1, "apply_gain: gain_stride %lld must be positive", (long long)gain_stride);
-    L3AC_TRY(check_lengths(samples, batch, max_samples));
+    L3AC_TRY(check_clip_lengths("loudness", samples, batch, max_samples));  // (this one message has always said "loudness")
     const bool vec = (((uintptr_t)audio | (uintptr_t)out) & 15) == 0 && (batch == 1 || ((audio_stride | out_stride) & 3) == 0);
-    const int group = samples ? RaggedUpload::CAP : batch;  // without lengths one launch takes the whole batch
-    for (int off = 0; off < batch; off += group) {
-        RaggedUpload blk{};
-        blk.offset = off;
-        blk.n = std::min(group, batch - off);
-        for (int i = 0; samples && i < blk.n; ++i) blk.vals[i] = samples[off + i];
+    return for_each_length_group(samples, batch, [&](const RaggedUpload& blk) -> int {
         const dim3 grid((unsigned)ceil_div64(ceil_div64(max_samples, 4), LD_GAIN_THREADS), (unsigned)blk.n);
         ProfScope prof(s, "apply_gain_kernel", 1.0 * blk.n * (double)max_samples, 8.0 * blk.n * (double)max_samples);
         if (vec)
@@ -470,6 +420,6 @@ int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, f
             hipLaunchKernelGGL(apply_gain_kernel<false>, grid, dim3(LD_GAIN_THREADS), 0, s, audio, audio_stride, out, out_stride, max_samples,
                                samples ? 1 : 0, blk, gain, gain_stride);
         L3AC_LAUNCH_CHECK();
-    }
-    return L3AC_OK;
+        return L3AC_OK;
+    });
 }

@@ -25,7 +25,7 @@
 // values in the frames that read them, and in their pair's means; every index is bounded by the parameters, whatever the values.
 //
 // Contraction is off for this whole file: every product and sum rounds on its own, in the order DESIGN.md states.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -63,8 +63,6 @@ struct LpcClamp {
     double trim, llr_max, is_max, cd_max;
 };
 
-int64_t align256(int64_t v) { return round_up64(v, 256); }
-
 int lds_need(int g, int pitch, int n) { return LP_WAVES * LP_WORK * 8 + n * 4 + 2 * ((g - 1) * pitch + n) * 4; }
 
 int lpc_geom(int32_t fs, int32_t order, int32_t frame, int32_t hop, LpcGeom* p) {
@@ -81,12 +79,6 @@ int lpc_geom(int32_t fs, int32_t order, int32_t frame, int32_t hop, LpcGeom* p) 
 }
 
 int64_t frames_of(int64_t samples, const LpcGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
-
-int lpc_shape(int32_t batch, int64_t max_samples) {
-    L3AC_REQUIRE(batch > 0 && batch <= 65535, "lpc: batch %d outside 1..65535", batch);
-    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "lpc: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
-    return L3AC_OK;
-}
 
 // the fold s[l] += s[l + h], h = 32 .. 1: lane 0 holds the sum (a lane at or above h adds what it is handed and is not read again)
 __device__ __forceinline__ double fold64(double v) {
@@ -344,9 +336,21 @@ int configure_frame_kernel() {
     return L3AC_OK;
 }
 
-int check_clips(const char* what, int32_t batch, int64_t max_samples, const int32_t* samples) {
-    for (int i = 0; samples && i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "%s: samples[%d] = %d outside [1, %lld]", what, i, samples[i], (long long)max_samples);
+struct LpcMetricsScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t vals, flags, need;
+};
+
+// the parameters checked, then the frames' four values [batch][F][4] fp64 and the frames' flags [batch][F] int32
+int lpc_metrics_scratch(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, LpcGeom* p,
+                        LpcMetricsScratch* sc) {
+    L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, p));
+    L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
+    const int64_t f_max = frames_of(max_samples, *p);
+    L3AC_REQUIRE(f_max <= LQ_MAX_FRAMES, "lpc_metrics: %lld frames are more than the %d of a pair", (long long)f_max, LQ_MAX_FRAMES);
+    ScratchPlan plan(batch);
+    sc->vals = plan.take((int64_t)batch * f_max * 32);
+    sc->flags = plan.take((int64_t)batch * f_max * 4);
+    sc->need = plan.bytes;
     return L3AC_OK;
 }
 
@@ -377,8 +381,8 @@ int64_t lpc_frames(int64_t samples, int32_t frame, int32_t hop) {
 int64_t lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
     LpcGeom p;
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
-    L3AC_TRY(lpc_shape(batch, max_samples));
-    return align256((int64_t)batch * 4);  // the clips' lengths
+    L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
+    return ScratchPlan(batch).bytes;  // the clips' lengths
 }
 
 int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
@@ -386,18 +390,15 @@ int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t 
                double* autocorr, int32_t* valid, int32_t* frames, void* scratch, int64_t scratch_bytes) {
     LpcGeom p;
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
-    L3AC_TRY(lpc_shape(batch, max_samples));
+    L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
     const int64_t f_max = frames_of(max_samples, p);
     L3AC_REQUIRE(audio, "lpc: null audio");
     L3AC_REQUIRE(f_max == 0 || (a && reflection && error && autocorr && valid), "lpc: null output buffer");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "lpc: row stride %lld below max_samples %lld", (long long)audio_stride,
                  (long long)max_samples);
-    L3AC_TRY(check_clips("lpc", batch, max_samples, samples));
-    const int64_t need = align256((int64_t)batch * 4);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "lpc: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "lpc: scratch of %lld bytes is below l3ac_lpc_scratch_bytes = %lld", (long long)scratch_bytes, (long long)need);
-    int* lens = samples ? static_cast<int*>(scratch) : nullptr;
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
+    L3AC_TRY(check_clip_lengths("lpc", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "lpc", "lpc", samples, batch, scratch, scratch_bytes, ScratchPlan(batch).bytes, &lens));
     L3AC_TRY(configure_frame_kernel());
     // (no frame anywhere: one workgroup per clip still writes the frame counts)
     const int64_t groups = std::max<int64_t>(ceil_div64(f_max, p.g), 1);
@@ -411,22 +412,18 @@ int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t 
 
 int64_t lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
     LpcGeom p;
-    L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
-    L3AC_TRY(lpc_shape(batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, p);
-    L3AC_REQUIRE(f_max <= LQ_MAX_FRAMES, "lpc_metrics: %lld frames are more than the %d of a pair", (long long)f_max, LQ_MAX_FRAMES);
-    // the clips' lengths, the frames' four values [batch][F][4] fp64, the frames' flags [batch][F] int32
-    return align256((int64_t)batch * 4) + align256((int64_t)batch * f_max * 32) + align256((int64_t)batch * f_max * 4);
+    LpcMetricsScratch sc;
+    L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
+    return sc.need;
 }
 
 int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
                        const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
                        double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
                        int64_t scratch_bytes) {
-    const int64_t need = lpc_metrics_scratch_bytes(batch, max_samples, sample_rate, order, frame, hop);
-    if (need < 0) return L3AC_EINVAL;
     LpcGeom p;
-    L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
+    LpcMetricsScratch sc;
+    L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
     L3AC_REQUIRE(trim > 0.0 && trim <= 1.0, "lpc_metrics: trim %g outside (0, 1]", trim);
     L3AC_REQUIRE(llr_max >= 0.0 && std::isfinite(llr_max), "lpc_metrics: llr_max %g must be finite and not negative", llr_max);
     L3AC_REQUIRE(is_max >= 0.0 && std::isfinite(is_max), "lpc_metrics: is_max %g must be finite and not negative", is_max);
@@ -435,18 +432,13 @@ int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, cons
     L3AC_REQUIRE(out && counts, "lpc_metrics: null output buffer");
     L3AC_REQUIRE(batch == 1 || (ref_stride >= max_samples && est_stride >= max_samples), "lpc_metrics: row stride below max_samples %lld",
                  (long long)max_samples);
-    L3AC_TRY(check_clips("lpc_metrics", batch, max_samples, samples));
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "lpc_metrics: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "lpc_metrics: scratch of %lld bytes is below l3ac_lpc_metrics_scratch_bytes = %lld", (long long)scratch_bytes,
-                 (long long)need);
+    L3AC_TRY(check_clip_lengths("lpc_metrics", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "lpc_metrics", "lpc_metrics", samples, batch, scratch, scratch_bytes, sc.need, &lens));
     const int64_t f_max = frames_of(max_samples, p);
     char* base = static_cast<char*>(scratch);
-    const int64_t vals_off = align256((int64_t)batch * 4);
-    const int64_t flags_off = vals_off + align256((int64_t)batch * f_max * 32);
-    int* lens = samples ? reinterpret_cast<int*>(base) : nullptr;
-    double* vals = frame_values ? frame_values : reinterpret_cast<double*>(base + vals_off);
-    int* flags = reinterpret_cast<int*>(base + flags_off);
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
+    double* vals = frame_values ? frame_values : reinterpret_cast<double*>(base + sc.vals);
+    int* flags = reinterpret_cast<int*>(base + sc.flags);
     const LpcClamp cl{trim, llr_max, is_max, cd_max};
     if (f_max > 0) {
         L3AC_TRY(configure_frame_kernel());

@@ -26,7 +26,7 @@
 // on the DTW side, so a first call can be captured.
 //
 // Contraction is off for this whole file: the only fused operation is the fmaf that the cepstrum's chain is written in.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -43,8 +43,6 @@ constexpr int DTW_MAX_FRAMES = 4096;  // three fp64 anti-diagonals of this many 
 constexpr int DTW_MAX_DIM = 64;
 
 static_assert(3 * DTW_MAX_FRAMES * 8 <= 160 * 1024, "the three anti-diagonals live in one workgroup's LDS");
-
-int64_t align256(int64_t v) { return round_up64(v, 256); }
 
 // ---- cepstra: grid (blocks of (frame, q) cells, batch) ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CEP_THREADS) void mfcc_dct_kernel(const float* __restrict__ cells, const float* __restrict__ dct,
@@ -185,10 +183,35 @@ int cep_params(int32_t n_mels, int32_t n_coeffs) {
     return L3AC_OK;
 }
 
-int dtw_shape(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
+struct MfccScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t cells, mel, need;
+};
+
+// the parameters checked, then the cells [batch][F][n_mels] and log_mel's own scratch (as large as it says: not rounded up)
+int mfcc_scratch(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs, MfccScratch* sc) {
+    L3AC_TRY(cep_params(n_mels, n_coeffs));
+    const int64_t mel = mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
+    if (mel < 0) return L3AC_EINVAL;
+    ScratchPlan plan(batch);
+    sc->cells = plan.take((int64_t)batch * (1 + max_samples / hop) * n_mels * 4);
+    sc->mel = plan.last(mel);
+    sc->need = plan.bytes;
+    return L3AC_OK;
+}
+
+struct DtwScratch {  // byte offsets into the caller's scratch, after side a's frame counts
+    int64_t lens_b, choice, need;
+};
+
+// the shape checked (frame counts, not samples), then side b's frame counts and one choice byte per cell [batch][Fa_max][Fb_max]
+int dtw_scratch(int32_t batch, int32_t max_frames_a, int32_t max_frames_b, DtwScratch* sc) {
     L3AC_REQUIRE(batch > 0 && batch <= 65535, "dtw: batch %d outside 1..65535", batch);
     L3AC_REQUIRE(max_frames_a >= 1 && max_frames_a <= DTW_MAX_FRAMES, "dtw: max_frames_a %d outside 1..%d", max_frames_a, DTW_MAX_FRAMES);
     L3AC_REQUIRE(max_frames_b >= 1 && max_frames_b <= DTW_MAX_FRAMES, "dtw: max_frames_b %d outside 1..%d", max_frames_b, DTW_MAX_FRAMES);
+    ScratchPlan plan(batch);
+    sc->lens_b = plan.take((int64_t)batch * 4);
+    sc->choice = plan.take((int64_t)batch * max_frames_a * max_frames_b);
+    sc->need = plan.bytes;
     return L3AC_OK;
 }
 
@@ -209,34 +232,27 @@ int64_t dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) {
 }
 
 int64_t mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs) {
-    L3AC_TRY(cep_params(n_mels, n_coeffs));
-    const int64_t mel = mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
-    if (mel < 0) return mel;
-    // the clips' lengths, the cells [batch][F][n_mels], then log_mel's own scratch
-    return align256((int64_t)batch * 4) + align256((int64_t)batch * (1 + max_samples / hop) * n_mels * 4) + mel;
+    MfccScratch sc;
+    L3AC_TRY(mfcc_scratch(batch, max_samples, n_fft, hop, n_mels, n_coeffs, &sc));
+    return sc.need;
 }
 
 int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
                 int32_t hop, const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
                 int64_t scratch_bytes) {
-    const int64_t need = mfcc_scratch_bytes(batch, max_samples, n_fft, hop, n_mels, n_coeffs);
-    if (need < 0) return L3AC_EINVAL;
+    MfccScratch sc;
+    L3AC_TRY(mfcc_scratch(batch, max_samples, n_fft, hop, n_mels, n_coeffs, &sc));
     L3AC_REQUIRE(audio && out, "mfcc: null buffer");
     L3AC_REQUIRE(basis && weights && dct, "mfcc: null table (l3ac_stft_basis / l3ac_mel_weights / l3ac_dct_table, copied to the device)");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "mfcc: row stride below max_samples %lld", (long long)max_samples);
-    for (int i = 0; samples && i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "mfcc: samples[%d] = %d outside [1, %lld]", i, samples[i], (long long)max_samples);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "mfcc: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "mfcc: scratch of %lld bytes is below l3ac_mfcc_scratch_bytes = %lld", (long long)scratch_bytes, (long long)need);
+    L3AC_TRY(check_clip_lengths("mfcc", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "mfcc", "mfcc", samples, batch, scratch, scratch_bytes, sc.need, &lens));
     const int64_t frames = 1 + max_samples / hop;
     char* base = static_cast<char*>(scratch);
-    int* lens = samples ? reinterpret_cast<int*>(base) : nullptr;
-    const int64_t cells_off = align256((int64_t)batch * 4);
-    const int64_t mel_off = cells_off + align256((int64_t)batch * frames * n_mels * 4);
-    float* cells = reinterpret_cast<float*>(base + cells_off);
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
-    L3AC_TRY(launch_log_mel(s, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, cells, base + mel_off,
-                            scratch_bytes - mel_off));
+    float* cells = reinterpret_cast<float*>(base + sc.cells);
+    L3AC_TRY(launch_log_mel(s, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, cells, base + sc.mel,
+                            scratch_bytes - sc.mel));
     const int n_out = n_coeffs + 1;
     ProfScope prof(s, "mfcc_dct_kernel", 2.0 * batch * (double)frames * n_out * n_mels, 4.0 * batch * (double)frames * (n_mels + n_out));
     hipLaunchKernelGGL(mfcc_dct_kernel, dim3((unsigned)ceil_div64(frames * n_out, CEP_THREADS), (unsigned)batch), dim3(CEP_THREADS), 0, s, cells, dct,
@@ -246,15 +262,16 @@ int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_sa
 }
 
 int64_t dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
-    L3AC_TRY(dtw_shape(batch, max_frames_a, max_frames_b));
-    // the two sides' frame counts, then one choice byte per cell [batch][Fa_max][Fb_max]
-    return 2 * align256((int64_t)batch * 4) + align256((int64_t)batch * max_frames_a * max_frames_b);
+    DtwScratch sc;
+    L3AC_TRY(dtw_scratch(batch, max_frames_a, max_frames_b, &sc));
+    return sc.need;
 }
 
 int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride,
                int32_t batch, int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b,
                int32_t diagonal_only, double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes) {
-    L3AC_TRY(dtw_shape(batch, max_frames_a, max_frames_b));
+    DtwScratch sc;
+    L3AC_TRY(dtw_scratch(batch, max_frames_a, max_frames_b, &sc));
     L3AC_REQUIRE(dim >= 1 && dim <= DTW_MAX_DIM, "dtw: dim %d outside 1..%d", dim, DTW_MAX_DIM);
     L3AC_REQUIRE(a && b, "dtw: null features");
     L3AC_REQUIRE(cost && path_len, "dtw: null output buffer");
@@ -273,16 +290,12 @@ int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_
             L3AC_REQUIRE(fa == fb, "dtw: diagonal_only needs equal frame counts, pair %d has %d and %d", i, fa, fb);
         }
     }
-    const int64_t need = dtw_scratch_bytes(batch, max_frames_a, max_frames_b);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "dtw: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "dtw: scratch of %lld bytes is below l3ac_dtw_scratch_bytes = %lld", (long long)scratch_bytes, (long long)need);
+    int* lens_a;
+    L3AC_TRY(stage_clip_lengths(s, "dtw", "dtw", frames_a, batch, scratch, scratch_bytes, sc.need, &lens_a));
     char* base = static_cast<char*>(scratch);
-    const int64_t lens_bytes = align256((int64_t)batch * 4);
-    int* lens_a = frames_a ? reinterpret_cast<int*>(base) : nullptr;
-    int* lens_b = frames_b ? reinterpret_cast<int*>(base + lens_bytes) : nullptr;
-    if (lens_a) L3AC_TRY(launch_ragged_upload(s, lens_a, frames_a, batch));
+    int* lens_b = frames_b ? reinterpret_cast<int*>(base + sc.lens_b) : nullptr;
     if (lens_b) L3AC_TRY(launch_ragged_upload(s, lens_b, frames_b, batch));
-    unsigned char* choice = reinterpret_cast<unsigned char*>(base + 2 * lens_bytes);
+    unsigned char* choice = reinterpret_cast<unsigned char*>(base + sc.choice);
     const double cells = (double)batch * max_frames_a * max_frames_b;
     ProfScope prof(s, "dtw_kernel", 3.0 * dim * cells, (8.0 * dim + 1.0) * cells);
     hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)batch), dim3(DTW_THREADS), 0, s, a, a_frame_stride, a_row_stride, b, b_frame_stride, b_row_stride, dim,

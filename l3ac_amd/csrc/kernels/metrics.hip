@@ -17,7 +17,7 @@
 //             filters lane, lane + 64, ..., then a xor tree) into frame_sum[clip][f]; metrics_mean_kernel sums a clip's frames in a
 //             fixed order.  No atomics: nothing depends on the group size or on the batch.
 // signal_metrics_kernel: one workgroup per clip, two fp64 passes with fixed per-thread strides and a fixed tree.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,11 +37,9 @@ struct MelGeom {
     int64_t spec_ld;                            // n_fft + 4: 16-byte rows
 };
 
-struct MelScratch {  // byte offsets into the caller's scratch
-    int64_t lens, runs, frame_sum, stage, spec, total_min;
+struct MelScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t runs, frame_sum, stage, spec, total_min;
 };
-
-int64_t align256(int64_t v) { return round_up64(v, 256); }
 
 int mel_geom(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, bool mels, MelGeom* g, MelScratch* sc) {
     L3AC_REQUIRE(n_fft >= 16 && n_fft <= 2048 && n_fft % 16 == 0, "metrics: n_fft %d must be a multiple of 16 in 16..2048", n_fft);
@@ -63,17 +61,12 @@ int mel_geom(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int
     g->rows = (int64_t)(batch - 1) * g->slots + g->frames;
     g->spec_ld = n_fft + 4;
     L3AC_REQUIRE(g->rows < ((int64_t)1 << 31), "metrics: %lld frame rows in one call (batch %d) exceed 2^31", (long long)g->rows, batch);
-    int64_t off = 0;
-    sc->lens = off;
-    off += align256((int64_t)batch * 4);
-    sc->runs = off;
-    off += align256((int64_t)MT_MAX_MELS * 8);
-    sc->frame_sum = off;
-    off += align256((int64_t)batch * g->frames * 8);
-    sc->stage = off;
-    off += align256(2 * (int64_t)batch * g->pitch * 4);
-    sc->spec = off;
-    sc->total_min = off + 2 * std::min<int64_t>(MT_MIN_GROUP, g->rows) * g->spec_ld * 4;
+    ScratchPlan plan(batch);
+    sc->runs = plan.take((int64_t)MT_MAX_MELS * 8);
+    sc->frame_sum = plan.take((int64_t)batch * g->frames * 8);
+    sc->stage = plan.take(2 * (int64_t)batch * g->pitch * 4);
+    sc->spec = plan.last(2 * std::min<int64_t>(MT_MIN_GROUP, g->rows) * g->spec_ld * 4);
+    sc->total_min = plan.bytes;
     return L3AC_OK;
 }
 
@@ -189,20 +182,6 @@ __global__ __launch_bounds__(MT_THREADS) void metrics_mel_kernel(const float* __
     }
 }
 
-// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order; every thread gets the sum
-template <int THREADS>
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // the previous use of lds is over
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) s += lds[w];
-    return s;
-}
-
 // ---- a clip's distance: the mean of its F(n) frame sums over F(n) n_mels cells; one workgroup per clip ------------------------------------
 __global__ __launch_bounds__(MT_THREADS) void metrics_mean_kernel(const double* __restrict__ frame_sum, const int* __restrict__ lens,
                                                                 double* __restrict__ out, MelGeom g) {
@@ -263,14 +242,6 @@ __global__ __launch_bounds__(SM_THREADS) void signal_metrics_kernel(const float*
 
 enum MelMode { MODE_STFT, MODE_LOG_MEL, MODE_DISTANCE };
 
-int check_lengths(const int32_t* samples, int batch, int64_t max_samples) {
-    if (!samples) return L3AC_OK;
-    for (int i = 0; i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "metrics: samples[%d] = %d outside [1, %lld]", i, samples[i],
-                     (long long)max_samples);
-    return L3AC_OK;
-}
-
 int run_mel(hipStream_t s, MelMode mode, const float* x0, int64_t stride0, const float* x1, int64_t stride1, int32_t batch, int64_t max_samples,
             const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis, const float* weights, void* out,
             void* scratch, int64_t scratch_bytes) {
@@ -283,12 +254,10 @@ int run_mel(hipStream_t s, MelMode mode, const float* x0, int64_t stride0, const
     L3AC_REQUIRE(((uintptr_t)basis & 15) == 0, "metrics: the basis must be 16-byte aligned");
     L3AC_REQUIRE(batch == 1 || (stride0 >= max_samples && (n_sig == 1 || stride1 >= max_samples)), "metrics: row stride below max_samples %lld",
                  (long long)max_samples);
-    L3AC_TRY(check_lengths(samples, batch, max_samples));
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "metrics: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= sc.total_min, "metrics: scratch of %lld bytes is below l3ac_mel_scratch_bytes = %lld", (long long)scratch_bytes,
-                 (long long)sc.total_min);
+    L3AC_TRY(check_clip_lengths("metrics", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "metrics", "mel", samples, batch, scratch, scratch_bytes, sc.total_min, &lens));
     char* base = static_cast<char*>(scratch);
-    int* lens = samples ? reinterpret_cast<int*>(base + sc.lens) : nullptr;
     int2* runs = reinterpret_cast<int2*>(base + sc.runs);
     double* frame_sum = reinterpret_cast<double*>(base + sc.frame_sum);
     float* stage = reinterpret_cast<float*>(base + sc.stage);
@@ -297,7 +266,6 @@ int run_mel(hipStream_t s, MelMode mode, const float* x0, int64_t stride0, const
     const int64_t group = std::min<int64_t>(g.rows, (scratch_bytes - sc.spec) / (n_sig * g.spec_ld * 4));
     float* spec1 = spec + group * g.spec_ld;
 
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
     if (mode == MODE_STFT)
         L3AC_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * g.frames * g.bins * 2 * sizeof(float), s));
     if (mode == MODE_LOG_MEL)
@@ -424,7 +392,7 @@ int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, c
     L3AC_REQUIRE(max_samples < ((int64_t)1 << 31), "signal_metrics: clips of %lld samples are too long", (long long)max_samples);
     L3AC_REQUIRE(batch == 1 || (ref_stride >= max_samples && est_stride >= max_samples), "signal_metrics: row stride below max_samples %lld",
                  (long long)max_samples);
-    L3AC_TRY(check_lengths(samples, batch, max_samples));
+    L3AC_TRY(check_clip_lengths("metrics", samples, batch, max_samples));  // (this one message has always said "metrics")
     int* lens = nullptr;
     if (samples) {  // the clips' lengths live in the scratch: batch int32
         L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 3) == 0 && scratch_bytes >= (int64_t)batch * 4,

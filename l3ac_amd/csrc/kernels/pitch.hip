@@ -21,7 +21,7 @@
 // make NaN values in the frames that read them; every index is bounded by the parameters, whatever the values.
 //
 // Contraction is off for this whole file: the one fused operation, the fmaf of the difference function, is spelled out.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -45,8 +45,6 @@ struct PitchGeom {
     int g, pitch, lds_bytes;                    // frames per group, min(hop, span), dynamic LDS of the launch
     double threshold;
 };
-
-int64_t align256(int64_t v) { return round_up64(v, 256); }
 
 int lds_need(int g, int pitch, int span, int lags) { return (int)round_up64(((int64_t)(g - 1) * pitch + span) * 4, 8) + g * lags * 12; }
 
@@ -78,12 +76,6 @@ int pitch_geom(int32_t fs, double fmin, double fmax, int32_t window, int32_t hop
 }
 
 int64_t frames_of(int64_t n, const PitchGeom& p) { return n < p.span ? 0 : 1 + (n - p.span) / p.hop; }
-
-int pitch_shape(int32_t batch, int64_t max_samples) {
-    L3AC_REQUIRE(batch > 0 && batch <= 65535, "pitch: batch %d outside 1..65535", batch);
-    L3AC_REQUIRE(max_samples > 0 && max_samples < ((int64_t)1 << 31), "pitch: max_samples %lld outside 1..2^31 - 1", (long long)max_samples);
-    return L3AC_OK;
-}
 
 __device__ __forceinline__ int wave_min_int(int v) {
 #pragma unroll
@@ -248,19 +240,6 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_kernel(const float* __restri
     }
 }
 
-// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order; every thread gets the result
-__device__ __forceinline__ double pm_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // the previous use of lds is over
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < PM_THREADS / 64; ++w) s += lds[w];
-    return s;
-}
-
 // ---- the pair metrics: one workgroup per clip; the clips' frame counts (at most RaggedUpload::CAP, clips lens.offset ...) are arguments ----------
 __global__ __launch_bounds__(PM_THREADS) void pitch_metrics_kernel(const double* __restrict__ f0_ref, const int* __restrict__ v_ref,
                                                                  const double* __restrict__ f0_est, const int* __restrict__ v_est,
@@ -282,12 +261,12 @@ __global__ __launch_bounds__(PM_THREADS) void pitch_metrics_kernel(const double*
             sq += cents * cents;
         }
     }
-    n_ref = pm_block_sum(n_ref, lds);
-    n_est = pm_block_sum(n_est, lds);
-    n_both = pm_block_sum(n_both, lds);
-    n_flip = pm_block_sum(n_flip, lds);
-    n_gross = pm_block_sum(n_gross, lds);
-    sq = pm_block_sum(sq, lds);
+    n_ref = block_sum<PM_THREADS>(n_ref, lds);
+    n_est = block_sum<PM_THREADS>(n_est, lds);
+    n_both = block_sum<PM_THREADS>(n_both, lds);
+    n_flip = block_sum<PM_THREADS>(n_flip, lds);
+    n_gross = block_sum<PM_THREADS>(n_gross, lds);
+    sq = block_sum<PM_THREADS>(sq, lds);
     if (threadIdx.x == 0) {
         const double total = (double)frames;  // (0 / 0 is NaN: no frame, or no frame voiced on both sides)
         out[4 * (int64_t)b] = sqrt(sq / n_both);
@@ -321,8 +300,8 @@ int64_t pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double f
 int64_t pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
-    L3AC_TRY(pitch_shape(batch, max_samples));
-    return align256((int64_t)batch * 4);  // the clips' lengths
+    L3AC_TRY(check_clip_batch("pitch", batch, max_samples));
+    return ScratchPlan(batch).bytes;  // the clips' lengths
 }
 
 int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
@@ -332,20 +311,15 @@ int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(threshold > 0.0 && threshold < 1.0, "pitch: threshold %g outside (0, 1)", threshold);
     p.threshold = threshold;
-    L3AC_TRY(pitch_shape(batch, max_samples));
+    L3AC_TRY(check_clip_batch("pitch", batch, max_samples));
     const int64_t f_max = frames_of(max_samples, p);
     L3AC_REQUIRE(audio, "pitch: null audio");
     L3AC_REQUIRE(f_max == 0 || (f0 && voiced && aperiodicity), "pitch: null output buffer");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "pitch: row stride %lld below max_samples %lld", (long long)audio_stride,
                  (long long)max_samples);
-    for (int i = 0; samples && i < batch; ++i)
-        L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "pitch: samples[%d] = %d outside [1, %lld]", i, samples[i], (long long)max_samples);
-    const int64_t need = align256((int64_t)batch * 4);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "pitch: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= need, "pitch: scratch of %lld bytes is below l3ac_pitch_scratch_bytes = %lld", (long long)scratch_bytes,
-                 (long long)need);
-    int* lens = samples ? static_cast<int*>(scratch) : nullptr;
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
+    L3AC_TRY(check_clip_lengths("pitch", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "pitch", "pitch", samples, batch, scratch, scratch_bytes, ScratchPlan(batch).bytes, &lens));
     // (no frame anywhere: one workgroup per clip still writes the frame counts)
     const int64_t runs = std::max<int64_t>(ceil_div64(f_max, (int64_t)PT_GROUPS * p.g), 1);
     const double terms = (double)batch * (double)f_max * p.w * (p.t + 1);
@@ -364,16 +338,11 @@ int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voi
     L3AC_REQUIRE(max_frames == 0 || (f0_ref && voiced_ref && f0_est && voiced_est), "pitch_metrics: null track");
     for (int i = 0; frames && i < batch; ++i)
         L3AC_REQUIRE(frames[i] >= 0 && frames[i] <= max_frames, "pitch_metrics: frames[%d] = %d outside [0, %lld]", i, frames[i], (long long)max_frames);
-    const int group = frames ? RaggedUpload::CAP : batch;  // without frame counts one launch takes the whole batch
-    for (int off = 0; off < batch; off += group) {
-        RaggedUpload blk{};
-        blk.offset = off;
-        blk.n = std::min(group, batch - off);
-        for (int i = 0; frames && i < blk.n; ++i) blk.vals[i] = frames[off + i];
+    return for_each_length_group(frames, batch, [&](const RaggedUpload& blk) -> int {
         ProfScope prof(s, "pitch_metrics_kernel", 0.0, 24.0 * blk.n * (double)max_frames);
         hipLaunchKernelGGL(pitch_metrics_kernel, dim3((unsigned)blk.n), dim3(PM_THREADS), 0, s, f0_ref, voiced_ref, f0_est, voiced_est, max_frames,
                            frames ? 1 : 0, blk, out, counts);
         L3AC_LAUNCH_CHECK();
-    }
-    return L3AC_OK;
+        return L3AC_OK;
+    });
 }

@@ -18,7 +18,7 @@
 //                        per lane), both d_m in fp64: sums over frames are xor trees, sums over bands run in the lane.
 //   stoi_mean_kernel     one workgroup per clip: the d_m summed in a fixed order; the sentinel 1e-5 when T < 30.
 // Nothing depends on the batch, the clip's row, the row strides or the group of slot rows one product takes.
-#include "../kernels.hpp"
+#include "metric_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -45,11 +45,9 @@ struct StoiGeom {
     int64_t pitch, slots, rows;  // staged row (floats), pitch / 128, slot rows that hold a spectral frame of some clip
 };
 
-struct StoiScratch {  // byte offsets into the caller's scratch
-    int64_t lens, runs, kcount, level, kept, stage, bands, dseg, spec, total_min;
+struct StoiScratch {  // byte offsets into the caller's scratch, after the clips' lengths
+    int64_t runs, kcount, level, kept, stage, bands, dseg, spec, total_min;
 };
-
-int64_t st_align256(int64_t v) { return round_up64(v, 256); }
 
 __host__ __device__ inline int64_t st_frames(int64_t n) { return n <= ST_FRAME ? 0 : (n - ST_FRAME + ST_HOP - 1) / ST_HOP; }
 
@@ -67,25 +65,16 @@ int stoi_geom(int32_t batch, int64_t max_samples, StoiGeom* g, StoiScratch* sc) 
     g->slots = g->pitch / ST_HOP;
     g->rows = g->t_max ? (int64_t)(batch - 1) * g->slots + g->t_max : 0;
     L3AC_REQUIRE(g->rows < ((int64_t)1 << 31), "stoi: %lld frame rows in one call (batch %d) exceed 2^31", (long long)g->rows, batch);
-    int64_t off = 0;
-    sc->lens = off;
-    off += st_align256((int64_t)batch * 4);
-    sc->runs = off;
-    off += st_align256(2 * ST_BANDS * 4);
-    sc->kcount = off;
-    off += st_align256((int64_t)batch * 4);
-    sc->level = off;
-    off += st_align256((int64_t)batch * g->f_max * 8);
-    sc->kept = off;
-    off += st_align256((int64_t)batch * g->f_max * 4);
-    sc->stage = off;
-    off += st_align256(2 * (int64_t)batch * g->pitch * 4);
-    sc->bands = off;
-    off += st_align256(2 * (int64_t)batch * g->t_max * ST_BAND_LD * 4);
-    sc->dseg = off;
-    off += st_align256((int64_t)batch * g->seg_max * 2 * 8);
-    sc->spec = off;
-    sc->total_min = off + 2 * std::min<int64_t>(ST_MIN_GROUP, g->rows) * ST_SPEC_LD * 4;
+    ScratchPlan plan(batch);
+    sc->runs = plan.take(2 * ST_BANDS * 4);
+    sc->kcount = plan.take((int64_t)batch * 4);
+    sc->level = plan.take((int64_t)batch * g->f_max * 8);
+    sc->kept = plan.take((int64_t)batch * g->f_max * 4);
+    sc->stage = plan.take(2 * (int64_t)batch * g->pitch * 4);
+    sc->bands = plan.take(2 * (int64_t)batch * g->t_max * ST_BAND_LD * 4);
+    sc->dseg = plan.take((int64_t)batch * g->seg_max * 2 * 8);
+    sc->spec = plan.last(2 * std::min<int64_t>(ST_MIN_GROUP, g->rows) * ST_SPEC_LD * 4);
+    sc->total_min = plan.bytes;
     return L3AC_OK;
 }
 
@@ -307,19 +296,6 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_segment_kernel(const float* _
     }
 }
 
-// fixed tree over a workgroup's values: xor tree inside each wave, then the waves' results in wave order
-__device__ __forceinline__ double st_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // the previous use of lds is over
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < ST_THREADS / 64; ++w) s += lds[w];
-    return s;
-}
-
 // ---- a clip's values: the mean of its T - 29 segments, or the sentinel; one workgroup per clip -----------------------------------------------
 __global__ __launch_bounds__(ST_THREADS) void stoi_mean_kernel(const double* __restrict__ dseg, const int* __restrict__ kcount, double* __restrict__ out,
                                                              StoiGeom g) {
@@ -331,8 +307,8 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_mean_kernel(const double* __r
         a += dseg[((int64_t)b * g.seg_max + m) * 2];
         c += dseg[((int64_t)b * g.seg_max + m) * 2 + 1];
     }
-    a = st_block_sum(a, lds);
-    c = st_block_sum(c, lds);
+    a = block_sum<ST_THREADS>(a, lds);
+    c = block_sum<ST_THREADS>(c, lds);
     if (threadIdx.x == 0) {
         out[2 * (int64_t)b] = segs >= 1 ? a / (double)segs : ST_SENTINEL;
         out[2 * (int64_t)b + 1] = segs >= 1 ? c / (double)segs : ST_SENTINEL;
@@ -407,15 +383,10 @@ int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float
     L3AC_REQUIRE(basis && ((uintptr_t)basis & 15) == 0, "stoi: the basis (l3ac_stoi_basis, copied to the device) must be a 16-byte aligned buffer");
     L3AC_REQUIRE(batch == 1 || (ref_stride >= max_samples && est_stride >= max_samples), "stoi: row stride below max_samples %lld",
                  (long long)max_samples);
-    if (samples)
-        for (int i = 0; i < batch; ++i)
-            L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "stoi: samples[%d] = %d outside [1, %lld]", i, samples[i],
-                         (long long)max_samples);
-    L3AC_REQUIRE(scratch && ((uintptr_t)scratch & 255) == 0, "stoi: scratch must be a 256-byte aligned device buffer");
-    L3AC_REQUIRE(scratch_bytes >= sc.total_min, "stoi: scratch of %lld bytes is below l3ac_stoi_scratch_bytes = %lld", (long long)scratch_bytes,
-                 (long long)sc.total_min);
+    L3AC_TRY(check_clip_lengths("stoi", samples, batch, max_samples));
+    int* lens;
+    L3AC_TRY(stage_clip_lengths(s, "stoi", "stoi", samples, batch, scratch, scratch_bytes, sc.total_min, &lens));
     char* base = static_cast<char*>(scratch);
-    int* lens = samples ? reinterpret_cast<int*>(base + sc.lens) : nullptr;
     int* runs = reinterpret_cast<int*>(base + sc.runs);
     int* kcount = reinterpret_cast<int*>(base + sc.kcount);
     double* level = reinterpret_cast<double*>(base + sc.level);
@@ -426,7 +397,6 @@ int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float
     float* spec = reinterpret_cast<float*>(base + sc.spec);
     const float* window = basis;  // row 0: w[j] cos(0)
 
-    if (lens) L3AC_TRY(launch_ragged_upload(s, lens, samples, batch));
     if (g.f_max > 0) {
         ProfScope prof(s, "stoi_energy_kernel", 0.0, 4.0 * batch * (double)max_samples);
         hipLaunchKernelGGL(stoi_energy_kernel, dim3((unsigned)ceil_div64(g.f_max, ST_THREADS / 64), (unsigned)batch), dim3(ST_THREADS), 0, s, ref, ref_stride,

@@ -8,38 +8,26 @@ from typing import Optional
 
 import torch
 
-from . import _capi
+from . import _capi, _metric
 from ._rows import row_stride
-from .metrics import _audio, _lengths
 
 
 def loudness_coeffs(sample_rate: int):
     """The library's K-weighting at ``sample_rate`` -> ``(sos (2, 6), M (4, 4))`` fp64 on the CPU: the two biquads as rows
     ``b0 b1 b2 a0 a1 a2`` (``scipy.signal.sosfilt``'s layout), and the matrix that advances the cascade's state over one 100 ms step of
     zero input.  Raises ValueError for an unsupported rate (a multiple of 10 in 8000..192000 is supported)."""
-    lib = _capi.load_library()
-    n = lib.l3ac_loudness_coeffs(int(sample_rate), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    host = torch.empty(n, dtype=torch.float64)
-    lib.l3ac_loudness_coeffs(int(sample_rate), host.data_ptr(), n)
+    host = _metric.host_table("l3ac_loudness_coeffs", torch.float64, int(sample_rate))
     return host[:12].view(2, 6).clone(), host[12:].view(4, 4).clone()
 
 
 def loudness_blocks(samples: int, sample_rate: int) -> int:
     """Gating blocks (400 ms, every 100 ms) of a clip of ``samples`` samples: ``max(samples // (sample_rate // 10) - 3, 0)``.  Raises
     ValueError for samples < 1 or an unsupported rate."""
-    lib = _capi.load_library()
-    n = lib.l3ac_loudness_blocks(int(samples), int(sample_rate))
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    return int(n)
+    return _metric.lib_value("l3ac_loudness_blocks", int(samples), int(sample_rate))
 
 
 def _check_rate(sample_rate: int) -> None:
-    lib = _capi.load_library()
-    if lib.l3ac_loudness_blocks(1, sample_rate) < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    _metric.lib_value("l3ac_loudness_blocks", 1, sample_rate)
 
 
 def _finite(value, what: str) -> float:
@@ -75,24 +63,20 @@ def loudness(audio: torch.Tensor, sample_rate: int = 16000, lengths=None, return
     it is in.  No table is uploaded: the call can be captured without a warm-up.  No CPU path: CPU tensors raise."""
     sample_rate = int(sample_rate)
     _check_rate(sample_rate)
-    x = _audio(audio, "loudness")
+    x = _metric.audio(audio, "loudness")
     b, t = x.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     dev = x.device
-    lib = _capi.load_library()
-    need = lib.l3ac_loudness_scratch_bytes(b, t, sample_rate)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    need = _metric.lib_value("l3ac_loudness_scratch_bytes", b, t, sample_rate)
     stats = torch.empty((b, 2), dtype=torch.float64, device=dev)
     counts = torch.empty((b, 2), dtype=torch.int32, device=dev)
     momentary = torch.empty((b, loudness_blocks(t, sample_rate)), dtype=torch.float64, device=dev) if return_momentary else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)  # (the caching allocator hands out 512-byte aligned blocks)
-        _capi.check(lib.l3ac_loudness(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, stats.data_ptr(), counts.data_ptr(),
-                                      momentary.data_ptr() if return_momentary and momentary.numel() else None, scratch.data_ptr(),
-                                      scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    out = {"lufs": stats[:, 0].contiguous(), "peak": stats[:, 1].contiguous(), "blocks": counts[:, 0].contiguous(),
-           "gated": counts[:, 1].contiguous()}
+        scratch = _metric.scratch(dev, need)
+        _capi.check(_capi.load_library().l3ac_loudness(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, stats.data_ptr(), counts.data_ptr(),
+                                                       momentary.data_ptr() if return_momentary and momentary.numel() else None,
+                                                       scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
+    out = dict(_metric.columns(stats, ("lufs", "peak")), **_metric.columns(counts, ("blocks", "gated")))
     if return_momentary:
         out["momentary"] = momentary
     return out
@@ -122,9 +106,8 @@ def loudness_gain(stats: dict, target_lufs: float = -23.0, peak_limit_db: Option
     packed = torch.stack((lufs, peak), dim=1).contiguous()
     gain = torch.empty((b, 2), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _capi.check(_capi.load_library().l3ac_loudness_gain(packed.data_ptr(), b, target, limit, gain.data_ptr(),
-                                                            torch.cuda.current_stream(dev).cuda_stream))
-    return {"gain_db": gain[:, 0].contiguous(), "gain": gain[:, 1].contiguous()}
+        _capi.check(_capi.load_library().l3ac_loudness_gain(packed.data_ptr(), b, target, limit, gain.data_ptr(), _metric.stream(dev)))
+    return _metric.columns(gain, ("gain_db", "gain"))
 
 
 @torch.no_grad()
@@ -132,7 +115,7 @@ def apply_gain(audio: torch.Tensor, gain: torch.Tensor, lengths=None) -> torch.T
     """(B, T) fp32 CUDA audio times a per-clip linear ``gain`` (B,) fp64 CUDA (``loudness_gain(...)["gain"]``, or its reciprocal to
     undo it after decoding) -> a new (B, T) fp32: ``float(double(x) * gain)``, one rounding.  ``lengths``: samples at or after a clip's
     length come out as zero."""
-    x = _audio(audio, "apply_gain")
+    x = _metric.audio(audio, "apply_gain")
     b, t = x.shape
     if not isinstance(gain, torch.Tensor) or not gain.is_cuda:
         raise RuntimeError("apply_gain needs a CUDA tensor gain: l3ac_amd has no CPU path")
@@ -140,12 +123,12 @@ def apply_gain(audio: torch.Tensor, gain: torch.Tensor, lengths=None) -> torch.T
         raise ValueError(f"gain must be ({b},), got {tuple(gain.shape)}")
     if gain.device != x.device:
         raise RuntimeError(f"apply_gain: audio is on {x.device} but gain is on {gain.device}")
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     g = gain.to(torch.float64)
     out = torch.empty((b, t), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _capi.check(_capi.load_library().l3ac_apply_gain(x.data_ptr(), row_stride(x), out.data_ptr(), row_stride(out), b, t, c_lens, g.data_ptr(),
-                                                         g.stride(0) if b > 1 else 1, torch.cuda.current_stream(x.device).cuda_stream))
+                                                         g.stride(0) if b > 1 else 1, _metric.stream(x.device)))
     return out
 
 

@@ -9,9 +9,8 @@ from typing import Optional
 
 import torch
 
-from . import _capi
-from ._rows import int_list, row_stride
-from .metrics import _audio, _table
+from . import _capi, _metric
+from ._rows import row_stride
 
 MAX_FRAMES = 16384  # the most frames a pair of ``lpc_metrics`` may have
 WINDOWS = ("hann", "rect")
@@ -20,37 +19,25 @@ WINDOWS = ("hann", "rect")
 def lpc_window(frame: int) -> torch.Tensor:
     """The library's analysis window (frame,) fp32 on the CPU: ``w[i] = 0.5 (1 - cos(2 pi (i + 1) / (frame + 1)))``, the asymmetric Hann
     form of the published measures, designed in fp64 and rounded once.  Raises ValueError for ``frame`` outside 2..8192."""
-    lib = _capi.load_library()
-    n = lib.l3ac_lpc_window(int(frame), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    host = torch.empty(n, dtype=torch.float32)
-    lib.l3ac_lpc_window(int(frame), host.data_ptr(), n)
-    return host
+    return _metric.host_table("l3ac_lpc_window", torch.float32, int(frame))
 
 
 def lpc_defaults(sample_rate: int) -> tuple:
     """``(order, frame, hop)`` at ``sample_rate``: order 10 below 10 kHz, else 16; a 30 ms frame, ``(30 fs + 500) // 1000`` samples; a hop
     of ``frame // 4``.  Raises ValueError for a rate outside 8000..192000."""
     out = (ctypes.c_int32 * 3)()
-    lib = _capi.load_library()
     try:
         rate = int(sample_rate)
     except (TypeError, ValueError):
         raise ValueError("lpc: sample_rate must be an integer") from None
-    if lib.l3ac_lpc_defaults(rate, out) != 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    _metric.lib_value("l3ac_lpc_defaults", rate, out)
     return int(out[0]), int(out[1]), int(out[2])
 
 
 def lpc_frames(samples: int, frame: int, hop: int) -> int:
     """Frames of a clip of ``samples`` samples: 0 below ``frame``, else ``1 + (samples - frame) // hop``.  Frame t reads samples
     ``[t hop, t hop + frame)``.  Raises ValueError for samples < 0, ``frame`` outside 2..8192 or hop < 1."""
-    lib = _capi.load_library()
-    n = lib.l3ac_lpc_frames(int(samples), int(frame), int(hop))
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    return int(n)
+    return _metric.lib_value("l3ac_lpc_frames", int(samples), int(frame), int(hop))
 
 
 def _check_params(sample_rate, order=None, frame=None, hop=None, window="hann") -> tuple:
@@ -63,36 +50,20 @@ def _check_params(sample_rate, order=None, frame=None, hop=None, window="hann") 
         hop = frame // 4 if hop is None else int(hop)
     except (TypeError, ValueError):
         raise ValueError("lpc: order, frame and hop must be integers") from None
-    lib = _capi.load_library()
-    if lib.l3ac_lpc_scratch_bytes(1, 1, int(sample_rate), order, frame, hop) < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    _metric.lib_value("l3ac_lpc_scratch_bytes", 1, 1, int(sample_rate), order, frame, hop)
     if window not in WINDOWS:
         raise ValueError(f"lpc: window {window!r} is not one of {WINDOWS}")
     return int(sample_rate), order, frame, hop
 
 
-def _shape(x, what: str) -> tuple:
-    if isinstance(x, torch.Tensor):
-        if x.dim() != 2:
-            raise ValueError(f"{what} must be (batch, samples), got {tuple(x.shape)}")
-        if x.shape[0] == 0 or x.shape[1] == 0:
-            raise ValueError("empty audio")
-        return tuple(x.shape)
-    return None
-
-
 def _clip_lengths(lengths, shape):
-    """``lengths=`` checked against a shape that is known -> (Python ints or None, the ctypes array the library takes or None)."""
-    if lengths is None or shape is None:
-        return None, None
-    b, t = shape
-    lens = int_list(lengths, b, 1, t, "lengths", f"a batch of {b}")
-    return lens, (ctypes.c_int32 * b)(*lens)
+    """``lengths=`` checked against a shape that is known (``_metric.shape``: before the device is) -> as ``_metric.lengths``."""
+    return (None, None) if shape is None else _metric.lengths(lengths, *shape)
 
 
 def _window(dev, window: str, frame: int):
     """The device copy of the window, uploaded by the first eager call; None for the rectangular window."""
-    return None if window == "rect" else _table(dev, ("lpc_window", frame), lambda: lpc_window(frame))
+    return None if window == "rect" else _metric.table(dev, ("lpc_window", frame), lambda: lpc_window(frame))
 
 
 @torch.no_grad()
@@ -110,14 +81,11 @@ def lpc(audio: torch.Tensor, sample_rate: int = 16000, order: Optional[int] = No
     own frames hold NaN / 0.  A clip's bits do not depend on the batch it is in; ``extra_scratch``: bytes to allocate above the minimum
     scratch (the result does not depend on it).  Capturable after one eager call (the window).  No CPU path: CPU tensors raise."""
     rate, p, n, hop = _check_params(sample_rate, order, frame, hop, window)
-    lens, c_lens = _clip_lengths(lengths, _shape(audio, "lpc"))
-    x = _audio(audio, "lpc")
+    lens, c_lens = _clip_lengths(lengths, _metric.shape(audio, "lpc"))
+    x = _metric.audio(audio, "lpc")
     b, t = x.shape
     dev = x.device
-    lib = _capi.load_library()
-    need = lib.l3ac_lpc_scratch_bytes(b, t, rate, p, n, hop)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    need = _metric.lib_value("l3ac_lpc_scratch_bytes", b, t, rate, p, n, hop)
     f_max = lpc_frames(t, n, hop)
     win = _window(dev, window, n)
     a = torch.empty((b, f_max, p + 1), dtype=torch.float64, device=dev)
@@ -128,10 +96,10 @@ def lpc(audio: torch.Tensor, sample_rate: int = 16000, order: Optional[int] = No
     frames = torch.empty(b, dtype=torch.int32, device=dev)
     ptr = (lambda v: v.data_ptr()) if f_max else (lambda v: None)
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + (0 if extra_scratch is None else max(0, int(extra_scratch))), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_lpc(x.data_ptr(), row_stride(x), b, t, c_lens, rate, p, n, hop, None if win is None else win.data_ptr(), ptr(a),
-                                 ptr(refl), ptr(err), ptr(r), ptr(valid), frames.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                 torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.scratch(dev, need, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_lpc(x.data_ptr(), row_stride(x), b, t, c_lens, rate, p, n, hop, None if win is None else win.data_ptr(),
+                                                  ptr(a), ptr(refl), ptr(err), ptr(r), ptr(valid), frames.data_ptr(), scratch.data_ptr(),
+                                                  scratch.numel(), _metric.stream(dev)))
     return {"a": a, "reflection": refl, "error": err, "autocorr": r, "valid": valid, "frames": frames}
 
 
@@ -167,21 +135,18 @@ def lpc_metrics(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: in
     Other parameters, the bit guarantee and stream capture as ``lpc``."""
     rate, p, n, hop = _check_params(sample_rate, order, frame, hop, window)
     trim, llr_max, is_max, cd_max = _check_metric_params(trim, llr_max, is_max, cd_max)
-    shape_r, shape_e = _shape(reference, "lpc_metrics"), _shape(estimate, "lpc_metrics")
+    shape_r, shape_e = _metric.shape(reference, "lpc_metrics"), _metric.shape(estimate, "lpc_metrics")
     if shape_r is not None and shape_e is not None and shape_r != shape_e:
         raise ValueError(f"lpc_metrics: reference {shape_r} and estimate {shape_e} differ in shape")
     lens, c_lens = _clip_lengths(lengths, shape_r)
     if shape_r is not None and lpc_frames(shape_r[1], n, hop) > MAX_FRAMES:
         raise ValueError(f"lpc_metrics: {lpc_frames(shape_r[1], n, hop)} frames are more than the {MAX_FRAMES} of a pair")
-    r, e = _audio(reference, "lpc_metrics"), _audio(estimate, "lpc_metrics")
+    r, e = _metric.audio(reference, "lpc_metrics"), _metric.audio(estimate, "lpc_metrics")
     if r.device != e.device:
         raise RuntimeError(f"lpc_metrics: reference is on {r.device} but estimate is on {e.device}")
     b, t = r.shape
     dev = r.device
-    lib = _capi.load_library()
-    need = lib.l3ac_lpc_metrics_scratch_bytes(b, t, rate, p, n, hop)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    need = _metric.lib_value("l3ac_lpc_metrics_scratch_bytes", b, t, rate, p, n, hop)
     f_max = lpc_frames(t, n, hop)
     win = _window(dev, window, n)
     out = torch.empty((b, 4), dtype=torch.float64, device=dev)
@@ -189,15 +154,13 @@ def lpc_metrics(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: in
     vals = torch.empty((b, f_max, 4), dtype=torch.float64, device=dev) if return_frames else None
     forms = torch.empty((b, f_max, 5), dtype=torch.float64, device=dev) if return_frames else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + (0 if extra_scratch is None else max(0, int(extra_scratch))), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_lpc_metrics(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, rate, p, n, hop,
-                                         None if win is None else win.data_ptr(), trim, llr_max, is_max, cd_max, out.data_ptr(), counts.data_ptr(),
-                                         vals.data_ptr() if return_frames and f_max else None, forms.data_ptr() if return_frames and f_max else None,
-                                         scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    res = {"llr": out[:, 0].contiguous(), "is_distance": out[:, 1].contiguous(), "cepstral_distance_db": out[:, 2].contiguous(),
-           "seg_snr_db": out[:, 3].contiguous(), "frames": counts[:, 0].contiguous(), "lpc_frames": counts[:, 1].contiguous(),
-           "snr_frames": counts[:, 2].contiguous()}
+        scratch = _metric.scratch(dev, need, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_lpc_metrics(
+            r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, rate, p, n, hop, None if win is None else win.data_ptr(), trim,
+            llr_max, is_max, cd_max, out.data_ptr(), counts.data_ptr(), vals.data_ptr() if return_frames and f_max else None,
+            forms.data_ptr() if return_frames and f_max else None, scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
+    res = dict(_metric.columns(out, ("llr", "is_distance", "cepstral_distance_db", "seg_snr_db")),
+               **_metric.columns(counts, ("frames", "lpc_frames", "snr_frames")))
     if return_frames:
-        res.update({"llr_frames": vals[..., 0].contiguous(), "is_frames": vals[..., 1].contiguous(), "cd_frames": vals[..., 2].contiguous(),
-                    "seg_snr_frames": vals[..., 3].contiguous(), "forms": forms})
+        res.update(_metric.columns(vals, ("llr_frames", "is_frames", "cd_frames", "seg_snr_frames")), forms=forms)
     return res

@@ -9,9 +9,9 @@ from typing import Optional
 
 import torch
 
-from . import _capi
+from . import _capi, _metric
 from ._rows import int_list, row_stride
-from .metrics import _audio, _check_params, _extra_bytes, _lengths, _table, mel_weights, stft_basis, stft_frames
+from .metrics import mel_weights, stft_basis, stft_frames
 
 MAX_FRAMES = 4096  # the most frames a side of a DTW pair may have
 MAX_DIM = 64       # the widest feature row of ``dtw``; also the most cepstral coefficients (``n_coeffs``)
@@ -21,13 +21,7 @@ MCD_SCALE = 5.0 * math.sqrt(2.0)  # 10 sqrt(2) / ln 10 on cepstra of the natural
 def dct_table(n_mels: int, n_coeffs: int) -> torch.Tensor:
     """The library's orthonormal DCT-II table (n_coeffs + 1, n_mels) fp32 on the CPU: row 0 = sqrt(1 / M), row q = sqrt(2 / M) cos(pi q
     (m + 1/2) / M), designed in fp64 and rounded once.  Raises ValueError for ``n_coeffs`` outside 1..min(n_mels - 1, 64)."""
-    lib = _capi.load_library()
-    n = lib.l3ac_dct_table(int(n_mels), int(n_coeffs), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    host = torch.empty(n, dtype=torch.float32)
-    lib.l3ac_dct_table(int(n_mels), int(n_coeffs), host.data_ptr(), n)
-    return host.view(int(n_coeffs) + 1, int(n_mels))
+    return _metric.host_table("l3ac_dct_table", torch.float32, int(n_mels), int(n_coeffs)).view(int(n_coeffs) + 1, int(n_mels))
 
 
 def _mfcc_hop(n_fft: int, hop) -> int:
@@ -39,29 +33,23 @@ def _mfcc_hop(n_fft: int, hop) -> int:
 
 def _check_mfcc_params(sample_rate: int, n_fft: int, hop: int, n_mels: int, n_coeffs: int) -> None:
     """The supported parameters, checked by the library before any device work: ValueError with its message."""
-    _check_params(sample_rate, n_fft, hop, n_mels)
-    lib = _capi.load_library()
-    if lib.l3ac_dct_table(n_mels, n_coeffs, None, 0) < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    _metric.check_mel_params(sample_rate, n_fft, hop, n_mels)
+    _metric.lib_value("l3ac_dct_table", n_mels, n_coeffs, None, 0)
 
 
 def _mfcc(x: torch.Tensor, sample_rate: int, n_fft: int, hop: int, n_mels: int, n_coeffs: int, c_lens, extra_scratch) -> torch.Tensor:
     b, t = x.shape
     dev = x.device
-    lib = _capi.load_library()
-    basis = _table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
-    weights = _table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
-    dct = _table(dev, ("dct", n_mels, n_coeffs), lambda: dct_table(n_mels, n_coeffs))
+    basis = _metric.table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
+    weights = _metric.table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
+    dct = _metric.table(dev, ("dct", n_mels, n_coeffs), lambda: dct_table(n_mels, n_coeffs))
     out = torch.empty((b, stft_frames(t, hop), n_coeffs + 1), dtype=torch.float32, device=dev)
-    need = lib.l3ac_mfcc_scratch_bytes(b, t, n_fft, hop, n_mels, n_coeffs)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    need = _metric.lib_value("l3ac_mfcc_scratch_bytes", b, t, n_fft, hop, n_mels, n_coeffs)
     with torch.cuda.device(dev):
         # the minimum — the lengths, the cells, log_mel's own scratch — and log_mel's extra room for larger products
-        scratch = torch.empty(int(need) + _extra_bytes(b, t, n_fft, hop, extra_scratch), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_mfcc(x.data_ptr(), b, t, row_stride(x), c_lens, n_fft, hop, basis.data_ptr(), weights.data_ptr(), n_mels,
-                                  dct.data_ptr(), n_coeffs, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                  torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.mel_scratch(dev, need, b, t, n_fft, hop, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_mfcc(x.data_ptr(), b, t, row_stride(x), c_lens, n_fft, hop, basis.data_ptr(), weights.data_ptr(), n_mels,
+                                                   dct.data_ptr(), n_coeffs, out.data_ptr(), scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     return out
 
 
@@ -76,8 +64,8 @@ def mfcc(audio: torch.Tensor, sample_rate: int = 16000, n_fft: int = 512, hop: O
     tables are uploaded by the first eager call)."""
     sample_rate, n_fft, hop, n_mels, n_coeffs = int(sample_rate), int(n_fft), _mfcc_hop(n_fft, hop), int(n_mels), int(n_coeffs)
     _check_mfcc_params(sample_rate, n_fft, hop, n_mels, n_coeffs)
-    x = _audio(audio, "mfcc")
-    lens, c_lens = _lengths(lengths, x.shape[0], x.shape[1])
+    x = _metric.audio(audio, "mfcc")
+    lens, c_lens = _metric.lengths(lengths, x.shape[0], x.shape[1])
     out = _mfcc(x, sample_rate, n_fft, hop, n_mels, n_coeffs, c_lens, extra_scratch)
     if lens is None:
         return out
@@ -143,20 +131,17 @@ def dtw(a: torch.Tensor, b: torch.Tensor, lengths_a=None, lengths_b=None, return
         raise RuntimeError(f"dtw: a is on {a.device} but b is on {b.device}")
     a, b = _rows_view(a), _rows_view(b)
     dev = a.device
-    lib = _capi.load_library()
-    need = lib.l3ac_dtw_scratch_bytes(n, fa, fb)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    cost = torch.empty(n, dtype=torch.float64, device=dev)
+    need = _metric.lib_value("l3ac_dtw_scratch_bytes", n, fa, fb)
+    cost =torch.empty(n, dtype=torch.float64, device=dev)
     steps = torch.empty(n, dtype=torch.int32, device=dev)
     path = torch.empty((n, fa + fb - 1, 2), dtype=torch.int32, device=dev) if return_path else None
     delta = torch.zeros((n, fa, fb), dtype=torch.float64, device=dev) if return_cost_matrix else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + (0 if extra_scratch is None else max(0, int(extra_scratch))), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_dtw(a.data_ptr(), a.stride(1), a.stride(0), b.data_ptr(), b.stride(1), b.stride(0), n, dim, fa, fb, c_a, c_b,
-                                 1 if diagonal_only else 0, cost.data_ptr(), steps.data_ptr(), path.data_ptr() if return_path else None,
-                                 delta.data_ptr() if return_cost_matrix else None, scratch.data_ptr(), scratch.numel(),
-                                 torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.scratch(dev, need, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_dtw(a.data_ptr(), a.stride(1), a.stride(0), b.data_ptr(), b.stride(1), b.stride(0), n, dim, fa, fb, c_a,
+                                                  c_b, 1 if diagonal_only else 0, cost.data_ptr(), steps.data_ptr(),
+                                                  path.data_ptr() if return_path else None, delta.data_ptr() if return_cost_matrix else None,
+                                                  scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     out = {"cost": cost, "path_length": steps}
     if return_path:
         out["path"] = path
@@ -169,14 +154,13 @@ _dtw = dtw  # (``mcd`` has a parameter of that name)
 
 
 def _sides(reference, estimate):
-    for x, name in ((reference, "reference"), (estimate, "estimate")):
-        if isinstance(x, torch.Tensor) and x.dim() != 2:
-            raise ValueError(f"mcd: {name} must be (batch, samples), got {tuple(x.shape)}")
-    if isinstance(reference, torch.Tensor) and isinstance(estimate, torch.Tensor):
-        if reference.shape[0] != estimate.shape[0]:
-            raise ValueError(f"mcd: reference {tuple(reference.shape)} and estimate {tuple(estimate.shape)} differ in batch")
-        return reference.shape[0], reference.shape[1], estimate.shape[1]
-    return None
+    """(batch, Tr, Te) of two tensors, checked before their devices are; None when a side is not a tensor."""
+    shape_r, shape_e = _metric.shape(reference, "mcd: reference", empty_ok=True), _metric.shape(estimate, "mcd: estimate", empty_ok=True)
+    if shape_r is None or shape_e is None:
+        return None
+    if shape_r[0] != shape_e[0]:
+        raise ValueError(f"mcd: reference {shape_r} and estimate {shape_e} differ in batch")
+    return shape_r[0], shape_r[1], shape_e[1]
 
 
 @torch.no_grad()
@@ -210,7 +194,7 @@ def mcd(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: int = 1600
         frames_r, frames_e = [1 + v // hop for v in lens_r], [1 + v // hop for v in lens_e]
         if not dtw and frames_r != frames_e:
             raise ValueError(f"mcd: dtw=False needs equal frame counts in every pair, got {frames_r} and {frames_e}")
-    r, e = _audio(reference, "mcd"), _audio(estimate, "mcd")
+    r, e = _metric.audio(reference, "mcd"), _metric.audio(estimate, "mcd")
     if r.device != e.device:
         raise RuntimeError(f"mcd: reference is on {r.device} but estimate is on {e.device}")
     c_r = _mfcc(r, sample_rate, n_fft, hop, n_mels, n_coeffs, None if lengths is None else (ctypes.c_int32 * n)(*lens_r), extra_scratch)

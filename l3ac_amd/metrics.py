@@ -1,5 +1,5 @@
 """Quality metrics on the GPU (csrc/kernels/metrics.hip): ``stft``, ``log_mel``, ``mel_distance`` and
-``signal_metrics``, and the per-device cache of the library's two fp32 tables (the window-folded DFT basis and the mel weights); and
+``signal_metrics``, and the library's two fp32 tables (the window-folded DFT basis and the mel weights; ``_metric.py`` caches the device copies); and
 speech intelligibility (csrc/kernels/stoi.hip, section 3.13): ``stoi`` and its host accessors."""
 from __future__ import annotations
 
@@ -8,100 +8,32 @@ from typing import Optional
 
 import torch
 
-from . import _capi
-from ._rows import contiguous_rows, int_list, row_stride, zero_after
+from . import _capi, _metric
+from ._metric import check_mel_params as _check_params, tables as _tables  # noqa: F401 (the package and the tests use these names)
+from ._rows import row_stride, zero_after
 from .resampling import resample, resample_length
 
 DEFAULT_SCALES = ((256, 64, 20), (512, 128, 40), (1024, 256, 80), (2048, 512, 80))  # (n_fft, hop, n_mels) at 16 kHz
 
-# bytes a call allocates above the minimum scratch: spectra of more frames per product (the results do not depend on it)
-_EXTRA_SCRATCH = 64 << 20
-
 
 def stft_frames(samples: int, hop: int) -> int:
     """Frames of a clip of ``samples`` samples: 1 + samples // hop.  Raises ValueError for samples < 1 or hop < 1."""
-    n = _capi.load_library().l3ac_stft_frames(int(samples), int(hop))
-    if n < 0:
-        raise ValueError(_capi.load_library().l3ac_last_error().decode())
-    return int(n)
+    return _metric.lib_value("l3ac_stft_frames", int(samples), int(hop))
 
 
 def stft_basis(n_fft: int) -> torch.Tensor:
     """The library's window-folded DFT basis (n_fft + 2, n_fft) fp32 on the CPU: row 2k = w cos, row 2k + 1 = -w sin."""
-    lib = _capi.load_library()
-    n = lib.l3ac_stft_basis(int(n_fft), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    host = torch.empty(n, dtype=torch.float32)
-    lib.l3ac_stft_basis(int(n_fft), host.data_ptr(), n)
-    return host.view(int(n_fft) + 2, int(n_fft))
+    return _metric.host_table("l3ac_stft_basis", torch.float32, int(n_fft)).view(int(n_fft) + 2, int(n_fft))
 
 
 def mel_weights(sample_rate: int, n_fft: int, n_mels: int) -> torch.Tensor:
     """The library's mel weights (n_mels, n_fft // 2 + 1) fp32 on the CPU: HTK scale, triangles, no normalisation."""
-    lib = _capi.load_library()
-    n = lib.l3ac_mel_weights(int(sample_rate), int(n_fft), int(n_mels), None, 0)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    host = torch.empty(n, dtype=torch.float32)
-    lib.l3ac_mel_weights(int(sample_rate), int(n_fft), int(n_mels), host.data_ptr(), n)
-    return host.view(int(n_mels), int(n_fft) // 2 + 1)
-
-
-# (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "dct", n_mels, n_coeffs: mcd.py) /
-# (device, "lpc_window", frame: lpc.py) -> device copy of the table
-_tables = {}
-
-
-def _table(device: torch.device, key: tuple, make) -> torch.Tensor:
-    key = (device,) + key
-    if key not in _tables:
-        if torch.cuda.is_current_stream_capturing():
-            # uploading the table would be a host -> device copy inside the graph; the eager warm-up call before capture fills the cache
-            raise RuntimeError(f"metrics: the table {key[1:]} is not on {device} yet; run the call once outside stream capture (the "
-                               "warm-up call before graph capture) to upload it")
-        _tables[key] = make().to(device)
-    return _tables[key]
-
-
-def _check_params(sample_rate: int, n_fft: int, hop: int, n_mels: int) -> None:
-    """The supported parameters, checked by the library before any device work: ValueError with its message."""
-    lib = _capi.load_library()
-    if lib.l3ac_mel_weights(sample_rate, n_fft, n_mels, None, 0) < 0 or lib.l3ac_mel_scratch_bytes(1, 1, n_fft, hop, n_mels) < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-
-
-def _audio(x, what: str) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError(f"{what} needs a CUDA tensor: l3ac_amd has no CPU path")
-    if x.dim() != 2:
-        raise ValueError(f"{what} must be (batch, samples), got {tuple(x.shape)}")
-    if x.shape[0] == 0 or x.shape[1] == 0:
-        raise ValueError("empty audio")
-    return contiguous_rows(x.to(torch.float32))
-
-
-def _lengths(lengths, b: int, t: int):
-    """``lengths=`` -> (Python ints or None, the ctypes array the library takes or None)."""
-    if lengths is None:
-        return None, None
-    lens = int_list(lengths, b, 1, t, "lengths", f"a batch of {b}")  # (ragged_lengths of the package: the same check)
-    return lens, (ctypes.c_int32 * b)(*lens)
-
-
-def _extra_bytes(b: int, t: int, n_fft: int, hop: int, extra_scratch) -> int:
-    """Bytes a call allocates above the minimum scratch."""
-    if extra_scratch is None:  # the default, never more than the spectra of every frame row of both signals
-        return min(_EXTRA_SCRATCH, 2 * b * (t // hop + n_fft // hop + 2) * (n_fft + 4) * 4)
-    return max(0, int(extra_scratch))
+    return _metric.host_table("l3ac_mel_weights", torch.float32, int(sample_rate), int(n_fft), int(n_mels)).view(int(n_mels), int(n_fft) // 2 + 1)
 
 
 def _scratch(dev, b: int, t: int, n_fft: int, hop: int, n_mels: int, extra_scratch) -> torch.Tensor:
-    need = _capi.load_library().l3ac_mel_scratch_bytes(b, t, n_fft, hop, n_mels)
-    if need < 0:
-        raise ValueError(_capi.load_library().l3ac_last_error().decode())
-    extra = _extra_bytes(b, t, n_fft, hop, extra_scratch)
-    return torch.empty(int(need) + extra, dtype=torch.uint8, device=dev)  # (the caching allocator hands out 512-byte aligned blocks)
+    need = _metric.lib_value("l3ac_mel_scratch_bytes", b, t, n_fft, hop, n_mels)
+    return _metric.mel_scratch(dev, need, b, t, n_fft, hop, extra_scratch)
 
 
 def _hop(n_fft: int, hop) -> int:
@@ -118,16 +50,16 @@ def stft(audio: torch.Tensor, n_fft: int, hop: Optional[int] = None, lengths=Non
     No CPU path: CPU tensors raise.  Under stream capture a table that is not on the device yet raises (run one eager call first)."""
     n_fft, hop = int(n_fft), _hop(n_fft, hop)
     _check_params(1, n_fft, hop, 1)
-    x = _audio(audio, "stft")
+    x = _metric.audio(audio, "stft")
     b, t = x.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     dev = x.device
-    basis = _table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
+    basis = _metric.table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
     spec = torch.empty((b, stft_frames(t, hop), n_fft // 2 + 1, 2), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         scratch = _scratch(dev, b, t, n_fft, hop, 1, extra_scratch)
         _capi.check(_capi.load_library().l3ac_stft(x.data_ptr(), b, t, row_stride(x), c_lens, n_fft, hop, basis.data_ptr(), spec.data_ptr(),
-                                                   scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
+                                                   scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     return torch.view_as_complex(spec)
 
 
@@ -139,30 +71,20 @@ def log_mel(audio: torch.Tensor, sample_rate: int = 16000, n_fft: int = 1024, ho
     (int32, on the CPU); the rows after a clip's own frames are zero.  Other arguments as ``stft``."""
     sample_rate, n_fft, hop, n_mels = int(sample_rate), int(n_fft), _hop(n_fft, hop), int(n_mels)
     _check_params(sample_rate, n_fft, hop, n_mels)
-    x = _audio(audio, "log_mel")
+    x = _metric.audio(audio, "log_mel")
     b, t = x.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     dev = x.device
-    basis = _table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
-    weights = _table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
+    basis = _metric.table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
+    weights = _metric.table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
     out = torch.empty((b, stft_frames(t, hop), n_mels), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         scratch = _scratch(dev, b, t, n_fft, hop, n_mels, extra_scratch)
         _capi.check(_capi.load_library().l3ac_log_mel(x.data_ptr(), b, t, row_stride(x), c_lens, n_fft, hop, basis.data_ptr(),
-                                                      weights.data_ptr(), n_mels, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                      torch.cuda.current_stream(dev).cuda_stream))
+                                                      weights.data_ptr(), n_mels, out.data_ptr(), scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     if lens is None:
         return out
     return out, torch.tensor([1 + n // hop for n in lens], dtype=torch.int32)
-
-
-def _pair(reference, estimate, what: str):
-    r, e = _audio(reference, what), _audio(estimate, what)
-    if r.shape != e.shape:
-        raise ValueError(f"{what}: reference {tuple(r.shape)} and estimate {tuple(e.shape)} differ in shape")
-    if r.device != e.device:
-        raise RuntimeError(f"{what}: reference is on {r.device} but estimate is on {e.device}")
-    return r, e
 
 
 def _scales(scales) -> tuple:
@@ -185,17 +107,17 @@ def mel_distance(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: i
     sample_rate, scales = int(sample_rate), _scales(scales)
     for n_fft, hop, n_mels in scales:
         _check_params(sample_rate, n_fft, hop, n_mels)
-    r, e = _pair(reference, estimate, "mel_distance")
+    r, e = _metric.pair(reference, estimate, "mel_distance")
     b, t = r.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     dev = r.device
     lib = _capi.load_library()
     rows = torch.empty((len(scales), b), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _metric.stream(dev)
         for i, (n_fft, hop, n_mels) in enumerate(scales):
-            basis = _table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
-            weights = _table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
+            basis = _metric.table(dev, ("basis", n_fft), lambda: stft_basis(n_fft))
+            weights = _metric.table(dev, ("mel", sample_rate, n_fft, n_mels), lambda: mel_weights(sample_rate, n_fft, n_mels))
             scratch = _scratch(dev, b, t, n_fft, hop, n_mels, extra_scratch)
             _capi.check(lib.l3ac_mel_distance(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, n_fft, hop, n_mels,
                                               basis.data_ptr(), weights.data_ptr(), rows[i].data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
@@ -208,17 +130,16 @@ def signal_metrics(reference: torch.Tensor, estimate: torch.Tensor, lengths=None
     """Time-domain metrics of (B, T) fp32 CUDA pairs, each clip over its own samples, in fp64 -> ``{"mse", "snr_db", "si_sdr_db"}``,
     each (B,) fp64 CUDA.  ``si_sdr_db`` is the zero-mean scale-invariant SDR of Le Roux et al.; the residual energies are summed
     directly in a second pass, so 80 dB pairs keep their digits.  A zero denominator gives +inf, 0 / 0 gives nan."""
-    r, e = _pair(reference, estimate, "signal_metrics")
+    r, e = _metric.pair(reference, estimate, "signal_metrics")
     b, t = r.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     dev = r.device
     out = torch.empty((b, 3), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        scratch = torch.empty(4 * b, dtype=torch.uint8, device=dev)
+        scratch = _metric.scratch(dev, 4 * b)
         _capi.check(_capi.load_library().l3ac_signal_metrics(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens,
-                                                             out.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                             torch.cuda.current_stream(dev).cuda_stream))
-    return {"mse": out[:, 0].contiguous(), "snr_db": out[:, 1].contiguous(), "si_sdr_db": out[:, 2].contiguous()}
+                                                             out.data_ptr(), scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
+    return _metric.columns(out, ("mse", "snr_db", "si_sdr_db"))
 
 
 # ---- speech intelligibility (csrc/kernels/stoi.hip, DESIGN.md section 3.13) -----------------------------------------------------------
@@ -228,20 +149,13 @@ STOI_RATE = 10000  # the rate STOI and ESTOI are defined at
 def stoi_frames(samples: int) -> int:
     """Analysis frames of a clip of ``samples`` samples at 10 kHz: 0 up to 256 samples, else ceil((samples - 256) / 128); ``stoi``
     then has one spectral frame fewer than the frames it keeps.  Raises ValueError for samples < 1."""
-    n = _capi.load_library().l3ac_stoi_frames(int(samples))
-    if n < 0:
-        raise ValueError(_capi.load_library().l3ac_last_error().decode())
-    return int(n)
+    return _metric.lib_value("l3ac_stoi_frames", int(samples))
 
 
 def stoi_basis() -> torch.Tensor:
     """The library's window-folded STOI basis (514, 256) fp32 on the CPU: row 2k = w cos, row 2k + 1 = -w sin of bin k of a 512-point
     DFT, w = hanning(258)[1:-1]; row 0 is the window."""
-    lib = _capi.load_library()
-    n = lib.l3ac_stoi_basis(None, 0)
-    host = torch.empty(n, dtype=torch.float32)
-    lib.l3ac_stoi_basis(host.data_ptr(), n)
-    return host.view(514, 256)
+    return _metric.host_table("l3ac_stoi_basis", torch.float32).view(514, 256)
 
 
 def stoi_bands() -> list:
@@ -266,35 +180,29 @@ def stoi(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: int = 160
     sample_rate = int(sample_rate)
     if sample_rate != STOI_RATE:
         resample_length(sample_rate, STOI_RATE, 1)  # unsupported rates raise before any device work
-    r, e = _pair(reference, estimate, "stoi")
+    r, e = _metric.pair(reference, estimate, "stoi")
     b, t = r.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     if sample_rate != STOI_RATE:
         given = [t] * b if lens is None else lens
         r = resample(zero_after(r, given), sample_rate, STOI_RATE)
         e = resample(zero_after(e, given), sample_rate, STOI_RATE)
         t = r.shape[1]
-        lens, c_lens = _lengths([resample_length(sample_rate, STOI_RATE, n) for n in given], b, t)
+        lens, c_lens = _metric.lengths([resample_length(sample_rate, STOI_RATE, n) for n in given], b, t)
     dev = r.device
     lib = _capi.load_library()
-    basis = _table(dev, ("stoi_basis",), stoi_basis)
-    need = lib.l3ac_stoi_scratch_bytes(b, t)
-    if need < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    basis = _metric.table(dev, ("stoi_basis",), stoi_basis)
+    need = _metric.lib_value("l3ac_stoi_scratch_bytes", b, t)
     t_max = max(stoi_frames(t) - 1, 0)
-    if extra_scratch is None:  # the default, never more than the spectra of every frame row of both signals
-        extra = min(_EXTRA_SCRATCH, 2 * b * (t_max + 3) * 516 * 4)
-    else:
-        extra = max(0, int(extra_scratch))
     out = torch.empty((b, 2), dtype=torch.float64, device=dev)
     frames = torch.empty(b, dtype=torch.int32, device=dev)
     bands = torch.empty((2, b, t_max, 15), dtype=torch.float32, device=dev) if return_bands else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + extra, dtype=torch.uint8, device=dev)
+        scratch = _metric.scratch(dev, need, extra_scratch, b * (t_max + 3), 516)  # (the default: every frame row of both signals)
         _capi.check(lib.l3ac_stoi(r.data_ptr(), row_stride(r), e.data_ptr(), row_stride(e), b, t, c_lens, basis.data_ptr(), out.data_ptr(),
                                   frames.data_ptr(), None if bands is None or not t_max else bands.data_ptr(), scratch.data_ptr(),
-                                  scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    result = {"stoi": out[:, 0].contiguous(), "estoi": out[:, 1].contiguous(), "frames": frames}
+                                  scratch.numel(), _metric.stream(dev)))
+    result = dict(_metric.columns(out, ("stoi", "estoi")), frames=frames)
     if return_bands:
         result["bands_reference"], result["bands_estimate"] = bands[0], bands[1]
     return result

@@ -7,9 +7,8 @@ from typing import Optional
 
 import torch
 
-from . import _capi
+from . import _capi, _metric
 from ._rows import row_stride
-from .metrics import _audio, _lengths, _pair
 
 
 def _args(sample_rate, fmin, fmax, window, hop) -> tuple:
@@ -28,9 +27,7 @@ def _check_params(sample_rate, fmin=60.0, fmax=500.0, threshold=0.1, hop=None, w
         if given is not None and int(given) < 1:  # (-1 is the library's own spelling of the default, not the caller's)
             raise ValueError(f"pitch: {name} {given} must be at least 1")
     lags = (ctypes.c_int32 * 5)()
-    lib = _capi.load_library()
-    if lib.l3ac_pitch_lags(*args, lags) != 0:
-        raise ValueError(lib.l3ac_last_error().decode())
+    _metric.lib_value("l3ac_pitch_lags", *args, lags)
     try:
         threshold = float(threshold)
     except (TypeError, ValueError):
@@ -55,32 +52,25 @@ def pitch_frames(samples: int, sample_rate: int = 16000, fmin: float = 60.0, fma
     ``[t hop, t hop + span)``; its nominal time is ``(t hop + span / 2) / fs``.  Raises ValueError for samples < 0 or unsupported
     parameters."""
     args, _, _ = _check_params(sample_rate, fmin, fmax, 0.5, hop, window)
-    lib = _capi.load_library()
-    n = lib.l3ac_pitch_frames(int(samples), *args)
-    if n < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    return int(n)
+    return _metric.lib_value("l3ac_pitch_frames", int(samples), *args)
 
 
 def _track(x: torch.Tensor, c_lens, args: tuple, threshold: float, lags: tuple, return_cmnd: bool, extra_scratch) -> dict:
     """One l3ac_pitch call on checked arguments."""
     b, t = x.shape
     dev = x.device
-    lib = _capi.load_library()
-    need = lib.l3ac_pitch_scratch_bytes(b, t, *args)
-    f_max = lib.l3ac_pitch_frames(t, *args)
-    if need < 0 or f_max < 0:
-        raise ValueError(lib.l3ac_last_error().decode())
-    f0 = torch.empty((b, f_max), dtype=torch.float64, device=dev)
+    need = _metric.lib_value("l3ac_pitch_scratch_bytes", b, t, *args)
+    f_max = _metric.lib_value("l3ac_pitch_frames", t, *args)
+    f0 =torch.empty((b, f_max), dtype=torch.float64, device=dev)
     voiced = torch.empty((b, f_max), dtype=torch.int32, device=dev)
     aper = torch.empty((b, f_max), dtype=torch.float64, device=dev)
     frames = torch.empty(b, dtype=torch.int32, device=dev)
     cmnd = torch.empty((b, f_max, lags[1] + 2), dtype=torch.float64, device=dev) if return_cmnd else None
     with torch.cuda.device(dev):
-        scratch = torch.empty(int(need) + (0 if extra_scratch is None else max(0, int(extra_scratch))), dtype=torch.uint8, device=dev)
-        _capi.check(lib.l3ac_pitch(x.data_ptr(), row_stride(x), b, t, c_lens, *args, threshold, f0.data_ptr(), voiced.data_ptr(), aper.data_ptr(),
-                                   cmnd.data_ptr() if return_cmnd and f_max else None, frames.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream))
+        scratch = _metric.scratch(dev, need, extra_scratch)
+        _capi.check(_capi.load_library().l3ac_pitch(x.data_ptr(), row_stride(x), b, t, c_lens, *args, threshold, f0.data_ptr(), voiced.data_ptr(),
+                                                    aper.data_ptr(), cmnd.data_ptr() if return_cmnd and f_max else None, frames.data_ptr(),
+                                                    scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
     out = {"f0": f0, "voiced": voiced, "aperiodicity": aper, "frames": frames}
     if return_cmnd:
         out["cmnd"] = cmnd
@@ -102,8 +92,8 @@ def pitch(audio: torch.Tensor, sample_rate: int = 16000, fmin: float = 60.0, fma
     0 .. tau_max + 1.  A clip's bits do not depend on the batch it is in; ``extra_scratch``: bytes to allocate above the minimum scratch
     (the result does not depend on it).  No table is uploaded: the call can be captured without a warm-up.  No CPU path: CPU tensors raise."""
     args, threshold, lags = _check_params(sample_rate, fmin, fmax, threshold, hop, window)
-    x = _audio(audio, "pitch")
-    _, c_lens = _lengths(lengths, *x.shape)
+    x = _metric.audio(audio, "pitch")
+    _, c_lens = _metric.lengths(lengths, *x.shape)
     return _track(x, c_lens, args, threshold, lags, return_cmnd, extra_scratch)
 
 
@@ -117,9 +107,9 @@ def pitch_metrics(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: 
     ``1200 log2(f_estimate / f_reference)`` over the frames voiced on both sides, in fp64 in a fixed order.  A ratio whose denominator
     is zero is NaN.  There is no time alignment of the pair (``align`` makes one first).  ``lengths``: the pairs' common lengths.  Parameters as ``pitch``."""
     args, threshold, lags = _check_params(sample_rate, fmin, fmax, threshold, hop, window)
-    r, e = _pair(reference, estimate, "pitch_metrics")
+    r, e = _metric.pair(reference, estimate, "pitch_metrics")
     b, t = r.shape
-    lens, c_lens = _lengths(lengths, b, t)
+    lens, c_lens = _metric.lengths(lengths, b, t)
     lib = _capi.load_library()
     c_frames = None if lens is None else (ctypes.c_int32 * b)(*(lib.l3ac_pitch_frames(n, *args) for n in lens))
     ref = _track(r, c_lens, args, threshold, lags, False, None)
@@ -131,7 +121,6 @@ def pitch_metrics(reference: torch.Tensor, estimate: torch.Tensor, sample_rate: 
     with torch.cuda.device(dev):
         _capi.check(lib.l3ac_pitch_metrics(ref["f0"].data_ptr() if f_max else None, ref["voiced"].data_ptr() if f_max else None,
                                            est["f0"].data_ptr() if f_max else None, est["voiced"].data_ptr() if f_max else None, b, f_max, c_frames,
-                                           out.data_ptr(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-    return {"f0_rmse_cents": out[:, 0].contiguous(), "gpe": out[:, 1].contiguous(), "vde": out[:, 2].contiguous(), "ffe": out[:, 3].contiguous(),
-            "frames": counts[:, 0].contiguous(), "voiced_reference": counts[:, 1].contiguous(), "voiced_estimate": counts[:, 2].contiguous(),
-            "voiced_both": counts[:, 3].contiguous()}
+                                           out.data_ptr(), counts.data_ptr(), _metric.stream(dev)))
+    return dict(_metric.columns(out, ("f0_rmse_cents", "gpe", "vde", "ffe")),
+                **_metric.columns(counts, ("frames", "voiced_reference", "voiced_estimate", "voiced_both")))
