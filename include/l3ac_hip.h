@@ -653,6 +653,53 @@ int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int
                      double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
                      int64_t scratch_bytes, void* stream);
 
+/* ---- BSS Eval SDR: the signal-to-distortion ratio after a fitted distortion filter of up to 1024 taps, with its two primitives, the lag
+ * correlation of whole clips and the Toeplitz solve (which states every formula and summation order) ------------------
+ * A pair: reference s and estimate s^, fp32, n >= 1 samples each; filter length L in 1..1024; diagonal loading load >= 0.  Everything is fp64
+ * with contraction off; samples are converted first, so a product of two samples is exact; a sample outside [0, n) is selected away, never
+ * multiplied by zero.
+ * Correlation: corr(u, v)[k] = sum_{t=0}^{n-1-k} u[t] v[t+k], k = 0..L-1 (+0 for k >= n), as 64 interleaved partial sums (partial l takes the
+ * terms t = l mod 64 in increasing t from +0) folded p[l] += p[l+h] for h = 32, 16, .., 1.  r = corr(s, s), b = corr(s, s^), then r[0] =
+ * r[0] (1.0 + load), skipped for load == 0.
+ * Toeplitz solve of G c = b, G[i][j] = r[|i-j|]: isum over i = i0..i1 is 64 partial sums by (i - i0) mod 64 in increasing i from +0 and the
+ * same fold.  a[0] = 1, E_0 = r[0], c[0] = b[0] / r[0]; for m = 1..L-1: acc = r[m] + isum_{i=1}^{m-1} a[i] r[m-i], k_m = -acc / E_{m-1},
+ * a'[i] = a[i] + k_m a[m-i] for i = 1..m-1, a'[m] = k_m, E_m = E_{m-1} (1 - k_m k_m); then lambda = b[m] - isum_{i=0}^{m-1} c[i] r[m-i], nu =
+ * lambda / E_m, c'[i] = c[i] + nu a'[m-i] for i = 0..m-1, c'[m] = nu.  A pair is valid iff r[0] > 0 and every E_m > 0 (a NaN fails both).
+ * Residual: y[t] = sum_{k=0}^{L-1} c[k] s[t-k] from +0 in increasing k over the k with 0 <= t-k < n, t = 0..n+L-2; e[t] = (t < n ? s^[t] :
+ * 0) - y[t].  T = sum y^2 and D = sum e^2: the outputs in segments of 4096; in segment q thread i of 256 takes t = 4096 q + i + 256 j, j =
+ * 0..15, those below n+L-1, in increasing j from +0; then a xor tree inside each wave of 64 and the four waves' results in wave order; then the
+ * segments' sums from +0 in increasing q.  sdr_db = 10 log10(T / D) as IEEE has it: +inf for D == 0 < T, -inf for T == 0 < D, NaN for 0 / 0.
+ * With one source BSS Eval's SIR is +inf and its SAR equals the SDR.
+ *   l3ac_correlate_scratch_bytes:      the minimum scratch of l3ac_correlate: 256 ceil(4 batch / 256) bytes (the lengths); < 0 for lags
+ *                                      outside 1..1024, a bad batch or max_samples, or max_samples + lags - 1 >= 2^31.
+ *   l3ac_correlate:                    u, v [batch] rows of max_samples floats, u_stride / v_stride floats apart; samples: HOST array of
+ *                                      batch lengths in 1..max_samples, or NULL -> out [batch][lags] fp64 = corr(u, v).
+ *   l3ac_toeplitz_solve_scratch_bytes: 256 ceil(4 batch / 256) bytes (the first region of every layout; the solve keeps its state in LDS);
+ *                                      < 0 for length outside 1..1024 or batch outside 1..65535.
+ *   l3ac_toeplitz_solve:               r, b [batch][length] fp64 -> x [batch][length] fp64 (the c above), error [batch] fp64 = E_{length-1},
+ *                                      valid [batch] int32.  An invalid system has x and error NaN.
+ *   l3ac_sdr_scratch_bytes:            the minimum scratch of l3ac_sdr: 256 ceil(4 batch / 256) + 256 ceil(16 batch L / 256) + 256 ceil(8
+ *                                      batch L / 256) + 256 ceil(16 batch S / 256) bytes, S = ceil((max_samples + L - 1) / 4096) (the
+ *                                      lengths, r and b, the filter, the segments' two sums); < 0 as l3ac_correlate_scratch_bytes.
+ *   l3ac_sdr:                          ref, est as u, v above; load finite and >= 0 -> out [batch][4] fp64 = sdr_db, T, D, E_{L-1}; valid
+ *                                      [batch] int32; filter (or NULL) [batch][L] fp64 = c; corr (or NULL; a test hook) [batch][2][L] fp64 =
+ *                                      r, b.  An invalid pair has out and filter NaN and keeps its r and b.
+ * All but `samples` are device buffers.  Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit
+ * guarantee and calling convention: as the quality metrics above (a pair's results depend on its own samples only — not on the batch, its
+ * row, the strides, the scratch size or what lies at or after its length, which is never read; no atomics; enqueue only, nothing allocated,
+ * no synchronisation).  No device table: all three are capturable as the first call.  Non-finite samples leave their own pair's results
+ * unspecified and disturb nothing else: no address, bound or launch size comes from a sample value. */
+int64_t l3ac_correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags);
+int l3ac_correlate(const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                   int32_t lags, double* out, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t l3ac_toeplitz_solve_scratch_bytes(int32_t batch, int32_t length);
+int l3ac_toeplitz_solve(const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+int64_t l3ac_sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length);
+int l3ac_sdr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+             int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch, int64_t scratch_bytes,
+             void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -185,6 +185,12 @@ SIGNATURES = {
     "l3ac_lpc_metrics_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32, _I32]),
     "l3ac_lpc_metrics": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _I32, _P, C.c_double, C.c_double, C.c_double,
                                    C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_correlate_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_correlate": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _I64, _P]),
+    "l3ac_toeplitz_solve_scratch_bytes": (_I64, [_I32, _I32]),
+    "l3ac_toeplitz_solve": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_sdr_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_sdr": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

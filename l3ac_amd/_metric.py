@@ -1,4 +1,4 @@
-"""What the metric modules share (metrics, loudness, pitch, align, mcd, lpc): the library's host values and
+"""What the metric modules share (metrics, loudness, pitch, align, mcd, lpc, sdr): the library's host values and
 tables, the checks of ``(batch, samples)`` audio and of ``lengths=``, the per-device cache of uploaded tables, the scratch allocation and
 the result columns.  Each module's parameters and the order of its checks are its own."""
 from __future__ import annotations

@@ -54,6 +54,7 @@ SOURCES = [
     "kernels/align.hip",
     "kernels/mcd.hip",
     "kernels/lpc.hip",
+    "kernels/sdr.hip",
 ]
 
 

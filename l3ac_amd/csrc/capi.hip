@@ -962,6 +962,30 @@ int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int
                               trim, llr_max, is_max, cd_max, out, counts, frame_values, forms, scratch, scratch_bytes);
 }
 
+// ---- BSS Eval SDR, lag correlation, Toeplitz solve --------------------------------------------
+int64_t l3ac_correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags) { return correlate_scratch_bytes(batch, max_samples, lags); }
+
+int l3ac_correlate(const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                   int32_t lags, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_correlate((hipStream_t)stream, u, u_stride, v, v_stride, batch, max_samples, samples, lags, out, scratch, scratch_bytes);
+}
+
+int64_t l3ac_toeplitz_solve_scratch_bytes(int32_t batch, int32_t length) { return toeplitz_solve_scratch_bytes(batch, length); }
+
+int l3ac_toeplitz_solve(const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
+    return launch_toeplitz_solve((hipStream_t)stream, r, b, batch, length, x, error, valid, scratch, scratch_bytes);
+}
+
+int64_t l3ac_sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length) { return sdr_scratch_bytes(batch, max_samples, filter_length); }
+
+int l3ac_sdr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+             int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch, int64_t scratch_bytes,
+             void* stream) {
+    return launch_sdr((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, filter_length, load, out, valid, filter, corr,
+                      scratch, scratch_bytes);
+}
+
 // ---- streaming token wire format ---------------------------------------------------
 int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
 

@@ -337,6 +337,19 @@ int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, cons
                        const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
                        double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
                        int64_t scratch_bytes);
+// the SDR of BSS Eval and its primitives (kernels/sdr.hip; include/l3ac_hip.h "BSS Eval SDR"): the lag correlation of
+// whole clips, the Toeplitz solve (Levinson with a general right-hand side, one wave per pair), and the two chained with the residual's
+// energies and 10 log10(T / D)
+int64_t correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags);
+int launch_correlate(hipStream_t s, const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, int32_t lags, double* out, void* scratch, int64_t scratch_bytes);
+int64_t toeplitz_solve_scratch_bytes(int32_t batch, int32_t length);
+int launch_toeplitz_solve(hipStream_t s, const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid,
+                          void* scratch, int64_t scratch_bytes);
+int64_t sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length);
+int launch_sdr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+               const int32_t* samples, int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch,
+               int64_t scratch_bytes);
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -80,13 +80,6 @@ int lpc_geom(int32_t fs, int32_t order, int32_t frame, int32_t hop, LpcGeom* p) 
 
 int64_t frames_of(int64_t samples, const LpcGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
 
-// the fold s[l] += s[l + h], h = 32 .. 1: lane 0 holds the sum (a lane at or above h adds what it is handed and is not read again)
-__device__ __forceinline__ double fold64(double v) {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
-    return v;
-}
-
 __device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }  // (NaN stays NaN)
 
 // Levinson-Durbin on r[0..p] -> a[0..p], refl[0..p-1], *err = E_p; false where r[0] > 0 or an E_m > 0 fails (the arrays are then partial)

@@ -1,4 +1,4 @@
-// What the metric families share (metrics, stoi, loudness, pitch, align, mcd, lpc .hip): the fixed-order workgroup
+// What the metric families share (metrics, stoi, loudness, pitch, align, mcd, lpc, sdr .hip): the fixed-order workgroup
 // reductions on the device, and on the host the scratch layout, the checks of a batch of clips and the staging of their lengths.  Each
 // family's arithmetic, geometry and parameter checks are its own.
 #pragma once
@@ -8,8 +8,8 @@
 #include <algorithm>
 
 // ---- device: THE fixed tree over a workgroup's values.  A xor tree inside each wave, then the waves' results in wave order; every thread
-// gets the result.  "summed in fp64 in a fixed order" of every family's bit guarantee is this function.  (fold64 in lpc.hip, over_frames in
-// stoi.hip and wave_min_int in pitch.hip are other trees and stay where they are.) --------------------------------------------------------
+// gets the result.  "summed in fp64 in a fixed order" of every family's bit guarantee is this function.  (over_frames in stoi.hip and
+// wave_min_int in pitch.hip are other trees and stay where they are.) ---------------------------------------------------------------------
 template <int THREADS>
 __device__ __forceinline__ double block_sum(double v, double* lds) {
 #pragma unroll
@@ -34,6 +34,14 @@ __device__ __forceinline__ double block_max(double v, double* lds) {  // (a maxi
 #pragma unroll
     for (int w = 1; w < THREADS / 64; ++w) s = fmax(s, lds[w]);
     return s;
+}
+
+// The fold of 64 interleaved partial sums, one a lane (lpc.hip, sdr.hip): s[l] += s[l + h], h = 32 .. 1; lane 0 holds the sum (a lane at or
+// above h adds what it is handed and is not read again).
+__device__ __forceinline__ double fold64(double v) {
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
+    return v;
 }
 
 // ---- host: the caller's scratch ---------------------------------------------------------------------------------------------------------
