@@ -71,7 +71,8 @@ class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
 
-# name -> (restype, argtypes); must list every symbol include/l3ac_hip.h declares (tests check this)
+# name -> (restype, argtypes): every symbol include/l3ac_hip.h declares, with the header's type in every slot and as the return type
+# (tests/test_host.py parses the header and checks both); where in the library an entry is defined does not show here
 _P, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
 SIGNATURES = {
     "l3ac_last_error": (C.c_char_p, []),

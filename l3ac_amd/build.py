@@ -22,6 +22,8 @@ OBJ_DIR = CSRC / (f"build_{_TAG}" if _TAG else "build")
 LIB_PATH = PKG / (f"libl3ac_hip_{_TAG}.so" if _TAG else "libl3ac_hip.so")
 ARCH = "gfx950"
 
+# capi.hip defines the entries that take a context and the option, error and profiler entries; a context-free entry of the header is
+# defined in its kernel family's own file below, next to the kernels it launches
 SOURCES = [
     "capi.hip",
     "network.hip",

@@ -1,4 +1,5 @@
-// extern "C" entry points of libl3ac_hip.so (include/l3ac_hip.h).
+// extern "C" entry points of libl3ac_hip.so (include/l3ac_hip.h) that need a context, and the option, error and profiler entries.
+// The context-free entries (packing, resampling, chunking, streaming, wire format, the metric families) are defined in kernels/<family>.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -702,305 +703,6 @@ int l3ac_op_decoder(l3ac_ctx* ctx, const float* feature, int32_t batch, int32_t 
     float* alt = ctx->ws.x1;
     L3AC_HIP_CHECK(hipMemcpyAsync(cur, feature, (size_t)batch * frames * ctx->cfg.feature_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     return run_decoder(ctx, s, batch, frames, &cur, &alt, audio);
-}
-
-int l3ac_pack_indices(const int32_t* indices, int32_t batch, int32_t n_tok, int32_t bits, uint32_t* packed,
-                      int32_t words_per_clip, void* stream) {
-    L3AC_REQUIRE(indices && packed, "pack: null buffer");
-    return launch_pack_indices((hipStream_t)stream, indices, batch, n_tok, bits, packed, words_per_clip);
-}
-
-int l3ac_unpack_indices(const uint32_t* packed, int32_t batch, int32_t n_tok, int32_t bits, int32_t words_per_clip,
-                        int32_t* indices, void* stream) {
-    L3AC_REQUIRE(indices && packed, "unpack: null buffer");
-    return launch_unpack_indices((hipStream_t)stream, packed, batch, n_tok, bits, words_per_clip, indices);
-}
-
-int64_t l3ac_resample_length(int32_t in_rate, int32_t out_rate, int64_t n_in) {
-    ResamplePlan p;
-    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
-    L3AC_REQUIRE(n_in >= 0 && n_in <= (INT64_MAX / 1024), "resample: bad input length %lld", (long long)n_in);
-    return resample_length(p, n_in);
-}
-
-int64_t l3ac_resample_bank(int32_t in_rate, int32_t out_rate, float* bank, int64_t cap) {
-    ResamplePlan p;
-    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
-    const int64_t need = resample_bank_floats(p);
-    if (bank && need > 0 && cap >= need) resample_fill_bank(p, bank);
-    return need;
-}
-
-int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
-                  const float* bank, float* y, int64_t y_stride, void* stream) {
-    return launch_resample((hipStream_t)stream, x, batch, n_in, x_stride, in_rate, out_rate, bank, y, y_stride);
-}
-
-// ---- long recordings as chunk rows ---------------------------------------------
-int64_t l3ac_chunk_plan(const int64_t* frames, int32_t batch, int64_t chunk_len, int64_t prefix_len, int32_t round_to,
-                        l3ac_chunk_desc* desc_out, int64_t cap) {
-    return chunk_plan(frames, batch, chunk_len, prefix_len, round_to, desc_out, cap);
-}
-
-int l3ac_chunk_cut(const void* src, int32_t recs, int64_t src_stride, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
-                   void* dst, int32_t rows, int64_t dst_row_frames, void* stream) {
-    return launch_chunk_cut((hipStream_t)stream, src, recs, src_stride, c, desc, count, dst, rows, dst_row_frames);
-}
-
-int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int32_t c, const l3ac_chunk_desc* desc, int32_t count,
-                     void* dst, int32_t recs, int64_t dst_stride, int64_t out_frames, void* stream) {
-    return launch_chunk_merge((hipStream_t)stream, src, rows, src_row_frames, c, desc, count, dst, recs, dst_stride, out_frames);
-}
-
-// ---- streaming sessions: the state carried between pushes -------------------------
-int l3ac_stream_gather(const void* state, int32_t streams, int64_t state_frames, const void* fresh, int64_t fresh_frames, int64_t fresh_stride,
-                       int32_t c, const l3ac_stream_desc* desc, int32_t count, void* rows, int32_t n_rows, int64_t row_frames, void* stream) {
-    return launch_stream_gather((hipStream_t)stream, state, streams, state_frames, fresh, fresh_frames, fresh_stride, c, desc, count, rows, n_rows,
-                                row_frames);
-}
-
-int l3ac_stream_carry(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* state,
-                      int32_t streams, int64_t state_frames, void* stream) {
-    return launch_stream_carry((hipStream_t)stream, rows, n_rows, row_frames, c, desc, count, state, streams, state_frames);
-}
-
-int l3ac_stream_append(const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int32_t c, const l3ac_stream_desc* desc, int32_t count,
-                       void* state, int32_t streams, int64_t state_frames, void* stream) {
-    return launch_stream_append((hipStream_t)stream, fresh, fresh_frames, fresh_stride, c, desc, count, state, streams, state_frames);
-}
-
-int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* dst,
-                     int32_t streams, int64_t dst_stride, int64_t out_frames, void* stream) {
-    return launch_stream_emit((hipStream_t)stream, rows, n_rows, row_frames, c, desc, count, dst, streams, dst_stride, out_frames);
-}
-
-// ---- streaming sample-rate conversion ---------------------------------------------
-int64_t l3ac_resample_stream_state(int32_t in_rate, int32_t out_rate) {
-    ResamplePlan p;
-    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
-    return resample_stream_state_floats(p);
-}
-
-int l3ac_resample_stream(const float* state_in, float* state_out, int32_t streams, int64_t state_stride, const float* fresh, int64_t fresh_frames,
-                         int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
-                         int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream) {
-    return launch_resample_stream((hipStream_t)stream, state_in, state_out, streams, state_stride, fresh, fresh_frames, fresh_stride, in_rate,
-                                  out_rate, bank, desc, count, out, out_frames, out_stride);
-}
-
-// ---- quality metrics -------------------------------------------------------------------
-int64_t l3ac_stft_frames(int64_t samples, int32_t hop) { return stft_frames(samples, hop); }
-
-int64_t l3ac_stft_basis(int32_t n_fft, float* basis, int64_t cap) { return stft_basis(n_fft, basis, cap); }
-
-int64_t l3ac_mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap) {
-    return mel_weights(sample_rate, n_fft, n_mels, w, cap);
-}
-
-int64_t l3ac_mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels) {
-    return mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
-}
-
-int l3ac_stft(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
-              const float* basis, float* spec, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_stft((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, spec, scratch, scratch_bytes);
-}
-
-int l3ac_log_mel(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
-                 const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_log_mel((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, out, scratch,
-                          scratch_bytes);
-}
-
-int l3ac_mel_distance(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                      const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis, const float* weights, double* out,
-                      void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_mel_distance((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, n_fft, hop, n_mels, basis, weights,
-                               out, scratch, scratch_bytes);
-}
-
-int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                        const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_signal_metrics((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, out, scratch, scratch_bytes);
-}
-
-// ---- speech intelligibility ----------------------------------------------------------
-int64_t l3ac_stoi_frames(int64_t samples) { return stoi_frames(samples); }
-
-int64_t l3ac_stoi_basis(float* basis, int64_t cap) { return stoi_basis(basis, cap); }
-
-int64_t l3ac_stoi_window(float* window, int64_t cap) { return stoi_window(window, cap); }
-
-int l3ac_stoi_bands(int32_t* runs) { return stoi_bands(runs); }
-
-int64_t l3ac_stoi_scratch_bytes(int32_t batch, int64_t max_samples) { return stoi_scratch_bytes(batch, max_samples); }
-
-int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-              const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_stoi((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, basis, out, frames_out, bands_out, scratch,
-                       scratch_bytes);
-}
-
-// ---- loudness ---------------------------------------------------------------------------
-int64_t l3ac_loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) { return loudness_coeffs(sample_rate, out, cap); }
-
-int64_t l3ac_loudness_blocks(int64_t samples, int32_t sample_rate) { return loudness_blocks(samples, sample_rate); }
-
-int64_t l3ac_loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
-    return loudness_scratch_bytes(batch, max_samples, sample_rate);
-}
-
-int l3ac_loudness(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
-                  double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_loudness((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, stats, counts, momentary, scratch,
-                           scratch_bytes);
-}
-
-int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain, void* stream) {
-    return launch_loudness_gain((hipStream_t)stream, stats, batch, target_lufs, peak_limit_db, gain);
-}
-
-int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
-                    const int32_t* samples, const double* gain, int64_t gain_stride, void* stream) {
-    return launch_apply_gain((hipStream_t)stream, audio, audio_stride, out, out_stride, batch, max_samples, samples, gain, gain_stride);
-}
-
-// ---- pitch ------------------------------------------------------------------------------
-int l3ac_pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out) {
-    return pitch_lags(sample_rate, fmin, fmax, window, hop, out);
-}
-
-int64_t l3ac_pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
-    return pitch_frames(samples, sample_rate, fmin, fmax, window, hop);
-}
-
-int64_t l3ac_pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
-    return pitch_scratch_bytes(batch, max_samples, sample_rate, fmin, fmax, window, hop);
-}
-
-int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
-               double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced, double* aperiodicity,
-               double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_pitch((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, fmin, fmax, window, hop, threshold, f0,
-                        voiced, aperiodicity, cmnd, frames, scratch, scratch_bytes);
-}
-
-int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
-                       int64_t max_frames, const int32_t* frames, double* out, int32_t* counts, void* stream) {
-    return launch_pitch_metrics((hipStream_t)stream, f0_ref, voiced_ref, f0_est, voiced_est, batch, max_frames, frames, out, counts);
-}
-
-// ---- time alignment -----------------------------------------------------------------------
-int64_t l3ac_xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag) { return xcorr_scratch_bytes(batch, max_samples, max_lag); }
-
-int l3ac_xcorr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-               int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr, void* scratch,
-               int64_t scratch_bytes, void* stream) {
-    return launch_xcorr((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, max_lag, lag, polarity, delay, correlation,
-                        xcorr, scratch, scratch_bytes);
-}
-
-int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                     const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
-                     int32_t* out_samples, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_align_apply((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, lag, out_ref, out_ref_stride, out_est,
-                              out_est_stride, out_samples, scratch, scratch_bytes);
-}
-
-// ---- mel-cepstral distortion with DTW alignment ---------------------------------------------
-int64_t l3ac_dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) { return dct_table(n_mels, n_coeffs, out, cap); }
-
-int64_t l3ac_mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs) {
-    return mfcc_scratch_bytes(batch, max_samples, n_fft, hop, n_mels, n_coeffs);
-}
-
-int l3ac_mfcc(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
-              const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
-              int64_t scratch_bytes, void* stream) {
-    return launch_mfcc((hipStream_t)stream, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, dct, n_coeffs, out,
-                       scratch, scratch_bytes);
-}
-
-int64_t l3ac_dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
-    return dtw_scratch_bytes(batch, max_frames_a, max_frames_b);
-}
-
-int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride, int32_t batch,
-             int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b, int32_t diagonal_only,
-             double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_dtw((hipStream_t)stream, a, a_frame_stride, a_row_stride, b, b_frame_stride, b_row_stride, batch, dim, max_frames_a, max_frames_b,
-                      frames_a, frames_b, diagonal_only, cost, path_len, path, delta, scratch, scratch_bytes);
-}
-
-// ---- linear prediction, LLR, Itakura-Saito, cepstral distance, segmental SNR ----------------
-int64_t l3ac_lpc_window(int32_t frame, float* out, int64_t cap) { return lpc_window(frame, out, cap); }
-
-int l3ac_lpc_defaults(int32_t sample_rate, int32_t* out) { return lpc_defaults(sample_rate, out); }
-
-int64_t l3ac_lpc_frames(int64_t samples, int32_t frame, int32_t hop) { return lpc_frames(samples, frame, hop); }
-
-int64_t l3ac_lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
-    return lpc_scratch_bytes(batch, max_samples, sample_rate, order, frame, hop);
-}
-
-int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate, int32_t order,
-             int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error, double* autocorr, int32_t* valid,
-             int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_lpc((hipStream_t)stream, audio, audio_stride, batch, max_samples, samples, sample_rate, order, frame, hop, window, a, reflection, error,
-                      autocorr, valid, frames, scratch, scratch_bytes);
-}
-
-int64_t l3ac_lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
-    return lpc_metrics_scratch_bytes(batch, max_samples, sample_rate, order, frame, hop);
-}
-
-int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                     const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
-                     double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
-                     int64_t scratch_bytes, void* stream) {
-    return launch_lpc_metrics((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, sample_rate, order, frame, hop, window,
-                              trim, llr_max, is_max, cd_max, out, counts, frame_values, forms, scratch, scratch_bytes);
-}
-
-// ---- BSS Eval SDR, lag correlation, Toeplitz solve --------------------------------------------
-int64_t l3ac_correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags) { return correlate_scratch_bytes(batch, max_samples, lags); }
-
-int l3ac_correlate(const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-                   int32_t lags, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
-    return launch_correlate((hipStream_t)stream, u, u_stride, v, v_stride, batch, max_samples, samples, lags, out, scratch, scratch_bytes);
-}
-
-int64_t l3ac_toeplitz_solve_scratch_bytes(int32_t batch, int32_t length) { return toeplitz_solve_scratch_bytes(batch, length); }
-
-int l3ac_toeplitz_solve(const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid, void* scratch,
-                        int64_t scratch_bytes, void* stream) {
-    return launch_toeplitz_solve((hipStream_t)stream, r, b, batch, length, x, error, valid, scratch, scratch_bytes);
-}
-
-int64_t l3ac_sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length) { return sdr_scratch_bytes(batch, max_samples, filter_length); }
-
-int l3ac_sdr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-             int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch, int64_t scratch_bytes,
-             void* stream) {
-    return launch_sdr((hipStream_t)stream, ref, ref_stride, est, est_stride, batch, max_samples, samples, filter_length, load, out, valid, filter, corr,
-                      scratch, scratch_bytes);
-}
-
-// ---- streaming token wire format ---------------------------------------------------
-int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) { return packed_bytes(n_tok, bits); }
-
-int l3ac_pack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const int32_t* fresh, int64_t fresh_tokens,
-                     int64_t fresh_stride, int32_t bits, const l3ac_pack_stream_desc* desc, int32_t count, uint8_t* out, int64_t out_bytes,
-                     int64_t out_stride, void* stream) {
-    return launch_pack_stream((hipStream_t)stream, state_in, state_out, streams, fresh, fresh_tokens, fresh_stride, bits, desc, count, out,
-                              out_bytes, out_stride);
-}
-
-int l3ac_unpack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const uint8_t* fresh, int64_t fresh_bytes,
-                       int64_t fresh_stride, int32_t bits, const l3ac_unpack_stream_desc* desc, int32_t count, int32_t* out, int64_t out_tokens,
-                       int64_t out_stride, void* stream) {
-    return launch_unpack_stream((hipStream_t)stream, state_in, state_out, streams, fresh, fresh_bytes, fresh_stride, bits, desc, count, out,
-                                out_tokens, out_stride);
 }
 
 int l3ac_profile_begin(void) {

@@ -1,4 +1,5 @@
-// Launch API of the HIP kernels (one .hip file per kernel family under kernels/).
+// Internal launch API of the codec's HIP kernels (one .hip file per kernel family under kernels/), and the helpers several families share.
+// The context-free entries of include/l3ac_hip.h are not declared again here: that header is their one declaration.
 // All pointers are device pointers; activations are frame-major [batch][frame][channel].
 #pragma once
 
@@ -170,10 +171,13 @@ struct FsqArgs {
 int launch_fsq(hipStream_t s, const FsqArgs& a);
 // measurement aid: fsq_kernel's grid and access pattern (feat 128, 6 levels) with no arithmetic — its achievable HBM ceiling
 int launch_fsq_copy_ceiling(hipStream_t s, const float* x, int64_t n, float* q, int32_t* idx, float* li, int blocks_per_cu = 0);
-// token bit stream (kernels/bitpack.hip)
-int launch_pack_indices(hipStream_t s, const int32_t* idx, int batch, int n_tok, int bits, uint32_t* out, int words_per_clip);
-int launch_unpack_indices(hipStream_t s, const uint32_t* in, int batch, int n_tok, int bits, int words_per_clip, int32_t* idx);
-// polyphase sample-rate conversion, scipy.signal.resample_poly's defaults (kernels/resample.hip)
+
+// ------------------------------------------------------------------------------------------------
+// The context-free entries (token packing, resampling, chunking, streaming, wire format, the metric families) have no declaration here:
+// each l3ac_* function of include/l3ac_hip.h is defined once, in its family's file under kernels/, and that is what other families call.
+// Below is only what several of those files share.
+// ------------------------------------------------------------------------------------------------
+// polyphase sample-rate conversion, scipy.signal.resample_poly's defaults (kernels/resample.hip, kernels/resample_stream.hip)
 struct ResamplePlan {
     int up, down;   // out_rate / gcd, in_rate / gcd
     int half_len;   // 10 max(up, down)
@@ -183,8 +187,7 @@ int resample_plan(int32_t in_rate, int32_t out_rate, ResamplePlan* p);  // L3AC_
 int64_t resample_length(const ResamplePlan& p, int64_t n_in);
 int64_t resample_bank_floats(const ResamplePlan& p);                     // 0 when up == down (a copy needs no filter)
 void resample_fill_bank(const ResamplePlan& p, float* bank);             // host: [up][2][KE] fp32, each tap rounded once from fp64
-int launch_resample(hipStream_t s, const float* x, int batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
-                    const float* bank, float* y, int64_t y_stride);
+int64_t resample_stream_state_floats(const ResamplePlan& p);             // a stream's carried inputs: K - 1 rounded up to a multiple of 4
 // ragged batches (kernels/ragged.hip): per-clip counts reach the device as kernel arguments, CAP values per launch
 struct RaggedUpload {
     static constexpr int CAP = 248;
@@ -199,157 +202,29 @@ int launch_ragged_dup(hipStream_t s, float* x, int batch, int frames, int c, con
 // compact clip k <-> batch clip perm[k0 + k] for k < count: `rows` rows of c floats; clip strides in floats
 int launch_ragged_gather(hipStream_t s, const float* src, float* dst, const int* perm, int k0, int count, int rows, int c,
                          int64_t batch_clip, int64_t compact_clip, bool scatter);
-// long recordings as chunk rows (kernels/chunk.hip): descriptors reach the device as kernel arguments, CAP per launch
-struct ChunkBlock {
-    static constexpr int CAP = 112;  // 3.5 KiB of the 4 KiB a launch's arguments may take
+// Descriptors of the chunk, stream, streaming-resample and wire-format calls are host values and reach the device as kernel arguments,
+// CAP per launch: each block stays inside the 4 KiB that a launch's arguments may take
+struct ChunkBlock {  // kernels/chunk.hip
+    static constexpr int CAP = 112;  // 3.5 KiB
     l3ac_chunk_desc desc[CAP];
 };
-// HOST: the chunks of `batch` recordings (ChunkData's geometry); the count, or L3AC_EINVAL.  Fills `out` when non-null (cap >= count)
-int64_t chunk_plan(const int64_t* frames, int batch, int64_t chunk_len, int64_t prefix_len, int round_to, l3ac_chunk_desc* out, int64_t cap);
-// recordings [recs][src_stride][c] -> chunk rows [rows][dst_row_frames][c], 4-byte elements; `desc` is a host array
-int launch_chunk_cut(hipStream_t s, const void* src, int recs, int64_t src_stride, int c, const l3ac_chunk_desc* desc, int count, void* dst,
-                     int rows, int64_t dst_row_frames);
-// chunk rows [rows][src_row_frames][c] -> recordings [recs][dst_stride][c], prefixes dropped, zeros from a recording's end to out_frames
-int launch_chunk_merge(hipStream_t s, const void* src, int rows, int64_t src_row_frames, int c, const l3ac_chunk_desc* desc, int count,
-                       void* dst, int recs, int64_t dst_stride, int64_t out_frames);
-// streaming sessions (kernels/stream.hip): the state carried between pushes; descriptors as kernel arguments, CAP per launch
-struct StreamBlock {
-    static constexpr int CAP = 72;  // 3.4 KiB of the 4 KiB a launch's arguments may take
+struct StreamBlock {  // kernels/stream.hip
+    static constexpr int CAP = 72;  // 3.4 KiB
     l3ac_stream_desc desc[CAP];
 };
-// chunk row desc.row = state[slot][0 : held] ++ fresh[slot][off : off + take] ++ zeros(pad); `desc` is a host array
-int launch_stream_gather(hipStream_t s, const void* state, int streams, int64_t state_frames, const void* fresh, int64_t fresh_frames,
-                         int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count, void* rows, int n_rows, int64_t row_frames);
-// state[slot][0 : keep] = the last keep of row desc.row's held + take own frames
-int launch_stream_carry(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* state,
-                        int streams, int64_t state_frames);
-// state[slot][held : held + take] = fresh[slot][off : off + take]
-int launch_stream_append(hipStream_t s, const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count,
-                         void* state, int streams, int64_t state_frames);
-// frames [prefix, held + take + pad) of row desc.row -> dst[slot][out ...], then `zero` zero frames
-int launch_stream_emit(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* dst,
-                       int streams, int64_t dst_stride, int64_t out_frames);
-// streaming sample-rate conversion (kernels/resample_stream.hip): one launch per push computes every stream's outputs
-// from state ++ new samples and writes its next state into the other state buffer; descriptors as kernel arguments, CAP per launch
-struct ResampleStreamBlock {
-    static constexpr int CAP = 128;  // 3 KiB of the 4 KiB a launch's arguments may take
+struct ResampleStreamBlock {  // kernels/resample_stream.hip
+    static constexpr int CAP = 128;  // 3 KiB
     l3ac_resample_stream_desc desc[CAP];
 };
-int64_t resample_stream_state_floats(const ResamplePlan& p);  // K - 1 rounded up to a multiple of 4
-int launch_resample_stream(hipStream_t s, const float* state_in, float* state_out, int streams, int64_t state_stride, const float* fresh,
-                           int64_t fresh_frames, int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank,
-                           const l3ac_resample_stream_desc* desc, int count, float* out, int64_t out_frames, int64_t out_stride);
-// streaming token wire format (kernels/bitpack_stream.hip): one launch per push packs / unpacks every stream's
-// held bits ++ new tokens / bytes and writes its next pending bits into the other state buffer; descriptors as kernel arguments, CAP per launch
-struct PackStreamBlock {
-    static constexpr int CAP = 160;  // 3.1 KiB of the 4 KiB a launch's arguments may take
+struct PackStreamBlock {  // kernels/bitpack_stream.hip
+    static constexpr int CAP = 160;  // 3.1 KiB
     l3ac_pack_stream_desc desc[CAP];
 };
 struct UnpackStreamBlock {
     static constexpr int CAP = 160;
     l3ac_unpack_stream_desc desc[CAP];
 };
-int64_t packed_bytes(int64_t n_tok, int bits);  // HOST: ceil(n_tok * bits / 8), L3AC_EINVAL for n_tok < 0 or bits outside 1..32
-int launch_pack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const int32_t* fresh, int64_t fresh_tokens,
-                       int64_t fresh_stride, int bits, const l3ac_pack_stream_desc* desc, int count, uint8_t* out, int64_t out_bytes,
-                       int64_t out_stride);
-int launch_unpack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const uint8_t* fresh, int64_t fresh_bytes,
-                         int64_t fresh_stride, int bits, const l3ac_unpack_stream_desc* desc, int count, int32_t* out, int64_t out_tokens,
-                         int64_t out_stride);
-// quality metrics (kernels/metrics.hip): STFT as one exact-fp32 GEMM over staged clip rows, log-mel, log-mel
-// distance and the time-domain metrics; `samples` is a host array (null: every clip has max_samples), handed over as kernel arguments
-int64_t stft_frames(int64_t samples, int32_t hop);                          // HOST: 1 + samples / hop, L3AC_EINVAL for samples or hop < 1
-int64_t stft_basis(int32_t n_fft, float* basis, int64_t cap);               // HOST: [n_fft + 2][n_fft] fp32, each entry rounded once from fp64
-int64_t mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap);  // HOST: [n_mels][n_fft / 2 + 1]
-int64_t mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels);
-int launch_stft(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                int32_t hop, const float* basis, float* spec, void* scratch, int64_t scratch_bytes);
-int launch_log_mel(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                   int32_t hop, const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes);
-int launch_mel_distance(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
-                        int64_t max_samples, const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis,
-                        const float* weights, double* out, void* scratch, int64_t scratch_bytes);
-int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
-                          int64_t max_samples, const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes);
-// speech intelligibility (kernels/stoi.hip; include/l3ac_hip.h "speech intelligibility"): STOI and ESTOI of pairs at 10 kHz
-int64_t stoi_frames(int64_t samples);               // HOST: A(samples), L3AC_EINVAL for samples < 1
-int64_t stoi_basis(float* basis, int64_t cap);      // HOST: [514][256] fp32, each entry rounded once from fp64
-int64_t stoi_window(float* w, int64_t cap);         // HOST: [256] fp32 = row 0 of the basis
-int stoi_bands(int32_t* runs);                      // HOST: 15 x (lo, hi)
-int64_t stoi_scratch_bytes(int32_t batch, int64_t max_samples);
-int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                const int32_t* samples, const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch,
-                int64_t scratch_bytes);
-// loudness (kernels/loudness.hip; include/l3ac_hip.h "loudness"): BS.1770-4 integrated loudness of mono clips in fp64,
-// the K-weighting recursion parallel over 100 ms steps (zero-state pass, per-clip scan of the 4-value state, energy pass), and the gain
-int64_t loudness_coeffs(int32_t sample_rate, double* out, int64_t cap);     // HOST: [2][6] b0 b1 b2 a0 a1 a2, then M [4][4]
-int64_t loudness_blocks(int64_t samples, int32_t sample_rate);              // HOST: J(samples)
-int64_t loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate);
-int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-                    int32_t sample_rate, double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes);
-int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain);
-int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
-                      const int32_t* samples, const double* gain, int64_t gain_stride);
-// pitch (kernels/pitch.hip; include/l3ac_hip.h "pitch"): YIN over groups of frames staged in LDS (fp32 difference
-// function, one lane per lag; fp64 from the prefix on), and the pairwise F0 metrics; window / hop -1: the defaults
-int pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out);  // HOST: tau_min tau_max W hop span
-int64_t pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);  // HOST: F(samples)
-int64_t pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop);
-int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-                 int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced,
-                 double* aperiodicity, double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes);
-int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
-                         int64_t max_frames, const int32_t* frames, double* out, int32_t* counts);
-// time alignment (kernels/align.hip; include/l3ac_hip.h "time alignment"): the cross-correlation of clip pairs over
-// lags -max_lag .. max_lag as a GEMM on the fp32 matrix pipe with fp64 diagonal sums, the pick of lag / polarity / delay / correlation,
-// and the shift by per-clip lags read from device memory
-int64_t xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag);
-int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                 const int32_t* samples, int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr,
-                 void* scratch, int64_t scratch_bytes);
-int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                       const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
-                       int32_t* out_samples, void* scratch, int64_t scratch_bytes);
-// mel-cepstral distortion (kernels/mcd.hip; include/l3ac_hip.h "mel-cepstral distortion"): the orthonormal DCT-II
-// table (host), the cepstra of log_mel's cells as one fp32 fmaf chain per coefficient, and the batched DTW over rows of fp32 features
-// (fp64 frame distances and accumulation, one workgroup per pair, the backtrace in the same kernel)
-int64_t dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap);
-int64_t mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs);
-int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                int32_t hop, const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
-                int64_t scratch_bytes);
-int64_t dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b);
-int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride,
-               int32_t batch, int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b,
-               int32_t diagonal_only, double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes);
-// linear prediction and the envelope measures (kernels/lpc.hip; include/l3ac_hip.h "linear prediction"): the window
-// (host), the geometry (host), short-time autocorrelation + Levinson-Durbin of one side, and of a pair with the three quadratic forms, the
-// cepstra, LLR / IS / CD / segmental SNR per frame and the sorted, trimmed means per pair (one workgroup per pair)
-int64_t lpc_window(int32_t frame, float* out, int64_t cap);
-int lpc_defaults(int32_t sample_rate, int32_t* out);
-int64_t lpc_frames(int64_t samples, int32_t frame, int32_t hop);
-int64_t lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
-int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-               int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error,
-               double* autocorr, int32_t* valid, int32_t* frames, void* scratch, int64_t scratch_bytes);
-int64_t lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop);
-int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                       const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
-                       double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
-                       int64_t scratch_bytes);
-// the SDR of BSS Eval and its primitives (kernels/sdr.hip; include/l3ac_hip.h "BSS Eval SDR"): the lag correlation of
-// whole clips, the Toeplitz solve (Levinson with a general right-hand side, one wave per pair), and the two chained with the residual's
-// energies and 10 log10(T / D)
-int64_t correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags);
-int launch_correlate(hipStream_t s, const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples,
-                     const int32_t* samples, int32_t lags, double* out, void* scratch, int64_t scratch_bytes);
-int64_t toeplitz_solve_scratch_bytes(int32_t batch, int32_t length);
-int launch_toeplitz_solve(hipStream_t s, const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid,
-                          void* scratch, int64_t scratch_bytes);
-int64_t sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length);
-int launch_sdr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-               const int32_t* samples, int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch,
-               int64_t scratch_bytes);
+
 // explicit-codebook L2 argmin (kernels/fsq.hip): scratch = vq_argmin_scratch_bytes(n, k) bytes, caller-provided
 size_t vq_argmin_scratch_bytes(int64_t n, int k, int form = 0);
 // form: 0 automatic, 1 the direct-form scan wherever the screened form would run (the reference the screened form is tested against)

@@ -241,15 +241,18 @@ int xcorr_scratch(int32_t batch, int64_t max_samples, int32_t max_lag, XcorrScra
 
 }  // namespace
 
-int64_t xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag) {
+extern "C" {
+
+int64_t l3ac_xcorr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t max_lag) {
     XcorrScratch sc;
     L3AC_TRY(xcorr_scratch(batch, max_samples, max_lag, &sc));
     return sc.need;
 }
 
-int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                 const int32_t* samples, int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr,
-                 void* scratch, int64_t scratch_bytes) {
+int l3ac_xcorr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+               int32_t max_lag, int32_t* lag, int32_t* polarity, double* delay, double* correlation, double* xcorr, void* scratch,
+               int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     XcorrScratch sc;
     L3AC_TRY(xcorr_scratch(batch, max_samples, max_lag, &sc));
     L3AC_REQUIRE(ref && est, "xcorr: null audio");
@@ -276,9 +279,10 @@ int launch_xcorr(hipStream_t s, const float* ref, int64_t ref_stride, const floa
     return L3AC_OK;
 }
 
-int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                       const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
-                       int32_t* out_samples, void* scratch, int64_t scratch_bytes) {
+int l3ac_align_apply(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, const int32_t* lag, float* out_ref, int64_t out_ref_stride, float* out_est, int64_t out_est_stride,
+                     int32_t* out_samples, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_clip_batch("align_apply", batch, max_samples));
     L3AC_REQUIRE(ref && est, "align_apply: null audio");
     L3AC_REQUIRE(lag, "align_apply: null lag");
@@ -295,3 +299,5 @@ int launch_align_apply(hipStream_t s, const float* ref, int64_t ref_stride, cons
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

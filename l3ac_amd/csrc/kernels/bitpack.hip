@@ -47,22 +47,32 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict_
 
 }  // namespace
 
-int launch_pack_indices(hipStream_t s, const int32_t* idx, int batch, int n_tok, int bits, uint32_t* out, int words_per_clip) {
+extern "C" {
+
+int l3ac_pack_indices(const int32_t* indices, int32_t batch, int32_t n_tok, int32_t bits, uint32_t* packed, int32_t words_per_clip,
+                      void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    L3AC_REQUIRE(indices && packed, "pack: null buffer");
     L3AC_REQUIRE(bits >= 1 && bits <= 32 && batch > 0 && batch <= 65535 && n_tok > 0, "pack: bad arguments");
     L3AC_REQUIRE((int64_t)words_per_clip * 32 >= (int64_t)n_tok * bits, "pack: output too small");
     ProfScope prof(s, "pack_kernel", 0.0, (double)batch * n_tok * (4.0 + bits / 8.0));
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)ceil_div64(words_per_clip, 256), (unsigned)batch), dim3(256), 0, s, idx, n_tok, bits,
-                       out, words_per_clip);
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)ceil_div64(words_per_clip, 256), (unsigned)batch), dim3(256), 0, s, indices, n_tok, bits,
+                       packed, words_per_clip);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
 
-int launch_unpack_indices(hipStream_t s, const uint32_t* in, int batch, int n_tok, int bits, int words_per_clip, int32_t* idx) {
+int l3ac_unpack_indices(const uint32_t* packed, int32_t batch, int32_t n_tok, int32_t bits, int32_t words_per_clip, int32_t* indices,
+                        void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    L3AC_REQUIRE(indices && packed, "unpack: null buffer");
     L3AC_REQUIRE(bits >= 1 && bits <= 32 && batch > 0 && batch <= 65535 && n_tok > 0, "unpack: bad arguments");
     L3AC_REQUIRE((int64_t)words_per_clip * 32 >= (int64_t)n_tok * bits, "unpack: input too small");
     ProfScope prof(s, "unpack_kernel", 0.0, (double)batch * n_tok * (4.0 + bits / 8.0));
-    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)ceil_div64(n_tok, 256), (unsigned)batch), dim3(256), 0, s, in, words_per_clip, bits,
-                       idx, n_tok);
+    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)ceil_div64(n_tok, 256), (unsigned)batch), dim3(256), 0, s, packed, words_per_clip, bits,
+                       indices, n_tok);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

@@ -160,14 +160,17 @@ int bps_check(const char* what, const uint32_t* state_in, uint32_t* state_out, i
 
 }  // namespace
 
-int64_t packed_bytes(int64_t n_tok, int bits) {
+extern "C" {
+
+int64_t l3ac_packed_bytes(int64_t n_tok, int32_t bits) {
     L3AC_REQUIRE(bits >= 1 && bits <= 32 && n_tok >= 0 && n_tok <= INT64_MAX / 64, "packed_bytes: %lld tokens of %d bits", (long long)n_tok, bits);
     return (n_tok * bits + 7) / 8;
 }
 
-int launch_pack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const int32_t* fresh, int64_t fresh_tokens,
-                       int64_t fresh_stride, int bits, const l3ac_pack_stream_desc* desc, int count, uint8_t* out, int64_t out_bytes,
-                       int64_t out_stride) {
+int l3ac_pack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const int32_t* fresh, int64_t fresh_tokens,
+                     int64_t fresh_stride, int32_t bits, const l3ac_pack_stream_desc* desc, int32_t count, uint8_t* out, int64_t out_bytes,
+                     int64_t out_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(bps_check("pack_stream", state_in, state_out, streams, fresh, fresh_tokens, fresh_stride, 4, bits, desc, count, out, out_bytes, out_stride, 1));
     L3AC_REQUIRE(out_stride % 4 == 0 && reinterpret_cast<uintptr_t>(fresh) % 4 == 0, "pack_stream: output rows of %lld bytes are no multiple of 4, or "
                  "the tokens are not 4-byte aligned", (long long)out_stride);
@@ -197,9 +200,10 @@ int launch_pack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_
     return L3AC_OK;
 }
 
-int launch_unpack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* state_out, int streams, const uint8_t* fresh, int64_t fresh_bytes,
-                         int64_t fresh_stride, int bits, const l3ac_unpack_stream_desc* desc, int count, int32_t* out, int64_t out_tokens,
-                         int64_t out_stride) {
+int l3ac_unpack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t streams, const uint8_t* fresh, int64_t fresh_bytes,
+                       int64_t fresh_stride, int32_t bits, const l3ac_unpack_stream_desc* desc, int32_t count, int32_t* out, int64_t out_tokens,
+                       int64_t out_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(bps_check("unpack_stream", state_in, state_out, streams, fresh, fresh_bytes, fresh_stride, 1, bits, desc, count, out, out_tokens, out_stride, 4));
     for (int i = 0; i < count; ++i) {
         const l3ac_unpack_stream_desc& d = desc[i];
@@ -227,3 +231,5 @@ int launch_unpack_stream(hipStream_t s, const uint32_t* state_in, uint32_t* stat
     }
     return L3AC_OK;
 }
+
+}  // extern "C"

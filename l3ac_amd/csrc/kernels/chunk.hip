@@ -51,45 +51,6 @@ __global__ __launch_bounds__(THREADS) void chunk_merge_kernel(const uint32_t* __
     if (d.last && end < out_frames) zero_span(rec + end * c, (out_frames - end) * c, tid, stride);
 }
 
-}  // namespace
-
-int64_t chunk_plan(const int64_t* frames, int batch, int64_t chunk_len, int64_t prefix_len, int round_to, l3ac_chunk_desc* out,
-                   int64_t cap) {
-    L3AC_REQUIRE(frames && batch > 0, "chunk_plan: no recordings");
-    L3AC_REQUIRE(prefix_len >= 0 && chunk_len > prefix_len, "chunk_plan: chunk_len (%lld) must exceed prefix_len (%lld >= 0)",
-                 (long long)chunk_len, (long long)prefix_len);
-    L3AC_REQUIRE(round_to >= 1, "chunk_plan: round_to = %d", round_to);
-    L3AC_REQUIRE(chunk_len + prefix_len <= INT32_MAX - round_to, "chunk_plan: a chunk row of %lld frames does not fit 32 bits",
-                 (long long)(chunk_len + prefix_len));
-    int64_t total = 0;
-    for (int b = 0; b < batch; ++b) {
-        L3AC_REQUIRE(frames[b] >= 1 && frames[b] <= (INT64_MAX >> 12), "chunk_plan: frames[%d] = %lld", b, (long long)frames[b]);
-        total += ceil_div64(round_up64(frames[b], round_to), chunk_len);
-    }
-    L3AC_REQUIRE(total <= INT32_MAX, "chunk_plan: %lld chunks", (long long)total);
-    if (!out) return total;
-    L3AC_REQUIRE(cap >= total, "chunk_plan: %lld chunks but room for %lld descriptors", (long long)total, (long long)cap);
-    int64_t row = 0;
-    for (int b = 0; b < batch; ++b) {
-        const int64_t n = round_up64(frames[b], round_to);
-        for (int64_t i = 0; i < n; i += chunk_len, ++row) {
-            l3ac_chunk_desc& d = out[row];
-            const int64_t start = i == 0 ? 0 : i - prefix_len;
-            const int64_t stop = std::min(n, i + chunk_len);
-            d.rec = b;
-            d.row = (int32_t)row;
-            d.start = start;
-            d.frames = (int32_t)(stop - start);
-            d.prefix = (int32_t)(i - start);
-            d.pad = (int32_t)std::max<int64_t>(stop - std::max(frames[b], start), 0);  // (rounding adds < round_to <= a chunk's own frames)
-            d.last = stop == n;
-        }
-    }
-    return total;
-}
-
-namespace {
-
 int check_descs(const char* who, const l3ac_chunk_desc* desc, int count, int recs, int64_t rec_frames, int rows, int64_t row_frames) {
     L3AC_REQUIRE(desc && count > 0, "%s: no descriptors", who);
     for (int i = 0; i < count; ++i) {
@@ -108,8 +69,46 @@ int check_descs(const char* who, const l3ac_chunk_desc* desc, int count, int rec
 
 }  // namespace
 
-int launch_chunk_cut(hipStream_t s, const void* src, int recs, int64_t src_stride, int c, const l3ac_chunk_desc* desc, int count, void* dst,
-                     int rows, int64_t dst_row_frames) {
+extern "C" {
+
+int64_t l3ac_chunk_plan(const int64_t* frames, int32_t batch, int64_t chunk_len, int64_t prefix_len, int32_t round_to,
+                        l3ac_chunk_desc* desc_out, int64_t cap) {
+    L3AC_REQUIRE(frames && batch > 0, "chunk_plan: no recordings");
+    L3AC_REQUIRE(prefix_len >= 0 && chunk_len > prefix_len, "chunk_plan: chunk_len (%lld) must exceed prefix_len (%lld >= 0)",
+                 (long long)chunk_len, (long long)prefix_len);
+    L3AC_REQUIRE(round_to >= 1, "chunk_plan: round_to = %d", round_to);
+    L3AC_REQUIRE(chunk_len + prefix_len <= INT32_MAX - round_to, "chunk_plan: a chunk row of %lld frames does not fit 32 bits",
+                 (long long)(chunk_len + prefix_len));
+    int64_t total = 0;
+    for (int b = 0; b < batch; ++b) {
+        L3AC_REQUIRE(frames[b] >= 1 && frames[b] <= (INT64_MAX >> 12), "chunk_plan: frames[%d] = %lld", b, (long long)frames[b]);
+        total += ceil_div64(round_up64(frames[b], round_to), chunk_len);
+    }
+    L3AC_REQUIRE(total <= INT32_MAX, "chunk_plan: %lld chunks", (long long)total);
+    if (!desc_out) return total;
+    L3AC_REQUIRE(cap >= total, "chunk_plan: %lld chunks but room for %lld descriptors", (long long)total, (long long)cap);
+    int64_t row = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int64_t n = round_up64(frames[b], round_to);
+        for (int64_t i = 0; i < n; i += chunk_len, ++row) {
+            l3ac_chunk_desc& d = desc_out[row];
+            const int64_t start = i == 0 ? 0 : i - prefix_len;
+            const int64_t stop = std::min(n, i + chunk_len);
+            d.rec = b;
+            d.row = (int32_t)row;
+            d.start = start;
+            d.frames = (int32_t)(stop - start);
+            d.prefix = (int32_t)(i - start);
+            d.pad = (int32_t)std::max<int64_t>(stop - std::max(frames[b], start), 0);  // (rounding adds < round_to <= a chunk's own frames)
+            d.last = stop == n;
+        }
+    }
+    return total;
+}
+
+int l3ac_chunk_cut(const void* src, int32_t recs, int64_t src_stride, int32_t c, const l3ac_chunk_desc* desc, int32_t count, void* dst,
+                   int32_t rows, int64_t dst_row_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_REQUIRE(src && dst && recs > 0 && rows > 0 && c >= 1 && src_stride >= 1 && dst_row_frames >= 1, "chunk_cut: bad arguments");
     L3AC_REQUIRE((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 4 == 0, "chunk_cut: buffers must be 4-byte aligned");
     L3AC_TRY(check_descs("chunk_cut", desc, count, recs, INT64_MAX, rows, dst_row_frames));
@@ -133,8 +132,9 @@ int launch_chunk_cut(hipStream_t s, const void* src, int recs, int64_t src_strid
     return L3AC_OK;
 }
 
-int launch_chunk_merge(hipStream_t s, const void* src, int rows, int64_t src_row_frames, int c, const l3ac_chunk_desc* desc, int count,
-                       void* dst, int recs, int64_t dst_stride, int64_t out_frames) {
+int l3ac_chunk_merge(const void* src, int32_t rows, int64_t src_row_frames, int32_t c, const l3ac_chunk_desc* desc, int32_t count, void* dst,
+                     int32_t recs, int64_t dst_stride, int64_t out_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_REQUIRE(src && dst && recs > 0 && rows > 0 && c >= 1 && src_row_frames >= 1, "chunk_merge: bad arguments");
     L3AC_REQUIRE(out_frames >= 1 && out_frames <= dst_stride, "chunk_merge: out_frames %lld for rows of %lld", (long long)out_frames,
                  (long long)dst_stride);
@@ -158,3 +158,5 @@ int launch_chunk_merge(hipStream_t s, const void* src, int rows, int64_t src_row
     }
     return L3AC_OK;
 }
+
+}  // extern "C"

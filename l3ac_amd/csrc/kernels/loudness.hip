@@ -315,7 +315,9 @@ int filter_design(int32_t fs, LoudFilter* f) {
 
 }  // namespace
 
-int64_t loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) {
+extern "C" {
+
+int64_t l3ac_loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) {
     LoudFilter f;
     L3AC_TRY(filter_design(sample_rate, &f));
     const int64_t need = 2 * 6 + 16;
@@ -329,21 +331,22 @@ int64_t loudness_coeffs(int32_t sample_rate, double* out, int64_t cap) {
     return need;
 }
 
-int64_t loudness_blocks(int64_t samples, int32_t sample_rate) {
+int64_t l3ac_loudness_blocks(int64_t samples, int32_t sample_rate) {
     LD_REQUIRE_RATE(sample_rate);
     L3AC_REQUIRE(samples >= 1, "loudness_blocks: samples %lld must be positive", (long long)samples);
     return std::max<int64_t>(samples / (sample_rate / 10) - 3, 0);
 }
 
-int64_t loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
+int64_t l3ac_loudness_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
     int64_t s_max;
     LoudScratch sc;
     L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
     return sc.total_min;
 }
 
-int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-                    int32_t sample_rate, double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes) {
+int l3ac_loudness(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                  double* stats, int32_t* counts, double* momentary, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     int64_t s_max;
     LoudScratch sc;
     L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
@@ -389,7 +392,8 @@ int launch_loudness(hipStream_t s, const float* audio, int64_t audio_stride, int
     return L3AC_OK;
 }
 
-int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain) {
+int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, double peak_limit_db, double* gain, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_REQUIRE(batch > 0 && batch <= 65535, "loudness_gain: batch %d outside 1..65535", batch);
     L3AC_REQUIRE(std::isfinite(target_lufs), "loudness_gain: target_lufs must be finite");
     L3AC_REQUIRE(stats && gain, "loudness_gain: null buffer");
@@ -401,8 +405,9 @@ int launch_loudness_gain(hipStream_t s, const double* stats, int32_t batch, doub
     return L3AC_OK;
 }
 
-int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
-                      const int32_t* samples, const double* gain, int64_t gain_stride) {
+int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
+                    const int32_t* samples, const double* gain, int64_t gain_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_clip_batch("apply_gain", batch, max_samples));
     L3AC_REQUIRE(audio && out && gain, "apply_gain: null buffer");
     L3AC_REQUIRE(batch == 1 || (audio_stride >= max_samples && out_stride >= max_samples), "apply_gain: row stride below max_samples %lld",
@@ -423,3 +428,5 @@ int launch_apply_gain(hipStream_t s, const float* audio, int64_t audio_stride, f
         return L3AC_OK;
     });
 }
+
+}  // extern "C"

@@ -349,14 +349,16 @@ int lpc_metrics_scratch(int32_t batch, int64_t max_samples, int32_t sample_rate,
 
 }  // namespace
 
-int64_t lpc_window(int32_t frame, float* out, int64_t cap) {
+extern "C" {
+
+int64_t l3ac_lpc_window(int32_t frame, float* out, int64_t cap) {
     L3AC_REQUIRE(frame >= 2 && frame <= LP_MAX_FRAME, "lpc_window: frame %d outside 2..%d", frame, LP_MAX_FRAME);
     if (!out || cap < frame) return frame;
     for (int i = 0; i < frame; ++i) out[i] = (float)(0.5 * (1.0 - std::cos(2.0 * M_PI * (double)(i + 1) / (double)(frame + 1))));
     return frame;
 }
 
-int lpc_defaults(int32_t sample_rate, int32_t* out) {
+int l3ac_lpc_defaults(int32_t sample_rate, int32_t* out) {
     L3AC_REQUIRE(sample_rate >= LP_MIN_RATE && sample_rate <= LP_MAX_RATE, "lpc: sample_rate %d outside %d..%d", sample_rate, LP_MIN_RATE, LP_MAX_RATE);
     L3AC_REQUIRE(out, "lpc_defaults: null out");
     const int frame = (int)((30 * (int64_t)sample_rate + 500) / 1000);
@@ -364,23 +366,24 @@ int lpc_defaults(int32_t sample_rate, int32_t* out) {
     return L3AC_OK;
 }
 
-int64_t lpc_frames(int64_t samples, int32_t frame, int32_t hop) {
+int64_t l3ac_lpc_frames(int64_t samples, int32_t frame, int32_t hop) {
     L3AC_REQUIRE(samples >= 0, "lpc_frames: samples %lld must not be negative", (long long)samples);
     L3AC_REQUIRE(frame >= 2 && frame <= LP_MAX_FRAME, "lpc_frames: frame %d outside 2..%d", frame, LP_MAX_FRAME);
     L3AC_REQUIRE(hop >= 1, "lpc_frames: hop %d must be at least 1", hop);
     return samples < frame ? 0 : 1 + (samples - frame) / hop;
 }
 
-int64_t lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
+int64_t l3ac_lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
     LpcGeom p;
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
     L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
     return ScratchPlan(batch).bytes;  // the clips' lengths
 }
 
-int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-               int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error,
-               double* autocorr, int32_t* valid, int32_t* frames, void* scratch, int64_t scratch_bytes) {
+int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate, int32_t order,
+             int32_t frame, int32_t hop, const float* window, double* a, double* reflection, double* error, double* autocorr, int32_t* valid,
+             int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     LpcGeom p;
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
     L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
@@ -403,17 +406,18 @@ int launch_lpc(hipStream_t s, const float* audio, int64_t audio_stride, int32_t 
     return L3AC_OK;
 }
 
-int64_t lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
+int64_t l3ac_lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
     LpcGeom p;
     LpcMetricsScratch sc;
     L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
     return sc.need;
 }
 
-int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                       const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
-                       double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
-                       int64_t scratch_bytes) {
+int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, const float* window, double trim,
+                     double llr_max, double is_max, double cd_max, double* out, int32_t* counts, double* frame_values, double* forms, void* scratch,
+                     int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     LpcGeom p;
     LpcMetricsScratch sc;
     L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
@@ -446,3 +450,5 @@ int launch_lpc_metrics(hipStream_t s, const float* ref, int64_t ref_stride, cons
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // Mel-cepstral distortion along a dynamic-time-warping path (include/l3ac_hip.h, "mel-cepstral distortion"; DESIGN.md §3.17, which is
 // normative): the cepstra of l3ac_log_mel's cells, a batched DTW over rows of fp32 features, and its backtrace.  No reference counterpart.
 //
-//   mfcc_dct_kernel   grid (blocks of cells, batch): launch_log_mel (metrics.hip: its staging, its product, its mel kernel — nothing of it is
+//   mfcc_dct_kernel   grid (blocks of cells, batch): l3ac_log_mel (metrics.hip: its staging, its product, its mel kernel — nothing of it is
 //                     repeated here) writes the clips' cells [batch][F][n_mels] into the scratch; one lane per (frame, q) then runs
 //                     c[f][q] = sum_m D[q][m] L[f][m] as ONE fp32 fmaf chain over m = 0 .. n_mels - 1 from +0: the chain launch_gemm
 //                     gives without a w_img.  (launch_gemm itself takes k and lda in multiples of 4: n_mels = 255 would need a padded
@@ -190,7 +190,7 @@ struct MfccScratch {  // byte offsets into the caller's scratch, after the clips
 // the parameters checked, then the cells [batch][F][n_mels] and log_mel's own scratch (as large as it says: not rounded up)
 int mfcc_scratch(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs, MfccScratch* sc) {
     L3AC_TRY(cep_params(n_mels, n_coeffs));
-    const int64_t mel = mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
+    const int64_t mel = l3ac_mel_scratch_bytes(batch, max_samples, n_fft, hop, n_mels);
     if (mel < 0) return L3AC_EINVAL;
     ScratchPlan plan(batch);
     sc->cells = plan.take((int64_t)batch * (1 + max_samples / hop) * n_mels * 4);
@@ -217,7 +217,9 @@ int dtw_scratch(int32_t batch, int32_t max_frames_a, int32_t max_frames_b, DtwSc
 
 }  // namespace
 
-int64_t dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) {
+extern "C" {
+
+int64_t l3ac_dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) {
     L3AC_TRY(cep_params(n_mels, n_coeffs));
     const int64_t need = (int64_t)(n_coeffs + 1) * n_mels;
     if (!out || cap < need) return need;
@@ -231,15 +233,16 @@ int64_t dct_table(int32_t n_mels, int32_t n_coeffs, float* out, int64_t cap) {
     return need;
 }
 
-int64_t mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs) {
+int64_t l3ac_mfcc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_coeffs) {
     MfccScratch sc;
     L3AC_TRY(mfcc_scratch(batch, max_samples, n_fft, hop, n_mels, n_coeffs, &sc));
     return sc.need;
 }
 
-int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                int32_t hop, const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
-                int64_t scratch_bytes) {
+int l3ac_mfcc(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, const float* weights, int32_t n_mels, const float* dct, int32_t n_coeffs, float* out, void* scratch,
+              int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     MfccScratch sc;
     L3AC_TRY(mfcc_scratch(batch, max_samples, n_fft, hop, n_mels, n_coeffs, &sc));
     L3AC_REQUIRE(audio && out, "mfcc: null buffer");
@@ -251,8 +254,8 @@ int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_sa
     const int64_t frames = 1 + max_samples / hop;
     char* base = static_cast<char*>(scratch);
     float* cells = reinterpret_cast<float*>(base + sc.cells);
-    L3AC_TRY(launch_log_mel(s, audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, cells, base + sc.mel,
-                            scratch_bytes - sc.mel));
+    L3AC_TRY(l3ac_log_mel(audio, batch, max_samples, audio_stride, samples, n_fft, hop, basis, weights, n_mels, cells, base + sc.mel,
+                          scratch_bytes - sc.mel, stream));
     const int n_out = n_coeffs + 1;
     ProfScope prof(s, "mfcc_dct_kernel", 2.0 * batch * (double)frames * n_out * n_mels, 4.0 * batch * (double)frames * (n_mels + n_out));
     hipLaunchKernelGGL(mfcc_dct_kernel, dim3((unsigned)ceil_div64(frames * n_out, CEP_THREADS), (unsigned)batch), dim3(CEP_THREADS), 0, s, cells, dct,
@@ -261,15 +264,16 @@ int launch_mfcc(hipStream_t s, const float* audio, int32_t batch, int64_t max_sa
     return L3AC_OK;
 }
 
-int64_t dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
+int64_t l3ac_dtw_scratch_bytes(int32_t batch, int32_t max_frames_a, int32_t max_frames_b) {
     DtwScratch sc;
     L3AC_TRY(dtw_scratch(batch, max_frames_a, max_frames_b, &sc));
     return sc.need;
 }
 
-int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride,
-               int32_t batch, int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b,
-               int32_t diagonal_only, double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes) {
+int l3ac_dtw(const float* a, int64_t a_frame_stride, int64_t a_row_stride, const float* b, int64_t b_frame_stride, int64_t b_row_stride, int32_t batch,
+             int32_t dim, int32_t max_frames_a, int32_t max_frames_b, const int32_t* frames_a, const int32_t* frames_b, int32_t diagonal_only,
+             double* cost, int32_t* path_len, int32_t* path, double* delta, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     DtwScratch sc;
     L3AC_TRY(dtw_scratch(batch, max_frames_a, max_frames_b, &sc));
     L3AC_REQUIRE(dim >= 1 && dim <= DTW_MAX_DIM, "dtw: dim %d outside 1..%d", dim, DTW_MAX_DIM);
@@ -303,3 +307,5 @@ int launch_dtw(hipStream_t s, const float* a, int64_t a_frame_stride, int64_t a_
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

@@ -317,12 +317,14 @@ int run_mel(hipStream_t s, MelMode mode, const float* x0, int64_t stride0, const
 
 }  // namespace
 
-int64_t stft_frames(int64_t samples, int32_t hop) {
+extern "C" {
+
+int64_t l3ac_stft_frames(int64_t samples, int32_t hop) {
     L3AC_REQUIRE(samples >= 1 && hop >= 1, "stft_frames: samples %lld and hop %d must be positive", (long long)samples, hop);
     return 1 + samples / hop;
 }
 
-int64_t stft_basis(int32_t n_fft, float* basis, int64_t cap) {
+int64_t l3ac_stft_basis(int32_t n_fft, float* basis, int64_t cap) {
     L3AC_REQUIRE(n_fft >= 16 && n_fft <= 2048 && n_fft % 16 == 0, "metrics: n_fft %d must be a multiple of 16 in 16..2048", n_fft);
     const int64_t need = (int64_t)(n_fft + 2) * n_fft;
     if (!basis || cap < need) return need;
@@ -338,7 +340,7 @@ int64_t stft_basis(int32_t n_fft, float* basis, int64_t cap) {
     return need;
 }
 
-int64_t mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap) {
+int64_t l3ac_mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w, int64_t cap) {
     L3AC_REQUIRE(sample_rate > 0, "metrics: sample_rate %d must be positive", sample_rate);
     L3AC_REQUIRE(n_fft >= 16 && n_fft <= 2048 && n_fft % 16 == 0, "metrics: n_fft %d must be a multiple of 16 in 16..2048", n_fft);
     L3AC_REQUIRE(n_mels >= 1 && n_mels <= MT_MAX_MELS, "metrics: n_mels %d outside 1..%d", n_mels, MT_MAX_MELS);
@@ -359,34 +361,38 @@ int64_t mel_weights(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* w
     return need;
 }
 
-int64_t mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels) {
+int64_t l3ac_mel_scratch_bytes(int32_t batch, int64_t max_samples, int32_t n_fft, int32_t hop, int32_t n_mels) {
     MelGeom g;
     MelScratch sc;
     L3AC_TRY(mel_geom(batch, max_samples, n_fft, hop, n_mels, true, &g, &sc));
     return sc.total_min;
 }
 
-int launch_stft(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                int32_t hop, const float* basis, float* spec, void* scratch, int64_t scratch_bytes) {
+int l3ac_stft(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+              const float* basis, float* spec, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return run_mel(s, MODE_STFT, audio, audio_stride, nullptr, 0, batch, max_samples, samples, n_fft, hop, 0, basis, nullptr, spec, scratch,
                    scratch_bytes);
 }
 
-int launch_log_mel(hipStream_t s, const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft,
-                   int32_t hop, const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes) {
+int l3ac_log_mel(const float* audio, int32_t batch, int64_t max_samples, int64_t audio_stride, const int32_t* samples, int32_t n_fft, int32_t hop,
+                 const float* basis, const float* weights, int32_t n_mels, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return run_mel(s, MODE_LOG_MEL, audio, audio_stride, nullptr, 0, batch, max_samples, samples, n_fft, hop, n_mels, basis, weights, out, scratch,
                    scratch_bytes);
 }
 
-int launch_mel_distance(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
-                        int64_t max_samples, const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis,
-                        const float* weights, double* out, void* scratch, int64_t scratch_bytes) {
+int l3ac_mel_distance(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, int32_t n_fft, int32_t hop, int32_t n_mels, const float* basis, const float* weights, double* out,
+                      void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return run_mel(s, MODE_DISTANCE, ref, ref_stride, est, est_stride, batch, max_samples, samples, n_fft, hop, n_mels, basis, weights, out, scratch,
                    scratch_bytes);
 }
 
-int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch,
-                          int64_t max_samples, const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes) {
+int l3ac_signal_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                        const int32_t* samples, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_REQUIRE(ref && est && out, "signal_metrics: null buffer");
     L3AC_REQUIRE(batch > 0 && max_samples > 0, "signal_metrics: empty input (batch %d, samples %lld)", batch, (long long)max_samples);
     L3AC_REQUIRE(max_samples < ((int64_t)1 << 31), "signal_metrics: clips of %lld samples are too long", (long long)max_samples);
@@ -405,3 +411,5 @@ int launch_signal_metrics(hipStream_t s, const float* ref, int64_t ref_stride, c
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

@@ -282,7 +282,9 @@ __global__ __launch_bounds__(PM_THREADS) void pitch_metrics_kernel(const double*
 
 }  // namespace
 
-int pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out) {
+extern "C" {
+
+int l3ac_pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, int32_t* out) {
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(out, "pitch_lags: null out");
@@ -290,23 +292,24 @@ int pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t window, in
     return L3AC_OK;
 }
 
-int64_t pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
+int64_t l3ac_pitch_frames(int64_t samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(samples >= 0, "pitch_frames: samples %lld must not be negative", (long long)samples);
     return frames_of(samples, p);
 }
 
-int64_t pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
+int64_t l3ac_pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_TRY(check_clip_batch("pitch", batch, max_samples));
     return ScratchPlan(batch).bytes;  // the clips' lengths
 }
 
-int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
-                 int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced,
-                 double* aperiodicity, double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes) {
+int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+               double fmin, double fmax, int32_t window, int32_t hop, double threshold, double* f0, int32_t* voiced, double* aperiodicity,
+               double* cmnd, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(threshold > 0.0 && threshold < 1.0, "pitch: threshold %g outside (0, 1)", threshold);
@@ -330,8 +333,9 @@ int launch_pitch(hipStream_t s, const float* audio, int64_t audio_stride, int32_
     return L3AC_OK;
 }
 
-int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
-                         int64_t max_frames, const int32_t* frames, double* out, int32_t* counts) {
+int l3ac_pitch_metrics(const double* f0_ref, const int32_t* voiced_ref, const double* f0_est, const int32_t* voiced_est, int32_t batch,
+                       int64_t max_frames, const int32_t* frames, double* out, int32_t* counts, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_REQUIRE(batch > 0 && batch <= 65535, "pitch_metrics: batch %d outside 1..65535", batch);
     L3AC_REQUIRE(max_frames >= 0 && max_frames < ((int64_t)1 << 31), "pitch_metrics: max_frames %lld outside 0..2^31 - 1", (long long)max_frames);
     L3AC_REQUIRE(out && counts, "pitch_metrics: null output buffer");
@@ -346,3 +350,5 @@ int launch_pitch_metrics(hipStream_t s, const double* f0_ref, const int32_t* voi
         return L3AC_OK;
     });
 }
+
+}  // extern "C"

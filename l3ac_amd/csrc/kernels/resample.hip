@@ -202,8 +202,26 @@ void resample_fill_bank(const ResamplePlan& p, float* bank) {
     }
 }
 
-int launch_resample(hipStream_t s, const float* x, int batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate,
-                    const float* bank, float* y, int64_t y_stride) {
+extern "C" {
+
+int64_t l3ac_resample_length(int32_t in_rate, int32_t out_rate, int64_t n_in) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    L3AC_REQUIRE(n_in >= 0 && n_in <= (INT64_MAX / 1024), "resample: bad input length %lld", (long long)n_in);
+    return resample_length(p, n_in);
+}
+
+int64_t l3ac_resample_bank(int32_t in_rate, int32_t out_rate, float* bank, int64_t cap) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    const int64_t need = resample_bank_floats(p);
+    if (bank && need > 0 && cap >= need) resample_fill_bank(p, bank);
+    return need;
+}
+
+int l3ac_resample(const float* x, int32_t batch, int64_t n_in, int64_t x_stride, int32_t in_rate, int32_t out_rate, const float* bank,
+                  float* y, int64_t y_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     ResamplePlan p;
     L3AC_TRY(resample_plan(in_rate, out_rate, &p));
     L3AC_REQUIRE(x && y, "resample: null buffer");
@@ -246,3 +264,5 @@ int launch_resample(hipStream_t s, const float* x, int batch, int64_t n_in, int6
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

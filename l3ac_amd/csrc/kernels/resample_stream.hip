@@ -119,9 +119,18 @@ bool rss_apart(const void* a, int64_t a_elements, const void* b, int64_t b_eleme
 
 int64_t resample_stream_state_floats(const ResamplePlan& p) { return 4 * ceil_div64(p.K - 1, 4); }
 
-int launch_resample_stream(hipStream_t s, const float* state_in, float* state_out, int streams, int64_t state_stride, const float* fresh,
-                           int64_t fresh_frames, int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank,
-                           const l3ac_resample_stream_desc* desc, int count, float* out, int64_t out_frames, int64_t out_stride) {
+extern "C" {
+
+int64_t l3ac_resample_stream_state(int32_t in_rate, int32_t out_rate) {
+    ResamplePlan p;
+    L3AC_TRY(resample_plan(in_rate, out_rate, &p));
+    return resample_stream_state_floats(p);
+}
+
+int l3ac_resample_stream(const float* state_in, float* state_out, int32_t streams, int64_t state_stride, const float* fresh, int64_t fresh_frames,
+                         int64_t fresh_stride, int32_t in_rate, int32_t out_rate, const float* bank, const l3ac_resample_stream_desc* desc,
+                         int32_t count, float* out, int64_t out_frames, int64_t out_stride, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     ResamplePlan p;
     L3AC_TRY(resample_plan(in_rate, out_rate, &p));
     const bool copy = p.up == p.down;
@@ -199,3 +208,5 @@ int launch_resample_stream(hipStream_t s, const float* state_in, float* state_ou
     }
     return L3AC_OK;
 }
+
+}  // extern "C"

@@ -247,13 +247,16 @@ void enqueue_solve(hipStream_t s, const double* r, const double* b, int64_t row,
 
 }  // namespace
 
-int64_t correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags) {
+extern "C" {
+
+int64_t l3ac_correlate_scratch_bytes(int32_t batch, int64_t max_samples, int32_t lags) {
     L3AC_TRY(check_extent("correlate", "lags", batch, max_samples, lags));
     return ScratchPlan(batch).bytes;  // the clips' lengths
 }
 
-int launch_correlate(hipStream_t s, const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples,
-                     const int32_t* samples, int32_t lags, double* out, void* scratch, int64_t scratch_bytes) {
+int l3ac_correlate(const float* u, int64_t u_stride, const float* v, int64_t v_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+                   int32_t lags, double* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_extent("correlate", "lags", batch, max_samples, lags));
     L3AC_REQUIRE(u && v, "correlate: null audio");
     L3AC_REQUIRE(out, "correlate: null output buffer");
@@ -267,14 +270,15 @@ int launch_correlate(hipStream_t s, const float* u, int64_t u_stride, const floa
     return L3AC_OK;
 }
 
-int64_t toeplitz_solve_scratch_bytes(int32_t batch, int32_t length) {
+int64_t l3ac_toeplitz_solve_scratch_bytes(int32_t batch, int32_t length) {
     L3AC_TRY(check_taps("toeplitz_solve", "length", length));
     L3AC_REQUIRE(batch > 0 && batch <= 65535, "toeplitz_solve: batch %d outside 1..65535", batch);
     return ScratchPlan(batch).bytes;  // the first region of every layout; the solve keeps its state in LDS
 }
 
-int launch_toeplitz_solve(hipStream_t s, const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid,
-                          void* scratch, int64_t scratch_bytes) {
+int l3ac_toeplitz_solve(const double* r, const double* b, int32_t batch, int32_t length, double* x, double* error, int32_t* valid, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_taps("toeplitz_solve", "length", length));
     L3AC_REQUIRE(batch > 0 && batch <= 65535, "toeplitz_solve: batch %d outside 1..65535", batch);
     L3AC_REQUIRE(r && b, "toeplitz_solve: null input");
@@ -286,15 +290,16 @@ int launch_toeplitz_solve(hipStream_t s, const double* r, const double* b, int32
     return L3AC_OK;
 }
 
-int64_t sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length) {
+int64_t l3ac_sdr_scratch_bytes(int32_t batch, int64_t max_samples, int32_t filter_length) {
     SdrScratch sc;
     L3AC_TRY(sdr_scratch(batch, max_samples, filter_length, &sc));
     return sc.need;
 }
 
-int launch_sdr(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-               const int32_t* samples, int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch,
-               int64_t scratch_bytes) {
+int l3ac_sdr(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+             int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch, int64_t scratch_bytes,
+             void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     SdrScratch sc;
     L3AC_TRY(sdr_scratch(batch, max_samples, filter_length, &sc));
     L3AC_REQUIRE(load >= 0.0 && std::isfinite(load), "sdr: load %g must be finite and not negative", load);
@@ -324,3 +329,5 @@ int launch_sdr(hipStream_t s, const float* ref, int64_t ref_stride, const float*
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }
+
+}  // extern "C"

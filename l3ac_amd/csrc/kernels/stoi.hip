@@ -319,18 +319,20 @@ double hann258(int j) { return 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)(j + 1)
 
 }  // namespace
 
-int64_t stoi_frames(int64_t samples) {
+extern "C" {
+
+int64_t l3ac_stoi_frames(int64_t samples) {
     L3AC_REQUIRE(samples >= 1, "stoi_frames: samples %lld must be positive", (long long)samples);
     return st_frames(samples);
 }
 
-int64_t stoi_window(float* w, int64_t cap) {
-    if (!w || cap < ST_FRAME) return ST_FRAME;
-    for (int j = 0; j < ST_FRAME; ++j) w[j] = (float)hann258(j);
+int64_t l3ac_stoi_window(float* window, int64_t cap) {
+    if (!window || cap < ST_FRAME) return ST_FRAME;
+    for (int j = 0; j < ST_FRAME; ++j) window[j] = (float)hann258(j);
     return ST_FRAME;
 }
 
-int64_t stoi_basis(float* basis, int64_t cap) {
+int64_t l3ac_stoi_basis(float* basis, int64_t cap) {
     const int64_t need = (int64_t)ST_BASIS_ROWS * ST_FRAME;
     if (!basis || cap < need) return need;
     const double step = 2.0 * M_PI / ST_NFFT;
@@ -345,7 +347,7 @@ int64_t stoi_basis(float* basis, int64_t cap) {
     return need;
 }
 
-int stoi_bands(int32_t* runs) {
+int l3ac_stoi_bands(int32_t* runs) {
     L3AC_REQUIRE(runs, "stoi_bands: null buffer");
     auto nearest = [](double f) {  // the first bin whose frequency is nearest to f
         int best = 0;
@@ -366,16 +368,16 @@ int stoi_bands(int32_t* runs) {
     return L3AC_OK;
 }
 
-int64_t stoi_scratch_bytes(int32_t batch, int64_t max_samples) {
+int64_t l3ac_stoi_scratch_bytes(int32_t batch, int64_t max_samples) {
     StoiGeom g;
     StoiScratch sc;
     L3AC_TRY(stoi_geom(batch, max_samples, &g, &sc));
     return sc.total_min;
 }
 
-int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
-                const int32_t* samples, const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch,
-                int64_t scratch_bytes) {
+int l3ac_stoi(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+              const float* basis, double* out, int32_t* frames_out, float* bands_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     StoiGeom g;
     StoiScratch sc;
     L3AC_TRY(stoi_geom(batch, max_samples, &g, &sc));
@@ -410,7 +412,7 @@ int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float
     }
     if (g.t_max > 0) {
         int32_t host_runs[2 * ST_BANDS], lo_hi[2 * ST_BANDS];
-        L3AC_TRY(stoi_bands(host_runs));
+        L3AC_TRY(l3ac_stoi_bands(host_runs));
         for (int i = 0; i < ST_BANDS; ++i) {  // the kernel reads [lo of every band][hi of every band]
             lo_hi[i] = host_runs[2 * i];
             lo_hi[ST_BANDS + i] = host_runs[2 * i + 1];
@@ -460,3 +462,5 @@ int launch_stoi(hipStream_t s, const float* ref, int64_t ref_stride, const float
     }
     return L3AC_OK;
 }
+
+}  // extern "C"

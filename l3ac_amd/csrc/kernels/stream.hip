@@ -125,8 +125,11 @@ int launch_blocks(const l3ac_stream_desc* desc, int count, int c, int64_t (*span
 
 }  // namespace
 
-int launch_stream_gather(hipStream_t s, const void* state, int streams, int64_t state_frames, const void* fresh, int64_t fresh_frames,
-                         int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count, void* rows, int n_rows, int64_t row_frames) {
+extern "C" {
+
+int l3ac_stream_gather(const void* state, int32_t streams, int64_t state_frames, const void* fresh, int64_t fresh_frames, int64_t fresh_stride,
+                       int32_t c, const l3ac_stream_desc* desc, int32_t count, void* rows, int32_t n_rows, int64_t row_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_common("stream_gather", desc, count, streams, c));
     L3AC_REQUIRE(state && rows && state_frames >= 1 && n_rows > 0 && row_frames >= 1 && fresh_frames >= 0 && fresh_stride >= 1,
                  "stream_gather: bad arguments");
@@ -155,8 +158,9 @@ int launch_stream_gather(hipStream_t s, const void* state, int streams, int64_t 
                          });
 }
 
-int launch_stream_carry(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* state,
-                        int streams, int64_t state_frames) {
+int l3ac_stream_carry(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* state,
+                      int32_t streams, int64_t state_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_common("stream_carry", desc, count, streams, c));
     L3AC_REQUIRE(state && rows && state_frames >= 1 && n_rows > 0 && row_frames >= 1, "stream_carry: bad arguments");
     L3AC_REQUIRE((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(rows)) % 4 == 0, "stream_carry: buffers must be 4-byte aligned");
@@ -182,8 +186,9 @@ int launch_stream_carry(hipStream_t s, const void* rows, int n_rows, int64_t row
                          });
 }
 
-int launch_stream_append(hipStream_t s, const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int c, const l3ac_stream_desc* desc, int count,
-                         void* state, int streams, int64_t state_frames) {
+int l3ac_stream_append(const void* fresh, int64_t fresh_frames, int64_t fresh_stride, int32_t c, const l3ac_stream_desc* desc, int32_t count,
+                       void* state, int32_t streams, int64_t state_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_common("stream_append", desc, count, streams, c));
     L3AC_REQUIRE(state && state_frames >= 1 && fresh_frames >= 0 && fresh_stride >= 1, "stream_append: bad arguments");
     L3AC_REQUIRE((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(fresh)) % 4 == 0, "stream_append: buffers must be 4-byte aligned");
@@ -207,8 +212,9 @@ int launch_stream_append(hipStream_t s, const void* fresh, int64_t fresh_frames,
                          });
 }
 
-int launch_stream_emit(hipStream_t s, const void* rows, int n_rows, int64_t row_frames, int c, const l3ac_stream_desc* desc, int count, void* dst,
-                       int streams, int64_t dst_stride, int64_t out_frames) {
+int l3ac_stream_emit(const void* rows, int32_t n_rows, int64_t row_frames, int32_t c, const l3ac_stream_desc* desc, int32_t count, void* dst,
+                     int32_t streams, int64_t dst_stride, int64_t out_frames, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     L3AC_TRY(check_common("stream_emit", desc, count, streams, c));
     L3AC_REQUIRE(rows && dst && n_rows > 0 && row_frames >= 1, "stream_emit: bad arguments");
     L3AC_REQUIRE(out_frames >= 1 && out_frames <= dst_stride, "stream_emit: out_frames %lld for rows of %lld", (long long)out_frames, (long long)dst_stride);
@@ -235,3 +241,5 @@ int launch_stream_emit(hipStream_t s, const void* rows, int n_rows, int64_t row_
                              return L3AC_OK;
                          });
 }
+
+}  // extern "C"

@@ -9,6 +9,8 @@ python tests/golden/make_metric_contract.py``); no GPU is needed.  It records
   * ``launch``  for each launch entry a valid call on fake pointers (never made as it stands) and calls with one of its arguments wrong, then
                 with two: the return code and the message, i.e. which check comes first.  Every one must be refused by the host-side
                 validation — the script fails on a call that is not.
+A family added later is recorded after the earlier ones (the SDR family, from the commit before its entries moved out of capi.hip into
+kernels/sdr.hip): the earlier records must come out as they are in the file, the new records and messages behind them.
 """
 import itertools
 import json
@@ -181,8 +183,39 @@ LAUNCH = {
 }
 
 
-def launch_cases(lib, fn: str) -> dict:
-    names, base, wrong = LAUNCH[fn]
+# ---- the SDR family, recorded later than the rest: its records and messages are APPENDED, the earlier ones keep their place and index --------
+def sdr_host_calls() -> dict:
+    taps = ([8, 1, 2, 512, 1024], [0, 1025, -1])
+    extent = [[1, TOP - 1, 1], [1, TOP - 1, 2], [65535, TOP - 1024, 1024], [1, TOP - 1023, 1024]]  # max_samples + taps - 1 at and past 2^31 - 1
+    return {
+        "l3ac_correlate_scratch_bytes": sweep(BATCH, ([1, 4096, 5000, TOP - 8], [0, TOP]), taps) + extent,
+        "l3ac_toeplitz_solve_scratch_bytes": sweep(BATCH, taps),
+        "l3ac_sdr_scratch_bytes": sweep(BATCH, ([1, 4088, 4089, 4090, 5000, TOP - 8], [0, TOP]), taps) + extent,  # 4089 + 8 - 1: one segment
+    }
+
+
+SDR_LAUNCH = {
+    "l3ac_correlate": (
+        "u u_stride v v_stride batch max_samples samples lags out scratch scratch_bytes stream",
+        [F, 100, F, 100, 2, 100, [50, 100], 8, F, F, BIG, None],
+        shape()[:5] + LENS + SCRATCH + [("u", None), ("v", None), ("out", None), ("u_stride", 99), ("v_stride", 99), ("lags", 0), ("lags", 1025),
+                                        ("max_samples", TOP - 4)]),
+    "l3ac_toeplitz_solve": (
+        "r b batch length x error valid scratch scratch_bytes stream",
+        [F, F, 2, 8, F, F, F, F, BIG, None],
+        [("batch", 0), ("batch", 65536), ("batch", -1), ("length", 0), ("length", 1025), ("r", None), ("b", None), ("x", None), ("error", None),
+         ("valid", None)] + SCRATCH),
+    "l3ac_sdr": (
+        "ref ref_stride est est_stride batch max_samples samples filter_length load out valid filter corr scratch scratch_bytes stream",
+        [F, 100, F, 100, 2, 100, [50, 100], 8, 0.001, F, F, None, None, F, BIG, None],
+        shape()[:5] + LENS + SCRATCH + [("ref", None), ("est", None), ("out", None), ("valid", None), ("ref_stride", 99), ("est_stride", 99),
+                                        ("filter_length", 0), ("filter_length", 1025), ("load", -1.0), ("load", "inf"), ("load", "nan"),
+                                        ("max_samples", TOP - 4)]),
+}
+
+
+def launch_cases(lib, fn: str, spec) -> dict:
+    names, base, wrong = spec
     params = names.split()
     assert len(params) == len(base) == len(_capi.SIGNATURES[fn][1]), fn
     singles = [{str(params.index(p)): v} for p, v in wrong]
@@ -207,13 +240,14 @@ def message(err):
 
 def main() -> None:
     lib = _capi.load_library()
-    host = {}
-    for fn, calls in host_calls().items():
-        host[fn] = []
-        for args in calls:
-            ret, err, out = run_call(lib, fn, args)
-            host[fn].append([args, ret, message(err), out])
-    launch = {fn: launch_cases(lib, fn) for fn in LAUNCH}
+    host, launch = {}, {}
+    for host_part, launch_part in ((host_calls(), LAUNCH), (sdr_host_calls(), SDR_LAUNCH)):  # in the order recorded: messages keep their index
+        for fn, calls in host_part.items():
+            host[fn] = []
+            for args in calls:
+                ret, err, out = run_call(lib, fn, args)
+                host[fn].append([args, ret, message(err), out])
+        launch.update({fn: launch_cases(lib, fn, spec) for fn, spec in launch_part.items()})
     # one line per entry: "messages" [text], "host" {entry: [[args, return value, message or null, output buffers or null]]},
     # "launch" {entry: {"params", "base" (the valid call), "ret", "cases": [[{index of the parameter: wrong value}, message]]}}
     text = json.dumps({"messages": MESSAGES, "host": host, "launch": launch}, separators=(",", ":"))

@@ -117,6 +117,40 @@ def test_library_exports_every_declared_symbol():
     assert lib.l3ac_hop_length(None) == 0
 
 
+def test_binding_matches_the_header_type_by_type():
+    """Every prototype of include/l3ac_hip.h against _capi.SIGNATURES: the return type, the number of arguments, each scalar's type,
+    and that each pointer is bound as one.  (A c_int32 slot where the header says int64_t or double reads the wrong register.)"""
+    header = (REPO / "include" / "l3ac_hip.h").read_text()
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    code = re.sub(r"//[^\n]*", " ", code)
+    returns = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "void": None, "const char*": ctypes.c_char_p}
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
+    protos = re.findall(r"(?<![\w*])(const\s+char\s*\*|int|int32_t|int64_t|void)\s+(l3ac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", code)
+    assert len(protos) >= 100 and len({name for _, name, _ in protos}) == len(protos)
+    assert {name for _, name, _ in protos} == set(_capi.SIGNATURES)
+    wrong = []
+    for ret, name, params in protos:
+        restype, argtypes = _capi.SIGNATURES[name]
+        if restype is not returns[re.sub(r"\s*\*", "*", " ".join(ret.split()))]:
+            wrong.append(f"{name}: returns {ret}, bound as {restype}")
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if params == ["void"]:
+            params = []
+        if len(params) != len(argtypes):
+            wrong.append(f"{name}: {len(params)} parameters, {len(argtypes)} bound")
+            continue
+        for i, (p, bound) in enumerate(zip(params, argtypes)):
+            if "*" in p:
+                ok = bound in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(bound, type) and issubclass(bound, ctypes._Pointer))
+            else:
+                kind = [t for t in p.split()[:-1] if t != "const"]  # the type's words, without the parameter's name
+                assert len(kind) == 1 and kind[0] in scalars, f"{name}: parameter {i} `{p}` is no scalar this test knows"
+                ok = bound is scalars[kind[0]]
+            if not ok:
+                wrong.append(f"{name}: parameter {i} `{p}` bound as {bound}")
+    assert not wrong, "\n".join(wrong)
+
+
 def test_bf16x3_split_is_exact():
     """The operand split of the bf16x3 kernels (include/l3ac_hip.h, kernels/split_bf16.hpp), evaluated by the library's
     host routine that also builds the weight images — no GPU involved: three bf16 planes add back to the fp32 value

@@ -2,7 +2,8 @@
 the commit before the metric families got their shared base (csrc/kernels/metric_common.hpp, l3ac_amd/_metric.py) returned — every
 ``*_scratch_bytes``, ``*_frames``, ``*_blocks``, ``*_lags``, ``*_defaults`` value and table length over a grid of arguments, and for every
 launch entry the return code and the message of calls with one wrong argument and with two (which error wins).  The replay requires
-equality of every value and every string.  tests/golden/make_metric_contract.py wrote the file and states its layout."""
+equality of every value and every string.  tests/golden/make_metric_contract.py wrote the file and states its layout.  The SDR family's
+records were appended from the commit before every context-free entry became one definition in its family's file."""
 import json
 from pathlib import Path
 
@@ -71,5 +72,6 @@ def test_refused_launch_calls_fail_with_the_recorded_code_and_message(fn):
 
 def test_the_fixture_covers_every_metric_entry():
     names = [n for n in _capi.SIGNATURES
-             if n.split("_")[1] in ("stft", "mel", "log", "signal", "stoi", "loudness", "apply", "pitch", "xcorr", "align", "dct", "mfcc", "dtw", "lpc")]
+             if n.split("_")[1] in ("stft", "mel", "log", "signal", "stoi", "loudness", "apply", "pitch", "xcorr", "align", "dct", "mfcc", "dtw", "lpc",
+                                    "correlate", "toeplitz", "sdr")]
     assert sorted(names) == sorted(set(CONTRACT["host"]) | set(CONTRACT["launch"]))

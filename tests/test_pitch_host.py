@@ -154,12 +154,6 @@ def test_exports_and_abi_version():
     assert re.search(r"#define\s+L3AC_ABI_VERSION\s+5\b", header) and _capi.ABI_VERSION == 5  # additive: the version stays
     lib = _capi.load_library()
     assert lib.l3ac_abi_version() == 5
-    for name, ret in (("l3ac_pitch_lags", "int"), ("l3ac_pitch_frames", "int64_t"), ("l3ac_pitch_scratch_bytes", "int64_t"), ("l3ac_pitch", "int"),
-                      ("l3ac_pitch_metrics", "int")):
-        m = re.search(r"\b" + ret + r"\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S)
-        assert m, f"{name} is not declared"
-        assert len(m.group(1).split(",")) == len(_capi.SIGNATURES[name][1]), name
-        assert hasattr(lib, name)
 
 
 # ---- the oracle on known periods --------------------------------------------------------------------------------------------------------------

@@ -39,7 +39,5 @@ def test_ragged_entries_are_declared_and_bound():
     for name, n_args in (("l3ac_encode_ragged", 10), ("l3ac_decode_ragged", 8)):
         m = re.search(rf"int {name}\(([^;]*)\);", header)
         assert m, f"{name} missing from the header"
-        assert len(m.group(1).split(",")) == n_args
-        restype, argtypes = _capi.SIGNATURES[name]
-        assert len(argtypes) == n_args
+        assert len(m.group(1).split(",")) == n_args  # (that the binding has as many, of the header's types: tests/test_host.py)
     assert "#define L3AC_ABI_VERSION 5" in header  # additive entries: the ABI stays at 5
