@@ -700,6 +700,80 @@ int l3ac_sdr(const float* ref, int64_t ref_stride, const float* est, int64_t est
              int32_t filter_length, double load, double* out, int32_t* valid, double* filter, double* corr, void* scratch, int64_t scratch_bytes,
              void* stream);
 
+/* ---- critical-band measures: the spectrum of un-centred frames, frequency-weighted segmental SNR, weighted spectral slope distance, log-
+ * spectral distance (which states every formula and summation order) -------------------------------------------------
+ * Framing as linear prediction above: frame N in 2..2048, hop >= 1, F(n) = l3ac_lpc_frames(n, N, hop); frame t reads samples [t hop, t hop +
+ * N) of its own clip; xw[j] = (double)x[j] (double)w[j] with `window` the DEVICE copy of l3ac_lpc_window's output or NULL for the rectangular
+ * window.  n_fft: a power of two in 16..4096, n_fft >= N; h = n_fft / 2.  Everything is fp64 with contraction off.
+ * Twiddles T[m] = (cos 2 pi m / n_fft, -sin 2 pi m / n_fft), m = 0..h-1: `twiddles` is the DEVICE copy of l3ac_bands_twiddles' output and part
+ * of the definition.  FFT: complex radix-2 decimation in time; z[bitrev(j)] = (xw[j], 0) for j < N, (0, 0) up to n_fft; for spans L = 2, 4, ..,
+ * n_fft and j = 0..L/2-1, with w = T[j n_fft / L], a = z[i + j], b = z[i + j + L/2]: t_re = w_re b_re - w_im b_im, t_im = w_re b_im + w_im b_re
+ * (four rounded products, one rounded subtraction or addition each), a' = a + t, b' = a - t.  Bins k = 0..h-1 are kept: P[k] = re re + im im,
+ * A[k] = sqrt(P[k]) correctly rounded; S = sum_k A[k] as 64 interleaved partial sums (partial l takes k = l mod 64 in increasing k from +0)
+ * folded s[l] += s[l+g] for g = 32, 16, .., 1.
+ * Band filters: `weights` is the DEVICE copy of l3ac_band_weights' output, [bands][h] fp64, bands in 2..64; a band sum of v is sum_k W[i][k]
+ * v[k] over the band's run of non-zero weights in increasing k from +0 (the product rounded, then the sum).
+ * fwSegSNR of a frame: m[k] = A[k] / S (normalize = 1) or A[k]; M[i] the band sum of m on each side; d = Mr_i - Me_i, err_i = d d where that is
+ * above 2^-52, else 2^-52; w_i = pow(Mr_i, gamma); snr_i = 10 log10((Mr_i Mr_i) / err_i); (sum_i w_i snr_i) / (sum_i w_i), both from +0 in
+ * band order, clamped to [-10, 35]; the frame counts iff S > 0 on both sides.
+ * WSS of a frame, per side: E[i] = the band sum of P where that is above 1e-10, else 1e-10; e[i] = 10 log10(E[i]); s[i] = e[i+1] - e[i], i =
+ * 0..bands-2; "rising at i" is E[i+1] > E[i]; the nearest peak of i: rising: n = i, while n <= bands-2 and rising at n: n++, peak at n;
+ * otherwise n = i, while n >= 0 and not rising at n: n--, peak at n + 1; emax = e[first i of the largest E]; W_side[i] = (20 / ((20 + emax)
+ * - e[i])) (1 / ((1 + e[peak]) - e[i])).  W[i] = (W_r[i] + W_e[i]) / 2, d = s_r[i] - s_e[i]; the frame value is (sum_i W[i] (d d)) / (sum_i
+ * W[i]), both from +0 in band order.
+ * LSD of a frame: sqrt((sum_k (10 log10(max(Pr[k], 1e-10)) - 10 log10(max(Pe[k], 1e-10)))^2) / h), the sum as S's.
+ * Per pair (at most 16384 frames): fw_seg_snr_db the mean of the counted frames' values summed in frame order, NaN for none; wss: all V = F
+ * frames' values sorted ascending, the first k = floor(trim V + 0.5) summed in that order from +0 and divided by k, NaN for V = 0 or k = 0;
+ * lsd_db the mean of all frames' values summed in frame order, NaN for none.
+ *   l3ac_bands_default_fft:            HOST only: the smallest power of two >= max(2 frame, 16); < 0 for frame outside 2..2048.
+ *   l3ac_bands_twiddles:               HOST only: T as n_fft doubles (re, im interleaved); same protocol as l3ac_mel_weights (returns the
+ *                                      count; nothing is written when out is NULL or cap is below it).  T[0] = (1, 0), T[n_fft / 4] = (0, -1)
+ *                                      exactly; the others are designed in long double on an angle mirrored into [0, pi / 4], rounded once.
+ *   l3ac_bands_critical:               HOST only: the default table as 50 doubles: 25 centre frequencies, then 25 bandwidths, in Hz.
+ *   l3ac_band_weights:                 HOST only: sample_rate in 8000..192000; centre_hz, bandwidth_hz: `bands` doubles each.  With f0 =
+ *                                      centre / (fs / 2) h and bw = bandwidth / (fs / 2) h in fp64: W[i][k] = exp(-11 ((k - floor(f0)) / bw)^2 +
+ *                                      ln(min_j bandwidth_j) - ln(bandwidth_i)) in long double, rounded once, and 0 where that is <=
+ *                                      exp(-30 / (2 * 2.303)).  Same protocol (bands h doubles).  < 0 for a centre outside [0, fs / 2), a
+ *                                      bandwidth that is not positive and finite, or a band without a non-zero weight.
+ *   l3ac_frame_spectrum_scratch_bytes: the minimum scratch of l3ac_frame_spectrum and l3ac_band_energies: 256 ceil(4 batch / 256) bytes.
+ *   l3ac_frame_spectrum:               audio [batch] rows of max_samples floats, audio_stride floats apart; samples: HOST array of batch
+ *                                      lengths in 1..max_samples, or NULL -> with F = F(max_samples): spectrum [batch][F][h][2] fp64 (re, im);
+ *                                      power, magnitude (or NULL) [batch][F][h] fp64 = P, A; magnitude_sum (or NULL) [batch][F] fp64 = S;
+ *                                      frames (or NULL) [batch] int32.  Rows at and after a clip's own F(n) are NaN.
+ *   l3ac_band_energies:                -> power, magnitude [batch][F][bands] fp64: the band sums of P (before the floor) and of A.
+ *   l3ac_band_metrics_scratch_bytes:   the minimum scratch of l3ac_band_metrics: 256 ceil(4 batch / 256) + 256 ceil(24 batch F / 256) + 256
+ *                                      ceil(4 batch F / 256) bytes (the lengths, the frames' three values, the frames' flags); < 0 for
+ *                                      unsupported parameters or F(max_samples) > 16384.
+ *   l3ac_band_metrics:                 ref, est as audio above; gamma finite, normalize 0 or 1, trim in (0, 1] -> out [batch][3] fp64 =
+ *                                      fw_seg_snr_db, wss, lsd_db; counts [batch][2] int32 = frames, frames counted for the fwSegSNR;
+ *                                      frame_values (or NULL) [batch][F][3] fp64, the fwSegSNR NaN where not counted; and the test hooks (or
+ *                                      NULL): magnitude_sum [batch][F][2] = S of ref, est; band_power, band_magnitude [batch][F][2][bands]
+ *                                      = the band sums of P (before the floor) and of m; peaks [batch][F][2][bands] int32 = the nearest
+ *                                      peak's band of i = 0..bands-2, then the first band of the largest E.
+ * All but `samples` are device buffers.  Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee
+ * and calling convention: as the quality metrics above (a pair's results depend on its own samples only — not on the batch, its row, the
+ * strides, the scratch size or what lies at or after its length, which is never read; no atomics; enqueue only, nothing allocated, no
+ * synchronisation, capturable).  Non-finite samples leave the frames that read them, and their pair's means, unspecified and disturb
+ * nothing else: no address, bound or loop count comes from a sample value. */
+int32_t l3ac_bands_default_fft(int32_t frame);
+int64_t l3ac_bands_twiddles(int32_t n_fft, double* out, int64_t cap);
+int64_t l3ac_bands_critical(double* out, int64_t cap);
+int64_t l3ac_band_weights(int32_t sample_rate, int32_t n_fft, int32_t bands, const double* centre_hz, const double* bandwidth_hz, double* out,
+                          int64_t cap);
+int64_t l3ac_frame_spectrum_scratch_bytes(int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft);
+int l3ac_frame_spectrum(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t frame,
+                        int32_t hop, int32_t n_fft, const float* window, const double* twiddles, double* spectrum, double* power, double* magnitude,
+                        double* magnitude_sum, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_band_energies(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t frame,
+                       int32_t hop, int32_t n_fft, const float* window, const double* twiddles, const double* weights, int32_t bands, double* power,
+                       double* magnitude, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t l3ac_band_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft, int32_t bands);
+int l3ac_band_metrics(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                      const int32_t* samples, int32_t frame, int32_t hop, int32_t n_fft, const float* window, const double* twiddles,
+                      const double* weights, int32_t bands, double gamma, int32_t normalize, double trim, double* out, int32_t* counts,
+                      double* frame_values, double* magnitude_sum, double* band_power, double* band_magnitude, int32_t* peaks, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -192,6 +192,16 @@ SIGNATURES = {
     "l3ac_toeplitz_solve": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "l3ac_sdr_scratch_bytes": (_I64, [_I32, _I64, _I32]),
     "l3ac_sdr": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_bands_default_fft": (_I32, [_I32]),
+    "l3ac_bands_twiddles": (_I64, [_I32, _P, _I64]),
+    "l3ac_bands_critical": (_I64, [_P, _I64]),
+    "l3ac_band_weights": (_I64, [_I32, _I32, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I64]),
+    "l3ac_frame_spectrum_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32]),
+    "l3ac_frame_spectrum": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_band_energies": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_band_metrics_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32, _I32]),
+    "l3ac_band_metrics": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _I32, C.c_double, _I32, C.c_double,
+                                    _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

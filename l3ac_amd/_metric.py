@@ -1,4 +1,4 @@
-"""What the metric modules share (metrics, loudness, pitch, align, mcd, lpc, sdr): the library's host values and
+"""What the metric modules share (metrics, loudness, pitch, align, mcd, lpc, sdr, bands): the library's host values and
 tables, the checks of ``(batch, samples)`` audio and of ``lengths=``, the per-device cache of uploaded tables, the scratch allocation and
 the result columns.  Each module's parameters and the order of its checks are its own."""
 from __future__ import annotations
@@ -32,7 +32,8 @@ def host_table(fn: str, dtype: torch.dtype, *args) -> torch.Tensor:
 
 
 # (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "stoi_basis") / (device, "dct", n_mels, n_coeffs) /
-# (device, "lpc_window", frame) -> device copy of the table; every metric module's tables live here
+# (device, "lpc_window", frame) / (device, "bands_twiddles", n_fft) / (device, "band_weights", sample_rate, n_fft, centres, widths) -> device
+# copy of the table; every metric module's tables live here
 tables = {}
 
 

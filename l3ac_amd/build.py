@@ -57,6 +57,7 @@ SOURCES = [
     "kernels/mcd.hip",
     "kernels/lpc.hip",
     "kernels/sdr.hip",
+    "kernels/bands.hip",
 ]
 
 

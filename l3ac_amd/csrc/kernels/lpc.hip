@@ -15,8 +15,8 @@
 //     forms            pairs only.  Lane i: the inner sums sum_j r[|i - j|] a[j] of the three quadratic forms in increasing j; lane 0: the
 //                      outer sums in increasing i, the cepstra of 1 / A, the four values and their clamps
 //   lpc_pair_kernel    one workgroup per pair: the frames' values of a measure go to LDS (+inf where the frame is not valid on both
-//                      sides, and up to the next power of two), a bitonic sort orders them — the sorted sequence of a set of numbers does
-//                      not depend on how it was reached — and lane 0 sums the first k = floor(trim V + 0.5) in that order.  16384 fp64
+//                      sides, and up to the next power of two), a bitonic sort orders them (lds_sort of metric_common.hpp) — the sorted
+//                      sequence of a set of numbers does not depend on how it was reached — and lane 0 sums the first k = floor(trim V + 0.5) in that order.  16384 fp64
 //                      values are 128 KiB of the CU's 160 KiB of LDS: this is what caps a pair at 16384 frames.  The segmental SNR is
 //                      the sum of the counted frames' values in frame order over their count.
 //
@@ -291,17 +291,7 @@ __global__ __launch_bounds__(LQ_THREADS) void lpc_pair_kernel(const double* __re
     for (int m = 0; m < 3; ++m) {
         for (int f = tid; f < n_pad; f += LQ_THREADS) buf[f] = (f < frames && (fl[f] & 1)) ? vals[(row0 + f) * 4 + m] : __builtin_huge_val();
         __syncthreads();
-        for (int size = 2; size <= n_pad; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int i = tid; i < (n_pad >> 1); i += LQ_THREADS) {
-                    const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                    const bool up = (lo & size) == 0;
-                    const double x = buf[lo], y = buf[hi];
-                    if ((x > y) == up) buf[lo] = y, buf[hi] = x;
-                }
-                __syncthreads();
-            }
-        }
+        lds_sort<LQ_THREADS>(buf, n_pad);
         if (tid == 0) {
             double s = 0.0;
             for (int f = 0; f < keep; ++f) s = s + buf[f];

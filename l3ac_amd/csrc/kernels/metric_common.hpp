@@ -1,5 +1,5 @@
-// What the metric families share (metrics, stoi, loudness, pitch, align, mcd, lpc, sdr .hip): the fixed-order workgroup
-// reductions on the device, and on the host the scratch layout, the checks of a batch of clips and the staging of their lengths.  Each
+// What the metric families share (metrics, stoi, loudness, pitch, align, mcd, lpc, sdr, bands .hip): the fixed-order workgroup
+// reductions and the LDS sort on the device, and on the host the scratch layout, the checks of a batch of clips and the staging of their lengths.  Each
 // family's arithmetic, geometry and parameter checks are its own.
 #pragma once
 
@@ -42,6 +42,24 @@ __device__ __forceinline__ double fold64(double v) {
 #pragma unroll
     for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
     return v;
+}
+
+// The ascending sort of n_pad fp64 values in LDS (a power of two; the caller pads with +inf) by a whole workgroup of THREADS (lpc.hip,
+// bands.hip: the trimmed means): a bitonic network.  The sorted sequence of a set of numbers does not depend on how it was reached.  The
+// values are in place behind a barrier of the caller's; ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void lds_sort(double* buf, int n_pad) {
+    for (int size = 2; size <= n_pad; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = threadIdx.x; i < (n_pad >> 1); i += THREADS) {
+                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const double x = buf[lo], y = buf[hi];
+                if ((x > y) == up) buf[lo] = y, buf[hi] = x;
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // ---- host: the caller's scratch ---------------------------------------------------------------------------------------------------------
