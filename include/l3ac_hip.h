@@ -824,7 +824,25 @@ int l3ac_unpack_stream(const uint32_t* state_in, uint32_t* state_out, int32_t st
 
 /* ---- single blocks of a context's network, for per-kernel parity tests ------------------------------ */
 /* `block` is the reference state-dict prefix of the block inside its module file, e.g. "encoder.blocks.1.0.module".
- * Shapes: x / y are [batch][frames][channels] frame-major. */
+ * Shapes: x / y are [batch][frames][channels] frame-major.
+ *
+ * Size limits (DESIGN.md section 3.20.1 lists every 32-bit quantity of the codec kernels with its bound).  A tensor may hold 2^31
+ * elements and more: row, clip and byte offsets are 64-bit, and the row kernels switch to a 64-bit instantiation.  What is bounded, for
+ * these entries and for l3ac_encode / l3ac_decode alike — a call past a limit is refused with L3AC_EINVAL before any launch, and by
+ * these entries before the context's workspace is sized for it:
+ *   batch <= 65535 (grid dimension of the per-clip kernels);
+ *   frames <= L3AC_MAX_CLIP_FRAMES (frame numbers inside a clip are 32-bit, with a tile and a halo added) and batch * frames <
+ *     L3AC_MAX_ROWS (tile numbers are 32-bit; the kernels' own launchers ask tiles < 2^31 - 65536);
+ *   rows = batch * frames < 2^31 wherever a convolution is evaluated as a GEMM (conv_k3, the unfused LegacyUnit, the gated up conv);
+ *   conv_unit_ring_kernel (C = 48 by default, C = 24 under "narrow_ring" = 2): frames * C < L3AC_MAX_RING_CLIP_ELEMS — it keeps
+ *     offsets INSIDE a clip in 32 bits;
+ *   an up layer in either form (the row kernel's linear upsampling, up_fused_kernel): frames * scale <= L3AC_MAX_LERP_FRAMES_OUT —
+ *     the source position is computed in fp32 as ATen does; past 2^23 output frames per clip it is no longer within half a frame of
+ *     the exact one: the row kernel can then read the row after the clip's last, the fused kernel take the wrong neighbour frame. */
+#define L3AC_MAX_CLIP_FRAMES 2147418112      /* 2^31 - 65536 */
+#define L3AC_MAX_ROWS 17179869184LL          /* 2^34 */
+#define L3AC_MAX_RING_CLIP_ELEMS 536870912   /* 2^29 */
+#define L3AC_MAX_LERP_FRAMES_OUT 8388608     /* 2^23 */
 int l3ac_op_first_block(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t samples, float* y, void* stream);
 /* The stem as l3ac_encode runs it: audio [batch] rows of `samples` valid floats, `audio_stride` floats apart (>= samples; what lies
  * between the rows is not read), -> y [batch][frames][d0] with frames >= samples > 0: frames samples .. frames - 1 are the zero

@@ -547,8 +547,19 @@ int l3ac_op_first_block_at(l3ac_ctx* ctx, const float* audio, int32_t batch, int
     return launch_first_block((hipStream_t)stream, ctx->first, audio, audio_stride, batch, samples, frames, y);
 }
 
+// The size limits every block entry shares, asked before the workspace is sized for the call: frame numbers inside a clip are ints with a
+// tile and a halo added (dwconv_ln_kernel, the enhance kernels, the LegacyUnit and head kernels, the stem), and 2^34 rows keep every
+// kernel's tile count -- tiles of 14 frames and more, plus one per clip -- below 2^31 - 65536
+static int op_shape_ok(int batch, int frames) {
+    L3AC_REQUIRE(frames <= L3AC_MAX_CLIP_FRAMES, "block entry: %d frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", frames);
+    L3AC_REQUIRE((int64_t)batch * frames < L3AC_MAX_ROWS, "block entry: batch * frames = %lld, the limit is 2^34 rows (32-bit tile numbers)",
+                 (long long)batch * frames);
+    return L3AC_OK;
+}
+
 // (h: 4C floats per row, or the wide ConvUnit front end's planes of whole 32-frame tiles when that is more)
 #define L3AC_OP_SCRATCH(c_max)                                                                                    \
+    L3AC_TRY(op_shape_ok(batch, frames));                                                                         \
     L3AC_TRY(workspace_ensure(ctx, (size_t)batch * frames * (c_max), (size_t)batch * frames * (c_max),           \
                               std::max((size_t)batch * frames * 4 * (c_max),                                      \
                                        (conv_unit_wide_scratch_bytes((c_max), (int64_t)batch * frames) + 3) / 4), \
@@ -559,6 +570,7 @@ int l3ac_op_conv_unit(l3ac_ctx* ctx, const char* block, const float* x, int32_t 
     L3AC_ENTER_WS(ctx, stream);
     const ConvUnitW* w = lookup(ctx->by_unit, block, "ConvUnit");
     if (!w) return L3AC_EINVAL;
+    L3AC_TRY(conv_unit_shape_ok(ctx, *w, x == y, frames));
     L3AC_OP_SCRATCH(w->c);
     return run_conv_unit(ctx, (hipStream_t)stream, *w, x, y, batch, frames);
 }
@@ -596,6 +608,7 @@ int l3ac_op_up_layer(l3ac_ctx* ctx, const char* block, const float* x, int32_t b
     L3AC_ENTER_WS(ctx, stream);
     const UpW* w = lookup(ctx->by_up, block, "up-layer");
     if (!w) return L3AC_EINVAL;
+    L3AC_TRY(up_layer_frames_ok(frames, w->scale));
     L3AC_OP_SCRATCH(w->cout);
     return run_up(ctx, (hipStream_t)stream, *w, x, ctx->ws.a, y, batch, frames);
 }
@@ -608,6 +621,7 @@ int l3ac_op_enhance_up(l3ac_ctx* ctx, const char* enhance_block, const char* up_
     if (!e || !w) return L3AC_EINVAL;
     L3AC_REQUIRE(e->c == w->cin, "enhance_up: blocks of different widths (%d vs %d)", e->c, w->cin);
     L3AC_REQUIRE(x != y, "op_enhance_up: x and y must not alias (x is only read)");
+    L3AC_TRY(up_layer_frames_ok(frames, w->scale));
     L3AC_OP_SCRATCH(w->cin > w->cout ? w->cin : w->cout);
     // the pipeline's fused form: gate applied inside the up conv's A staging; x is only read
     return run_enhance_up(ctx, (hipStream_t)stream, *e, *w, const_cast<float*>(x), ctx->ws.a, y, batch, frames);

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
         if (G::RESIDENT && !tile_ok) break;
         const int clip = tile_ok ? tile / tiles_per_clip : 0;
         const int t0 = tile_ok ? (tile - clip * tiles_per_clip) * G::TF : 0;
-        const float* const xc = x + (int64_t)clip * frames * C + 4 * lg;  // (32-bit offsets inside a clip: frames * C < 2^31 / 4)
+        const float* const xc = x + (int64_t)clip * frames * C + 4 * lg;  // (32-bit offsets inside a clip: frames * C < 2^31 / 4, launch_conv_unit_ring)
         bool frame_ok[G::FT];
         bf16x8 ap[G::FT][G::K1][3];
 #pragma unroll
@@ -391,9 +391,18 @@ bool conv_unit_ring_supported(int c) { return c == 24 || c == 48; }
 // round 5); the context option "narrow_ring" = 2 routes every supported width here (tests)
 bool conv_unit_ring_preferred(int c) { return c == 48; }
 
+// the kernel's tap loads take (unsigned)(frame * C + channel) from ints as the offset inside a clip
+int conv_unit_ring_clip_ok(int frames, int c) {
+    L3AC_REQUIRE((int64_t)frames * c < L3AC_MAX_RING_CLIP_ELEMS,
+                 "conv_unit_ring: clip too long: frames * C = %lld, the limit is 2^29 (32-bit offsets inside a clip; frames=%d C=%d)",
+                 (long long)frames * c, frames, c);
+    return L3AC_OK;
+}
+
 // x must not alias y (neighbouring tiles read each other's halo frames)
 int launch_conv_unit_ring(hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames) {
     L3AC_REQUIRE(x != y && w.ring_img && batch > 0 && frames > 0, "conv_unit_ring: bad arguments");
+    L3AC_TRY(conv_unit_ring_clip_ok(frames, w.c));
     // Geometries measured on the 256-clip step (profiles/r03/README.md; ms for the stage's launches, conv_unit_split_kernel beside):
     //   C = 48 (2 launches)  split 0.89 | resident 16 x 1: 0.83-0.85, 12 x 1: 0.88 | ring 8 x 2: 0.93 | 32 frames per wave, 8 / 12 x 1: 0.94 / 0.90
     //                        | fragments read one piece ahead 16 x 1: 0.84, 12 x 1: 0.87

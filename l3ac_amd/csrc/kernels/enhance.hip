@@ -176,6 +176,7 @@ __global__ __launch_bounds__(TILE) void head_kernel(const float* __restrict__ x,
 
 int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, int batch, int frames, int c, float* yi, const RaggedClips* rc) {
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && frames > 0, "enhance: bad shape");
+    L3AC_REQUIRE(frames <= L3AC_MAX_CLIP_FRAMES, "enhance: %d frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", frames);
     ProfScope prof(s, rc ? "enhance_branches_kernel<RAGGED>" : "enhance_branches_kernel", 2.0 * (28.0 + 34.0) * batch * frames,
                    4.0 * 5.0 * batch * frames);
     const dim3 grid((unsigned)ceil_div64(frames, TILE), (unsigned)batch);
@@ -186,6 +187,7 @@ int launch_enhance_branches(hipStream_t s, const EnhanceW& w, const float* x, in
 }
 
 int launch_enhance_stats(hipStream_t s, float* yi, int batch, int frames, float* stats, const RaggedClips* rc) {
+    L3AC_REQUIRE(batch > 0 && frames > 0 && frames <= L3AC_MAX_CLIP_FRAMES, "enhance: bad shape, or more than 2^31 - 65536 frames per clip");
     ProfScope prof(s, rc ? "enhance_stats_kernel<RAGGED>" : "enhance_stats_kernel", 16.0 * batch * frames, 48.0 * batch * frames);
     if (rc) hipLaunchKernelGGL(enhance_stats_kernel<true>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, rc->n, rc->mult);
     else hipLaunchKernelGGL(enhance_stats_kernel<false>, dim3((unsigned)batch), dim3(1024), 0, s, yi, frames, stats, nullptr, 1);
@@ -195,7 +197,7 @@ int launch_enhance_stats(hipStream_t s, float* yi, int batch, int frames, float*
 
 int launch_head(hipStream_t s, const float* x, int batch, int frames, int c, const float* w, const float* b,
                 float* audio, bool pretanh) {
-    L3AC_REQUIRE(c % 4 == 0 && batch <= 65535, "head: bad shape");
+    L3AC_REQUIRE(c % 4 == 0 && batch <= 65535 && frames <= L3AC_MAX_CLIP_FRAMES, "head: bad shape, or more than 2^31 - 65536 frames per clip");
     ProfScope prof(s, "head_kernel", 14.0 * c * batch * frames, 4.0 * (c + 1.0) * batch * frames);
     hipLaunchKernelGGL(head_kernel, dim3((unsigned)ceil_div64(frames, TILE), (unsigned)batch), dim3(TILE), 0, s, x, frames, c,
                        w, b, audio, pretanh ? 1 : 0);

@@ -183,6 +183,8 @@ __global__ __launch_bounds__(256) void first_block_split_kernel(const FirstBlock
 int launch_first_block(hipStream_t s, const FirstBlockW& w, const float* audio, int64_t audio_stride, int batch,
                        int samples, int frames, float* y, const RaggedClips* rc) {
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && frames >= samples && samples > 0, "first_block: bad shape");
+    // a workgroup's first frame plus its tile and halo is an int: blockIdx.x * TILE - HALO + i for i < TILE + 2 HALO
+    L3AC_REQUIRE(frames <= L3AC_MAX_CLIP_FRAMES, "first_block: %d frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", frames);
     const dim3 grid((unsigned)ceil_div64(frames, TILE), (unsigned)batch);
     const int* rn = rc ? rc->n : nullptr;
     const int* rs = rc ? rc->samples : nullptr;

@@ -542,7 +542,7 @@ int launch_legacy_t(hipStream_t s, const LegacyW& w, const float* x, float* y, i
     const double rows = (double)batch * frames;
     const int tiles_per_clip = (int)ceil_div64(frames, FRAMES);
     const int64_t total = (int64_t)tiles_per_clip * batch;
-    L3AC_REQUIRE(total < (1ll << 31), "legacy unit: too many tiles");
+    L3AC_REQUIRE(total < (1ll << 31) - 65536 && frames <= L3AC_MAX_CLIP_FRAMES, "legacy unit: too many tiles (the kernels look two grids ahead in 32 bits)");
     const unsigned grid = (unsigned)std::min<int64_t>(total, 2 * 256);  // persistent: 2 workgroups per CU
     ProfScope prof(s, split ? "legacy_unit_split_kernel" : "legacy_unit_kernel", rows * (2.0 * 7 * C * C + 2.0 * C * C + 40.0 * C),
                    rows * 8.0 * C);
@@ -583,7 +583,7 @@ int launch_legacy_unit_fused(hipStream_t s, const LegacyW& w, const float* x, fl
 }
 
 int launch_head_fused(hipStream_t s, const HeadW& w, const float* x, int batch, int frames, float* audio, bool pretanh) {
-    L3AC_REQUIRE(batch <= 65535, "head: bad arguments");
+    L3AC_REQUIRE(batch <= 65535 && frames <= L3AC_MAX_CLIP_FRAMES, "head: bad arguments, or more than 2^31 - 65536 frames per clip");
     switch (w.c) {
         case 8: return launch_head_t<8>(s, w, x, batch, frames, audio, pretanh);
         case 16: return launch_head_t<16>(s, w, x, batch, frames, audio, pretanh);

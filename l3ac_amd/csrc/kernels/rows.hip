@@ -261,6 +261,7 @@ int launch_dwconv_ln(hipStream_t s, const RowArgs& r, int lpr) {
     const int64_t blocks = ceil_div64(segs, THREADS / lpr);
     if (blocks <= 0) return L3AC_OK;
     L3AC_REQUIRE(blocks < (int64_t)1 << 31, "rows: grid too large");
+    L3AC_REQUIRE(r.frames_out <= L3AC_MAX_CLIP_FRAMES, "rows: %lld frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", (long long)r.frames_out);
     const double elems = (double)r.batch * r.frames_out * r.c;
     ProfScope prof(s, "dwconv_ln_kernel", 22.0 * elems, 8.0 * elems);
     if (r.c <= 4 * lpr)
@@ -445,6 +446,13 @@ int launch_rows(hipStream_t s, const RowArgs& r) {
     L3AC_REQUIRE(lpr <= 64 && r.c <= 4 * lpr * MAX_CH, "rows: c=%d too wide for the row kernel", r.c);
     const int lpr_pow2 = [&] { int v = 1; while (v * 4 < r.c && v < 64) v <<= 1; return v; }();  // dwconv_ln_kernel's grouping
     if (r.norm != NORM_NONE) L3AC_REQUIRE(r.nw && r.nb, "rows: norm without affine parameters");
+    // SRC_LERP evaluates ATen's source position in fp32: (t + 0.5) / scale - 0.5 is below frames_in - 0.5 for every t < frames_out while
+    // t + 0.5 and frames_in - 0.5 are exact, i.e. up to 2^23 output frames per clip; past that it can round up to frames_in, the row
+    // after the clip's last one
+    if (r.src == SRC_LERP)
+        L3AC_REQUIRE(r.frames_out <= L3AC_MAX_LERP_FRAMES_OUT,
+                     "rows: linear upsampling to %lld frames per clip: the limit is 2^23 (fp32 source positions; %lld frames x %d)",
+                     (long long)r.frames_out, (long long)r.frames_in, r.scale);
 #define L3AC_ROWS_CASE(S, N) \
     if (r.src == S && r.norm == N) return launch_rows_t<S, N>(s, r, lpr)
     L3AC_ROWS_CASE(SRC_PLAIN, NORM_LN);

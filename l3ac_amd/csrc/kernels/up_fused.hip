@@ -300,7 +300,10 @@ template <int CIN, int COUT>
 int launch_uf(hipStream_t s, const UpFusedArgs& a) {
     const int tiles_per_clip = (a.frames + UF_CORE - 1) / UF_CORE;
     const int64_t tiles = (int64_t)a.batch * tiles_per_clip;
-    L3AC_REQUIRE(tiles < ((int64_t)1 << 31) - 65536 && (int64_t)a.frames * a.scale < ((int64_t)1 << 30), "up_fused: too many tiles");
+    // (frames * scale: the kernel takes the neighbours of the lerp's source frame i0 from {f - 1, f, f + 1}, true while the fp32 source
+    // position is within half a frame of the exact one: d + 0.5 exact and T 2^-24 <= 1 / (2 S), i.e. T S <= 2^23; run_enhance_up asks first)
+    L3AC_REQUIRE(tiles < ((int64_t)1 << 31) - 65536 && (int64_t)a.frames * a.scale <= L3AC_MAX_LERP_FRAMES_OUT,
+                 "up_fused: too many tiles, or more than 2^23 output frames per clip");
     const double rows = (double)a.batch * a.frames;
     char name[64];
     std::snprintf(name, sizeof(name), "up_fused_kernel<%d,%d>", CIN, COUT);

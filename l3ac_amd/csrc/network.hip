@@ -762,7 +762,23 @@ int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, flo
     return launch_rows(s, r);
 }
 
+// The limit of an up layer in either form (launch_rows SRC_LERP, launch_up_fused): both take the source position of the linear upsampling
+// in fp32.  Asked before the layer's first launch, and by the l3ac_op_* entries before they size the workspace.
+int up_layer_frames_ok(int frames, int scale) {
+    L3AC_REQUIRE((int64_t)frames * scale <= L3AC_MAX_LERP_FRAMES_OUT,
+                 "up layer: %d frames x %d: more than 2^23 output frames per clip (fp32 source positions of the linear upsampling)", frames, scale);
+    return L3AC_OK;
+}
+
+// The limits of a ConvUnit call that depend on the form it takes (run_conv_unit's choice): conv_unit_ring_kernel's clip length
+int conv_unit_shape_ok(const l3ac_ctx* ctx, const ConvUnitW& w, bool in_place, int frames) {
+    const bool fused = !in_place && !use_wide(ctx, w) && !ctx->cfg.grn_exact && conv_unit_fused_supported(w.c);
+    if (fused && conv_unit_fused_takes_ring(w, ctx->gemm_split, ctx->narrow_ring)) return conv_unit_ring_clip_ok(frames, w.c);
+    return L3AC_OK;
+}
+
 int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tmp, float* y, int batch, int frames) {
+    L3AC_TRY(up_layer_frames_ok(frames, w.scale));
     GemmArgs g{};  // 1x1 conv (modules.py:161)
     g.a = x; g.lda = w.cin; g.w = w.w; g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
@@ -788,6 +804,7 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     const bool wide_up = ctx->img(w.w) != nullptr && gemm_split_eligible(w.cout, w.cin);
     if (w.cin % 16 != 0 || e.c != w.cin || wide_up) {
         L3AC_REQUIRE(tmp != nullptr, "enhance_up: scratch missing");
+        L3AC_TRY(up_layer_frames_ok(frames, w.scale));
         // the pipeline calls this in place (x == y: the gate may overwrite x); any other caller's x is only read, so the gated
         // rows go to the hidden-tensor scratch (free here: the up layer's GEMM writes tmp)
         float* gated = x;
@@ -800,6 +817,7 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     }
     Workspace& ws = ctx->ws;
     const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
+    L3AC_TRY(up_layer_frames_ok(frames, w.scale));
     L3AC_TRY(launch_enhance_branches(s, e.t, x, batch, frames, e.c, ws.yi, ctx->rag ? &rc : nullptr));
     L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr));
     if (use_up_fused(ctx, w) && x != y) {  // gate, conv, upsample and ChannelNorm in one kernel; it reads x while it writes y

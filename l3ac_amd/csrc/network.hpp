@@ -185,6 +185,8 @@ bool conv_unit_fused_supported(int c);
 int launch_conv_unit_fused(hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames, bool split, int ring = 0);
 // third form of the narrow ConvUnit (kernels/conv_unit_ring.hip): 16 frames per wave, weights through an LDS-DMA ring
 bool conv_unit_ring_supported(int c);
+bool conv_unit_fused_takes_ring(const ConvUnitW& w, bool split, int ring);  // launch_conv_unit_fused's choice
+int conv_unit_ring_clip_ok(int frames, int c);  // L3AC_EINVAL (message set) for a clip of L3AC_MAX_RING_CLIP_ELEMS elements or more
 bool conv_unit_ring_preferred(int c);  // the widths the pipeline routes there by default
 int launch_conv_unit_ring(hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames);
 std::vector<unsigned char> conv_unit_ring_image(const float* w1, const float* w2, int c);  // w1 [4c][c], w2 [c][4c]
@@ -232,6 +234,10 @@ int launch_head_fused(hipStream_t s, const HeadW& w, const float* x, int batch, 
 int conv_unit_step(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, float** cur, float** alt, int batch, int frames);
 // all ConvUnits of one stage (wide units: clip groups outside the units, see network.hip)
 int run_conv_units(l3ac_ctx* ctx, hipStream_t s, const std::vector<ConvUnitW>& units, float** cur, float** alt, int batch, int frames);
+
+// size limits that depend on the form a call takes, for callers that ask before they size a workspace (capi.hip)
+int up_layer_frames_ok(int frames, int scale);
+int conv_unit_shape_ok(const l3ac_ctx* ctx, const ConvUnitW& w, bool in_place, int frames);
 
 // blocks (x may alias y where noted)
 int run_conv_unit(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames);  // x == y ok
