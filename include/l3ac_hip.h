@@ -774,6 +774,47 @@ int l3ac_band_metrics(const float* ref, int64_t ref_stride, const float* est, in
                       double* frame_values, double* magnitude_sum, double* band_power, double* band_magnitude, int32_t* peaks, void* scratch,
                       int64_t scratch_bytes, void* stream);
 
+/* ---- coherence: the magnitude-squared coherence per level class and the coherence speech intelligibility index CSII with its three-level
+ * form I3 (Kates & Arehart 2005; DESIGN.md section 3.23, which states every formula and summation order) ------------------------------------
+ * Framing, window, twiddles, transform and band filters as the critical-band measures above (frame N in 2..2048, hop >= 1, n_fft a power of
+ * two in 16..4096 and >= N, all of them supported here; h = n_fft / 2; X, Y the kept bins of the reference's and the estimate's frame).
+ * Everything is fp64 with contraction off.  A pair may have at most 16384 frames.
+ * Level classes, decided on the reference: E_t = sum_j xw[j]^2 as 64 interleaved partials (partial l takes j = l mod 64 in increasing j from
+ * +0) folded s[l] += s[l+g], g = 32..1; S = sum_t E_t the same way over t; M = S / F; class 0: E_t >= M, 1: E_t >= 0.1 M, 2: E_t >= 0.001 M,
+ * 3: otherwise (each product rounded once); S == 0: every frame in class 3.
+ * Sums per class c and bin k over the class's frames: Sxx = sum (Xr Xr + Xi Xi), Syy likewise, Sxy_re = sum (Xr Yr + Xi Yi), Sxy_im = sum (Xi
+ * Yr - Xr Yi).  Order: a chunk is 4 G consecutive frames, G = 16 for n_fft <= 256, 8 up to 1024, 4 at 2048, 2 at 4096; the frames of a chunk
+ * in increasing t from +0, then the chunks in increasing order from +0.  "All frames" = ((c0 + c1) + (c2 + c3)) per value.
+ * g = min((Sxy_re^2 + Sxy_im^2) / (Sxx Syy), 1), 0 where Sxx Syy == 0.  msc and msc_levels hold NaN where the count is below 2.
+ * Bands: N_i = sum_k W[i][k] (g_k Syy_k), D_i = sum_k W[i][k] ((1 - g_k) Syy_k) over the band's run of non-zero weights in increasing k from
+ * +0; T_i = 0 if N_i == 0, 1 if D_i == 0 and N_i > 0, else (clamp(10 log10(N_i / D_i), -15, 15) + 15) / 30; the value of a row is (sum_i I_i
+ * T_i) / (sum_i I_i), both from +0 in band order, NaN where the row's frame count is below 2.  i3 = (-3.47 + 1.84 low) + 9.99 mid;
+ * intelligibility = 1 / (1 + exp(-i3)).
+ *   l3ac_sii_bands:               HOST only: the critical-band table of ANSI S3.5-1997 as 63 doubles: 21 centre frequencies, 21 bandwidths
+ *                                 (upper - lower edge), 21 importances; protocol of l3ac_bands_critical.
+ *   l3ac_coherence_scratch_bytes: the minimum scratch of l3ac_coherence and l3ac_csii, each term rounded up to 256: 4 batch + 8 batch F + 4
+ *                                 batch F + 20 batch + 128 batch h + 128 batch ceil(F / (4 G)) h bytes, F = F(max_samples); < 0 for
+ *                                 unsupported parameters or F > 16384.
+ *   l3ac_coherence:               ref, est, samples, window, twiddles as l3ac_band_metrics -> every output or NULL: msc [batch][h] over all
+ *                                 frames; msc_levels [batch][4][h]; sums [batch][4][4][h] = per class Sxx, Syy, Sxy_re, Sxy_im; counts
+ *                                 [batch][5] int32 = frames, then the frames of classes 0..3; frame_class [batch][F] int32, -1 at and after a
+ *                                 clip's own frames; frame_energy [batch][F] fp64, NaN there.
+ *   l3ac_csii:                    weights [bands][h] and importance [bands] (finite, positive) DEVICE tables, bands in 2..64 -> out
+ *                                 [batch][6] fp64 = csii (all frames), csii_high, csii_mid, csii_low (classes 0, 1, 2), i3, intelligibility;
+ *                                 counts as above; band_signal, band_distortion, band_value [batch][4][bands] = N, D, T of classes 0, 1, 2
+ *                                 and, in row 3, of all frames (computed whatever the counts); sums as above; all but out may be NULL.
+ * Bit guarantee, calling convention and non-finite samples as the critical-band measures above; fp64 buffers 8-byte aligned. */
+int64_t l3ac_sii_bands(double* out, int64_t cap);
+int64_t l3ac_coherence_scratch_bytes(int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft);
+int l3ac_coherence(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples,
+                   const int32_t* samples, int32_t frame, int32_t hop, int32_t n_fft, const float* window, const double* twiddles, double* msc,
+                   double* msc_levels, double* sums, int32_t* counts, int32_t* frame_class, double* frame_energy, void* scratch,
+                   int64_t scratch_bytes, void* stream);
+int l3ac_csii(const float* ref, int64_t ref_stride, const float* est, int64_t est_stride, int32_t batch, int64_t max_samples, const int32_t* samples,
+              int32_t frame, int32_t hop, int32_t n_fft, const float* window, const double* twiddles, const double* weights,
+              const double* importance, int32_t bands, double* out, int32_t* counts, double* band_signal, double* band_distortion,
+              double* band_value, double* sums, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- streaming token wire format: ragged packing and byte sessions -------------------------------------
  * The format of the rectangular calls above, stated per byte: token t of a stream occupies bits [t*bits, (t+1)*bits) of a little-endian bit
  * stream, byte k of the stream is bits [8k, 8k+8), and a stream of n tokens is ceil(n*bits/8) bytes, its last byte zero-padded: exactly the

@@ -49,6 +49,7 @@ from .lpc import (_check_params as _check_lpc_params, lpc, lpc_defaults, lpc_fra
 from .sdr import correlate, sdr, sdr as _sdr, toeplitz_solve
 from .bands import (_check_params as _check_band_params, band_energies, band_metrics, band_metrics as _band_metrics, band_weights, critical_bands,
                     frame_spectrum)
+from .coherence import coherence, csii, csii as _csii, sii_bands
 from .resampling import _resample_bank, resample, resample_length
 from .streaming import StreamDecoder, StreamEncoder, StreamResampler
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
@@ -62,7 +63,8 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "mel_weights", "DEFAULT_SCALES", "stoi", "stoi_frames", "stoi_basis", "stoi_bands", "loudness", "loudness_gain", "apply_gain",
            "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags", "delay",
            "apply_delay", "align", "mfcc", "dtw", "mcd", "dct_table", "lpc", "lpc_metrics", "lpc_frames", "lpc_defaults", "lpc_window",
-           "sdr", "correlate", "toeplitz_solve", "frame_spectrum", "band_energies", "band_metrics", "band_weights", "critical_bands"]
+           "sdr", "correlate", "toeplitz_solve", "frame_spectrum", "band_energies", "band_metrics", "band_weights", "critical_bands",
+           "coherence", "csii", "sii_bands"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -552,7 +554,8 @@ class L3AC:
     @torch.no_grad()
     def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
                  prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False,
-                 pitch: bool = False, mcd: bool = False, lpc: bool = False, sdr: bool = False, bands: bool = False) -> dict:
+                 pitch: bool = False, mcd: bool = False, lpc: bool = False, sdr: bool = False, bands: bool = False,
+                 coherence: bool = False) -> dict:
         """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
         and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
         ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
@@ -570,9 +573,17 @@ class L3AC:
         may then have at most 16384 frames.  ``sdr=True`` adds ``"sdr_db"`` and ``"sdr_valid"``: ``l3ac_amd.sdr`` of the same pairs with
         its default parameters, the SDR of BSS Eval after a fitted distortion filter of 512 taps (section 3.21).  ``bands=True`` adds
         ``"fw_seg_snr_db"``, ``"wss"`` and ``"lsd_db"``: ``l3ac_amd.band_metrics`` of the same pairs at the codec's rate with its default
-        parameters (section 3.22); a recording may then have at most 16384 frames.  Every value equals composing those public calls by
+        parameters (section 3.22); a recording may then have at most 16384 frames.  ``coherence=True`` adds ``"csii"``, ``"csii_high"``,
+        ``"csii_mid"``, ``"csii_low"`` and ``"csii_i3"``: ``l3ac_amd.csii`` of the same pairs at the codec's rate with its default parameters
+        (section 3.23), under the same limit of 16384 frames.  Every value equals composing those public calls by
         hand, bit for bit."""
         scales = _metric_scales(scales)
+        if coherence:  # a rate the defaults do not fit, or a batch too long for a pair, raises before any device work
+            _, coh_frame, coh_hop, _, _ = _check_band_params(self.config.sample_rate, bands=sii_bands(self.config.sample_rate)[:2])
+            longest = audio_data.shape[-1] if self._rate(sample_rate) is None else resample_length(int(sample_rate), self.config.sample_rate,
+                                                                                                  max(audio_data.shape[-1], 1))
+            if _lpc_frames(longest, coh_frame, coh_hop) > 16384:
+                raise ValueError(f"evaluate(coherence=True): {longest} samples are more than the 16384 frames of a pair")
         if bands:  # a rate the defaults do not fit, or a batch too long for a pair, raises before any device work
             _, band_frame, band_hop, _, _ = _check_band_params(self.config.sample_rate, bands=None)
             longest = audio_data.shape[-1] if self._rate(sample_rate) is None else resample_length(int(sample_rate), self.config.sample_rate,
@@ -634,6 +645,10 @@ class L3AC:
         if bands:
             bm = _band_metrics(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
             out.update({"fw_seg_snr_db": bm["fw_seg_snr_db"], "wss": bm["wss"], "lsd_db": bm["lsd_db"]})
+        if coherence:
+            cs = _csii(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
+            out.update({"csii": cs["csii"], "csii_high": cs["csii_high"], "csii_mid": cs["csii_mid"], "csii_low": cs["csii_low"],
+                        "csii_i3": cs["i3"]})
         tokens = info["lengths"]
         seconds = torch.tensor(lens, dtype=torch.float64) / self.config.sample_rate
         out["tokens"] = tokens

@@ -202,6 +202,11 @@ SIGNATURES = {
     "l3ac_band_metrics_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32, _I32]),
     "l3ac_band_metrics": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _I32, C.c_double, _I32, C.c_double,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_sii_bands": (_I64, [_P, _I64]),
+    "l3ac_coherence_scratch_bytes": (_I64, [_I32, _I64, _I32, _I32, _I32]),
+    "l3ac_coherence": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_csii": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64,
+                            _P]),
     "l3ac_profile_begin": (C.c_int, []),
     "l3ac_profile_end": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
 }

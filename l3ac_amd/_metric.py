@@ -32,8 +32,8 @@ def host_table(fn: str, dtype: torch.dtype, *args) -> torch.Tensor:
 
 
 # (device, "basis", n_fft) / (device, "mel", sample_rate, n_fft, n_mels) / (device, "stoi_basis") / (device, "dct", n_mels, n_coeffs) /
-# (device, "lpc_window", frame) / (device, "bands_twiddles", n_fft) / (device, "band_weights", sample_rate, n_fft, centres, widths) -> device
-# copy of the table; every metric module's tables live here
+# (device, "lpc_window", frame) / (device, "bands_twiddles", n_fft) / (device, "band_weights", sample_rate, n_fft, centres, widths) /
+# (device, "sii_importance", importances...) -> device copy of the table; every metric module's tables live here
 tables = {}
 
 

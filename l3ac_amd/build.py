@@ -58,6 +58,7 @@ SOURCES = [
     "kernels/lpc.hip",
     "kernels/sdr.hip",
     "kernels/bands.hip",
+    "kernels/coherence.hip",
 ]
 
 

@@ -10,7 +10,8 @@
 //                       (double)x[j] (double)w[j], then log2(n_fft) passes of n_fft / 2 butterflies with a barrier between them.  Every
 //                       output is one fixed expression tree: which thread takes which butterfly changes no bit.  Element i lives at
 //                       i ^ (i & 32 ? 31 : 0): the 32 lanes of an LDS read group then meet 32 different 8-byte banks in every pass (the
-//                       passes with a half-span below 32 would otherwise put lanes l and l + 16 on one bank).
+//                       passes with a half-span below 32 would otherwise put lanes l and l + 16 on one bank).  The network lives in
+//                       fft_f64.hpp, which coherence.hip shares.
 //     bins              k < n_fft / 2: P = re re + im im, A = sqrt(P) (correctly rounded), into the arrays' upper halves, which the bins
 //                       at and above Nyquist have left; the first side of a pair moves to a third array.
 //     sums              the team's first wave: S = sum A as 64 interleaved partials folded with fold64; lane i the band sums of band i,
@@ -27,6 +28,7 @@
 // values.
 //
 // Contraction is off for this whole file: every product and sum rounds on its own, in the order DESIGN.md states.
+#include "fft_f64.hpp"
 #include "metric_common.hpp"
 
 #include <algorithm>
@@ -86,8 +88,6 @@ int bands_geom(int32_t frame, int32_t hop, int32_t n_fft, int32_t bands, BandsGe
 int64_t frames_of(int64_t samples, const BandsGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
 
 __device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }  // (NaN stays NaN)
-
-__device__ __forceinline__ int swz(int i) { return i ^ ((i & 32) ? 31 : 0); }
 
 struct BandsIo {
     const float* ref;
@@ -186,26 +186,8 @@ __global__ __launch_bounds__(BD_THREADS) void bands_frame_kernel(BandsIo io, Ban
         const int64_t row = (int64_t)b * f_max + t0 + k;
         for (int side = 0; side < sides; ++side) {
             const float* x = (side ? xs1 : xs0) + (active ? k : 0) * p.pitch;
-            for (int i = tl; i < nf; i += ts) {
-                const int r = swz((int)(__brev((unsigned)i) >> (32 - p.log2n)));
-                zre[r] = i < n_frame ? (double)x[i] * (double)win[i] : 0.0;
-                zim[r] = 0.0;
-            }
-            __syncthreads();
-            for (int s = 1; s <= p.log2n; ++s) {
-                const int hf = 1 << (s - 1), tstep = nf >> s;
-                for (int q = tl; q < (nf >> 1); q += ts) {
-                    const int j = q & (hf - 1);
-                    const int ia = ((q >> (s - 1)) << s) | j;
-                    const int sa = swz(ia), sb = swz(ia + hf);
-                    const double wr = io.tw[2 * j * tstep], wi = io.tw[2 * j * tstep + 1];
-                    const double ar = zre[sa], ai = zim[sa], br = zre[sb], bi = zim[sb];
-                    const double tr = wr * br - wi * bi, ti = wr * bi + wi * br;
-                    zre[sa] = ar + tr, zim[sa] = ai + ti;
-                    zre[sb] = ar - tr, zim[sb] = ai - ti;
-                }
-                __syncthreads();
-            }
+            fft_f64_load(zre, zim, x, win, n_frame, nf, p.log2n, tl, ts);
+            fft_f64_passes(zre, zim, io.tw, nf, p.log2n, tl, ts);
             double* pw = (pair && side == 0) ? q0 : zre + h;
             double* mg = (pair && side == 0) ? q0 + h : zim + h;
             for (int kk = tl; kk < h; kk += ts) {  // (the elements below h stay below h under swz: h is below 32 or a multiple of 32)
