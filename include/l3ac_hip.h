@@ -492,6 +492,73 @@ int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, d
 int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
                     const int32_t* samples, const double* gain, int64_t gain_stride, void* stream);
 
+/* ---- IIR filtering: scipy.signal.sosfilt one-shot and streaming, Butterworth designs -----------------------------
+ * A cascade of 1 <= sections <= 8 second-order sections filters MONO clips, in fp64 throughout (the fp32 samples convert exactly).  `sos`
+ * is a HOST array [sections][5] = b0 b1 b2 a1 a2 (a0 = 1: the caller has divided by it).  One sample through one section is one
+ * transposed-direct-form-II step, y = b0 x + s1; s1 = b1 x - a1 y + s2; s2 = b2 x - a2 y, each product rounded before its sum (no
+ * contraction): scipy's order.  The sections run in cascade; every clip starts from rest at its sample 0.  Every coefficient must be
+ * finite and every section inside the stability triangle, |a2| < 1 and |a1| < 1 + a2 (first-order sections, b2 = a2 = 0, and the
+ * identity 1 0 0 0 0 included).
+ * The recursion runs in parallel over time in segments of SEG = l3ac_sosfilt_segment samples (256) anchored at sample 0, and SEG is
+ * part of the definition of the bits: (A) every segment is filtered from a zero state and keeps its end state (2 sections values: s1, s2
+ * of section 0, of section 1, ...); (B) per clip start_{s+1} = M start_s + end_s over the complete segments, where M advances the
+ * cascade's state over SEG samples of zero input; M, the running state and the products are pairs of doubles hi + lo, the row of M
+ * times the state summed in column order, then the end state added; (C) every segment is filtered again from hi(start_s), and that
+ * is y.  M is designed on the device on every call, by the same step in pair arithmetic (coefficients as (c, 0)) on SEG zero samples
+ * from each unit state: no table, no upload, nothing to warm up before a capture.
+ *   l3ac_sosfilt_segment:       HOST only: SEG.
+ *   l3ac_sosfilt_scratch_bytes: the minimum scratch of l3ac_sosfilt, and of l3ac_sosfilt_stream with batch = its descriptors and
+ *                               max_samples = max(fresh_frames, 1); < 0 for batch outside 1..65535, max_samples outside 1..2^31 - 1 or
+ *                               sections outside 1..8.
+ *   l3ac_sosfilt:               audio [batch][audio_stride] fp32 (`samples`: HOST array of batch lengths in 1..max_samples, or NULL) -> out
+ *                               [batch][out_stride], fp64 when out_f64 is non-zero, else fp32 = (float)y; zeros at and after a clip's length
+ *                               up to max_samples.  out must not overlap audio.
+ *   l3ac_sosfilt_matrix:        M of `sos` -> hi, lo: DEVICE buffers [2 sections][2 sections] fp64, row-major (the tests' view of it).
+ *   l3ac_sosfilt_stream_state:  HOST only: doubles per state row, 8 sections; < 0 for sections outside 1..8.
+ *   l3ac_sosfilt_stream:        one push of S live streams.  A stream at position p = s SEG + k carries in its row of a state buffer
+ *                               [streams][state_stride] the start pair of its current segment (hi, then lo), its running true state and
+ *                               its running zero-state state; k is the caller's.  A push continues both recursions of the stream's
+ *                               current segment sample by sample, hands the completed segments' end states to the scan, and saves both
+ *                               running states of the last, partial segment: out[slot][0 : take] = the filtered samples, zeros from there to
+ *                               fresh_frames, and state_out[slot] = the stream's state afterwards (a stream that takes nothing is copied;
+ *                               L3AC_SOS_END leaves the slot at rest: zeros; a descriptor with L3AC_SOS_FRESH starts from rest without
+                               reading its state row, so a slot can be handed to a new stream at any time).  As many outputs as inputs, no latency, nothing to flush.  state_in and
+ *                               state_out are two buffers that must not overlap (a session alternates them; a fresh buffer is zeros);
+ *                               describe idle streams too, so that their state follows.  `desc` is a HOST array with at most one
+ *                               descriptor per stream, handed to the device as kernel arguments.  out may be null when fresh_frames is 0.
+ *                               However a stream is split over pushes and whatever the other streams do, the concatenation of its outputs
+ *                               is l3ac_sosfilt of the whole stream bit for bit.
+ *   l3ac_butter_sos:            HOST only: the bilinear Butterworth low-pass or high-pass of `order` 1..16 with pre-warping, in closed form,
+ *                               K = tan(pi cutoff_hz / sample_rate): out [ceil(order / 2)][6] = b0 b1 b2 a0 a1 a2 with a0 = 1, scipy's
+ *                               layout.  An odd order puts the first-order section first, b = (K, K, 0) / (1 + K) or (1, -1, 0) / (1 + K),
+ *                               a = (1, (K - 1) / (K + 1), 0); pair k = 0 .. order / 2 - 1 follows with q = 2 sin(pi (2 k + 1) / (2 order)),
+ *                               a0 = 1 + q K + K^2, a = (1, 2 (K^2 - 1) / a0, (1 - q K + K^2) / a0), b = (K^2, 2 K^2, K^2) / a0 or
+ *                               (1, -2, 1) / a0.  The size-query protocol of l3ac_stft_basis; < 0 for an order outside 1..16 or a cutoff
+ *                               outside (0, sample_rate / 2).
+ * Every bad argument (sections outside 1..8, a non-finite coefficient, an unstable section, batch 0 or above 65535, a length outside
+ * 1..max_samples, a row stride below max_samples, a null buffer, a scratch below the minimum, a descriptor out of range) is L3AC_EINVAL
+ * before any device work, with a message naming it.  Bit guarantee and calling convention: as the quality metrics above (a clip's
+ * output does not depend on the batch, its row, the strides or the scratch size; no atomics; enqueue only, nothing allocated, no
+ * synchronisation; l3ac_sosfilt is capturable as the first call of a process). */
+typedef struct l3ac_sosfilt_stream_desc {
+    int32_t slot;    /* stream: row of the state buffers, of the new samples and of the output */
+    int32_t k;       /* samples the stream's current segment has had: its position modulo SEG */
+    int32_t take;    /* new samples, from the front of the stream's row of `fresh` */
+    int32_t flags;   /* L3AC_SOS_END: the stream ends with this push, its slot is at rest afterwards; L3AC_SOS_FRESH: the stream begins
+                        with this push (k = 0): nothing of state_in is read, whatever the slot held */
+} l3ac_sosfilt_stream_desc;
+enum { L3AC_SOS_END = 1, L3AC_SOS_FRESH = 2 };
+int32_t l3ac_sosfilt_segment(void);
+int64_t l3ac_sosfilt_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sections);
+int l3ac_sosfilt(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, const double* sos,
+                 int32_t sections, void* out, int64_t out_stride, int32_t out_f64, void* scratch, int64_t scratch_bytes, void* stream);
+int l3ac_sosfilt_matrix(const double* sos, int32_t sections, double* hi, double* lo, void* stream);
+int64_t l3ac_sosfilt_stream_state(int32_t sections);
+int l3ac_sosfilt_stream(const double* state_in, double* state_out, int32_t streams, int64_t state_stride, const float* fresh, int64_t fresh_frames,
+                        int64_t fresh_stride, const double* sos, int32_t sections, const l3ac_sosfilt_stream_desc* desc, int32_t count, void* out,
+                        int64_t out_stride, int32_t out_f64, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t l3ac_butter_sos(int32_t order, double cutoff_hz, double sample_rate, int32_t highpass, double* out, int64_t cap);
+
 /* ---- pitch: YIN F0 tracking and the pairwise F0 metrics (which states every formula) ------------------------------
  * A deterministic YIN tracker (de Cheveigne & Kawahara 2002, steps 1-5) of MONO clips.  Parameters: sample_rate fs, fmin, fmax, window W
  * (-1: tau_max), hop (-1: fs / 100), threshold.  tau_min = floor(fs / fmax), tau_max = ceil(fs / fmin), T = tau_max + 1, span = W + T.

@@ -51,7 +51,8 @@ from .bands import (_check_params as _check_band_params, band_energies, band_met
                     frame_spectrum)
 from .coherence import coherence, csii, csii as _csii, sii_bands
 from .resampling import _resample_bank, resample, resample_length
-from .streaming import StreamDecoder, StreamEncoder, StreamResampler
+from .streaming import StreamDecoder, StreamEncoder, StreamResampler, filter_advance
+from .filtering import StreamFilter, butter_sos, highpass, k_weighting_sos, sosfilt, sosfilt_matrix, sosfilt_segment
 from .wire import (StreamPacker, StreamUnpacker, bits_per_token, frame_header, pack_advance, pack_indices, packed_bytes, parse_frame,
                    unpack_advance, unpack_indices)
 from .config import CONFIG_DIR, L3ACConfig, ModelConfig, list_models, resolve_config_file
@@ -64,7 +65,8 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "normalize_loudness", "loudness_coeffs", "loudness_blocks", "pitch", "pitch_metrics", "pitch_frames", "pitch_lags", "delay",
            "apply_delay", "align", "mfcc", "dtw", "mcd", "dct_table", "lpc", "lpc_metrics", "lpc_frames", "lpc_defaults", "lpc_window",
            "sdr", "correlate", "toeplitz_solve", "frame_spectrum", "band_energies", "band_metrics", "band_weights", "critical_bands",
-           "coherence", "csii", "sii_bands"]
+           "coherence", "csii", "sii_bands", "sosfilt", "sosfilt_segment", "sosfilt_matrix", "butter_sos", "k_weighting_sos", "highpass",
+           "StreamFilter", "stream_filter", "filter_advance"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -746,6 +748,14 @@ def stream_resampler(streams: int, orig_sr: int, target_sr: int) -> StreamResamp
 
     Rates are checked here (``resample_length``'s errors); the state lives on the device of the first push."""
     return StreamResampler(streams, orig_sr, target_sr)
+
+
+def stream_filter(streams: int, sos, dtype: torch.dtype = torch.float32) -> StreamFilter:
+    """A session that runs ``streams`` concurrent live streams through the cascade ``sos`` (``sosfilt``'s (N, 6) rows) packet by packet:
+    ``y, n = flt.push(audio, lengths=None, end=None)`` returns each stream's new samples filtered, as many as it was given.  However
+    a stream is split over pushes, what it emits adds up to ``sosfilt`` of the whole stream, bit for bit (``StreamFilter.push``).  Needs
+    no codec; ``sos`` is checked here (``sosfilt``'s errors); the state lives on the device of the first push."""
+    return StreamFilter(streams, sos, dtype)
 
 
 def get_model(config_name, model_dir=None, synthetic_seed: Optional[int] = None, synthetic_profile: str = "mild") -> L3AC:

@@ -67,6 +67,12 @@ class UnpackStreamDesc(C.Structure):
     _fields_ = [("slot", C.c_int32), ("held", C.c_int32), ("take", C.c_int32), ("count", C.c_int32), ("keep", C.c_int32)]
 
 
+class SosStreamDesc(C.Structure):
+    """l3ac_sosfilt_stream_desc: one stream's share of one filtering push (include/l3ac_hip.h)."""
+    _fields_ = [("slot", C.c_int32), ("k", C.c_int32), ("take", C.c_int32), ("flags", C.c_int32)]
+    END, FRESH = 1, 2  # L3AC_SOS_END, L3AC_SOS_FRESH
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -163,6 +169,14 @@ SIGNATURES = {
     "l3ac_loudness": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _P, _I64, _P]),
     "l3ac_loudness_gain": (C.c_int, [_P, _I32, C.c_double, C.c_double, _P, _P]),
     "l3ac_apply_gain": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _I64, _P]),
+    "l3ac_sosfilt_segment": (_I32, []),
+    "l3ac_sosfilt_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_sosfilt": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), C.POINTER(C.c_double), _I32, _P, _I64, _I32, _P, _I64, _P]),
+    "l3ac_sosfilt_matrix": (C.c_int, [C.POINTER(C.c_double), _I32, _P, _P, _P]),
+    "l3ac_sosfilt_stream_state": (_I64, [_I32]),
+    "l3ac_sosfilt_stream": (C.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, C.POINTER(C.c_double), _I32, C.POINTER(SosStreamDesc), _I32, _P, _I64, _I32, _P,
+                                      _I64, _P]),
+    "l3ac_butter_sos": (_I64, [_I32, C.c_double, C.c_double, _I32, _P, _I64]),
     "l3ac_pitch_lags": (C.c_int, [_I32, C.c_double, C.c_double, _I32, _I32, C.POINTER(_I32)]),
     "l3ac_pitch_frames": (_I64, [_I64, _I32, C.c_double, C.c_double, _I32, _I32]),
     "l3ac_pitch_scratch_bytes": (_I64, [_I32, _I64, _I32, C.c_double, C.c_double, _I32, _I32]),

@@ -8,7 +8,7 @@
 //   2. loudness_scan_kernel         one thread per clip walks the steps in order: start_{s+1} = M start_s + end_s, M the 4x4 matrix that
 //                                   advances the cascade's state over one step of zero input (the response is linear: from a true start
 //                                   state the end state is the zero-input part M start plus the zero-state part); start_s replaces end_s.
-//                                   M and the running state are pairs of doubles (hi + lo), see Pair below
+//                                   M and the running state are pairs of doubles (hi + lo), see pair.hpp
 //   3. loudness_pass_kernel<true>   every (clip, step) reruns the recursion from its true start state and sums y^2 in sample order: e_s
 //   4. loudness_gate_kernel         one workgroup per clip: z_j, l_j, the absolute and the relative gate, L, the sample peak, the counts
 // The coefficients and M are designed on the host in fp64 (loudness_coeffs) and travel as kernel arguments: no device table, nothing to
@@ -28,6 +28,8 @@
 #include <limits>
 
 #pragma clang fp contract(off)
+
+#include "pair.hpp"
 
 namespace {
 
@@ -62,26 +64,7 @@ __host__ __device__ __forceinline__ T biquad(const T (&c)[5], T x, T& s1, T& s2)
     return y;
 }
 
-// An unevaluated sum hi + lo of two doubles (Dekker / Knuth): what the scan carries.  M's entries are some 1e4 times its eigenvalues (a
-// near-double pole: n p^n), so a matrix rounded to fp64, or a product summed in fp64, moves the decay of a free tail by 1e-9 a step;
-// with pairs the scan adds nothing to what the passes' own fp64 recursion costs.  The one fma here is spelled out.
-struct Pair {
-    double hi, lo;
-};
-__device__ __forceinline__ Pair fast_two_sum(double a, double b) {  // |a| >= |b|
-    const double s = a + b;
-    return {s, b - (s - a)};
-}
-__device__ __forceinline__ Pair pair_add(Pair a, Pair b) {
-    const double s = a.hi + b.hi, bb = s - a.hi;
-    const double err = (a.hi - (s - bb)) + (b.hi - bb);
-    return fast_two_sum(s, err + (a.lo + b.lo));
-}
-__device__ __forceinline__ Pair pair_mul(Pair a, Pair b) {
-    const double p = a.hi * b.hi;
-    const double err = fma(a.hi, b.hi, -p);
-    return fast_two_sum(p, err + (a.hi * b.lo + a.lo * b.hi));
-}
+// (Pair, pair_add, pair_mul: what the scan carries, pair.hpp)
 
 int loud_geom(int32_t batch, int64_t max_samples, int32_t sample_rate, int64_t* s_max, LoudScratch* sc) {
     LD_REQUIRE_RATE(sample_rate);

@@ -1,4 +1,4 @@
-// What the metric families share (metrics, stoi, loudness, pitch, align, mcd, lpc, sdr, bands .hip): the fixed-order workgroup
+// What the metric families share (metrics, stoi, loudness, iir, pitch, align, mcd, lpc, sdr, bands, coherence .hip): the fixed-order workgroup
 // reductions and the LDS sort on the device, and on the host the scratch layout, the checks of a batch of clips and the staging of their lengths.  Each
 // family's arithmetic, geometry and parameter checks are its own.
 #pragma once

@@ -13,6 +13,8 @@ the ragged calls, so its bits are those of ``encode_audio`` / ``decode_audio`` o
 
 Last, streaming sample-rate conversion: its geometry (``resample_advance``) and ``StreamResampler``
 (``l3ac_amd.stream_resampler``), whose carried state is each stream's last inputs; one launch of csrc/kernels/resample_stream.hip per push.
+The bookkeeping of streaming IIR filtering (``filter_advance``) is here too; its session, ``StreamFilter``, is in
+filtering.py.
 """
 from __future__ import annotations
 
@@ -173,9 +175,41 @@ def resample_advance(state: ResampleState, new_frames: int, end: bool, geo: Resa
     return push, (ResampleState() if end else ResampleState(keep, now, done + count))
 
 
+# ---- 1c. streaming IIR filtering: bookkeeping ------------------------------------------------------------------
+FILTER_SEGMENT = 256  # l3ac_sosfilt_segment(): the segment of the parallel recursion, anchored at a stream's first sample
+
+
+class FilterState(NamedTuple):
+    """What one filtered stream is between pushes on the host: ``k`` samples into its current segment (its position modulo the segment;
+    the start pair of that segment and both running states are on the device) and ``seen`` samples received so far."""
+    k: int = 0
+    seen: int = 0
+
+
+class FilterPush(NamedTuple):
+    """One stream's share of one push, l3ac_sosfilt_stream_desc's fields: the stream's current segment has had ``k`` samples, the push
+    brings ``take`` more and emits ``count`` = ``take`` outputs; ``end``: the slot is at rest afterwards; ``fresh``: the stream has
+    received nothing yet, so the push starts from rest and reads nothing of what the slot holds on the device (``reset`` relies on it)."""
+    k: int
+    take: int
+    count: int
+    end: bool
+    fresh: bool
+
+
+def filter_advance(state: FilterState, new_frames: int, end: bool, segment: int = FILTER_SEGMENT) -> Tuple[FilterPush, FilterState]:
+    """One push of ``new_frames`` samples onto a stream in ``state``: as many outputs as inputs, at once (no latency, nothing to flush).
+    ``end`` only returns the slot to rest."""
+    if new_frames < 0:
+        raise ValueError(f"{new_frames} new frames")
+    k, seen = state
+    push = FilterPush(k, new_frames, new_frames, bool(end), seen == 0)
+    return push, (FilterState() if end else FilterState((k + new_frames) % segment, seen + new_frames))
+
+
 # ---- 2. sessions -------------------------------------------------------------------------------------------------------------
 class _Streams:
-    """What all five sessions share: the per-stream host state and the parsing of a push's ``lengths`` / ``end``."""
+    """What all six sessions share: the per-stream host state and the parsing of a push's ``lengths`` / ``end``."""
     _fresh = None  # the state of a fresh stream
 
     def __init__(self, streams: int):
@@ -208,7 +242,7 @@ class _Streams:
 
 
 class _CarrySession(_Streams):
-    """The sessions of one launch per push (StreamResampler, wire.StreamPacker / StreamUnpacker): the carried state lives on the device of
+    """The sessions of one launch per push (StreamResampler, wire.StreamPacker / StreamUnpacker, filtering.StreamFilter): the carried state lives on the device of
     the first push, in two buffers read and written alternately.  A push cannot be captured: ``_phase`` names the host value that moves."""
     _what = "session"
     _elements = "elements"
