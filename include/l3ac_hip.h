@@ -203,7 +203,9 @@ int l3ac_fsq_copy_ceiling_at(const float* x, int64_t n, float* q_feature, int32_
  * queries [n][dim] (= tanh(latents)), codebook [k][dim] (= indices_to_codes(arange(k)), vq/fsq.py:80-81);
  * out_idx[i] = argmin_k ||q_i - c_k||^2, lowest k on exact ties.  dim <= 8.
  * The result is DEFINED by dist = sum_d (q_d - c_d)^2 accumulated with fmaf in dimension order and strict '<' over
- * increasing k; from 5 120 queries on the candidates are first screened on the fp32 matrix cores and then decided by
+ * increasing k.  A query for which no code compares below +inf (a NaN or Inf coordinate, or distances that all overflow)
+ * gets index 0, as torch.argmin does on an all-NaN or all-inf row: out_idx is always an index into the codebook.
+ * From 5 120 queries on the candidates are first screened on the fp32 matrix cores and then decided by
  * exactly that arithmetic (kernels/fsq.hip, "screened form"), so every size returns the same bits.
  * `scratch` is a caller-owned device buffer of at least l3ac_vq_argmin_scratch_bytes(n, k, form) bytes (partial minima of
  * the codebook slices, code norms, the list of queries that need the full direct-form search): the call allocates nothing

@@ -715,8 +715,11 @@ __global__ __launch_bounds__(THREADS) void vq_argmin_combine_kernel(const float*
                 best = take ? d : best;
                 best_p = take ? pp : best_p;
             }
-            // (no slice below +inf: the first slice's entry, as a chain over the slices would have kept)
-            out_idx[list ? (int64_t)list[qi] : qi] = part_idx[(int64_t)(best_p == 0x7fffffff ? 0 : best_p) * n + qi];
+            // (no slice below +inf: the first slice's entry, as a chain over the slices would have kept.)  A slice in which no code
+            // compared below +inf (NaN or +inf distances throughout) still carries the search kernels' "none yet" marker: such a
+            // query gets index 0, what torch.argmin returns on an all-NaN or all-inf row — the result is always a codebook index.
+            const int32_t won = part_idx[(int64_t)(best_p == 0x7fffffff ? 0 : best_p) * n + qi];
+            out_idx[list ? (int64_t)list[qi] : qi] = won == 0x7fffffff ? 0 : won;
         }
         __syncthreads();
     }
