@@ -4,8 +4,9 @@
 //
 //   bands_frame_kernel  grid (groups of frames, batch), 4 waves.  A group is G consecutive frames of one clip; G and the waves of a frame
 //                       are functions of n_fft alone: one wave a frame (four frames in step) and G = 16 up to n_fft = 256, the whole
-//                       workgroup a frame above, with G = 8 up to 1024, 4 at 2048 and 2 at 4096.  The group's samples of the one or two
-//                       sides and the window go to LDS once, as in lpc.hip.  Then per frame and side, all fp64:
+//                       workgroup a frame above, with G = 8 up to 1024, 4 at 2048 and 2 at 4096 (SpectralGeom of spectral_frames.hpp,
+//                       which coherence.hip shares).  The group's samples of the one or two sides and the window go to LDS once
+//                       (stage_group of frame_groups.hpp, which owns the framing).  Then per frame and side, all fp64:
 //     FFT               complex radix-2 decimation in time on two LDS arrays (re, im) of n_fft doubles: the bit-reversed load of xw[j] =
 //                       (double)x[j] (double)w[j], then log2(n_fft) passes of n_fft / 2 butterflies with a barrier between them.  Every
 //                       output is one fixed expression tree: which thread takes which butterfly changes no bit.  Element i lives at
@@ -15,12 +16,12 @@
 //     bins              k < n_fft / 2: P = re re + im im, A = sqrt(P) (correctly rounded), into the arrays' upper halves, which the bins
 //                       at and above Nyquist have left; the first side of a pair moves to a third array.
 //     sums              the team's first wave: S = sum A as 64 interleaved partials folded with fold64; lane i the band sums of band i,
-//                       one chain over the band's run of non-zero weights (found once per workgroup)
+//                       one chain over the band's run of non-zero weights (band_runs, once per workgroup)
 //     measures          pairs only, the first wave: lane i the terms of band i (the peak walks are bounded by `bands`), lane 0 the sums
 //                       in band order; the log-spectral distance as 64 interleaved partials
-//   bands_pair_kernel   one workgroup per pair: the frames' WSS values sorted in LDS (lds_sort of metric_common.hpp) and the lowest k
-//                       summed in that order, the two other measures summed in frame order; as lpc_pair_kernel, which caps a pair at
-//                       16384 frames.
+//   bands_pair_kernel   one workgroup per pair, built on the pair pieces of metric_common.hpp like lpc_pair_kernel: the frames' WSS values
+//                       sorted in LDS and the lowest k summed in that order (lds_trimmed_mean), the two other measures summed in frame
+//                       order (lds_ordered_mean); the LDS caps a pair at 16384 frames.
 //
 // A frame's values depend on its own N samples a side only — never on the batch, the clip's row, the row stride, the scratch size, the
 // frame's place in its group or what lies after the clip's length, which is never read; no atomics.  Non-finite samples make unspecified
@@ -29,7 +30,7 @@
 //
 // Contraction is off for this whole file: every product and sum rounds on its own, in the order DESIGN.md states.
 #include "fft_f64.hpp"
-#include "metric_common.hpp"
+#include "spectral_frames.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,9 +40,6 @@
 namespace {
 
 constexpr int BD_THREADS = 256;
-constexpr int BD_MIN_FRAME = 2, BD_MAX_FRAME = 2048;
-constexpr int BD_MIN_FFT = 16, BD_MAX_FFT = 4096;
-constexpr int BD_MIN_BANDS = 2, BD_MAX_BANDS = 64;
 constexpr int BD_MIN_RATE = 8000, BD_MAX_RATE = 192000;
 constexpr int BD_TABLE_BANDS = 25;
 // a team's small rows of doubles in LDS: the two sums S, then rows of 64: the band sums M and E of each side, E clamped and in dB of each
@@ -49,45 +47,23 @@ constexpr int BD_TABLE_BANDS = 25;
 enum { SM_S = 0, SM_M = 8, SM_P = SM_M + 128, SM_EC = SM_P + 128, SM_DB = SM_EC + 128, SM_T0 = SM_DB + 128, SM_T1 = SM_T0 + 64, SM_T2 = SM_T1 + 64,
        SM_T3 = SM_T2 + 64, BD_SMALL = SM_T3 + 64 };
 
-constexpr int BQ_THREADS = 1024;
-constexpr int BQ_MAX_FRAMES = 16384;  // one workgroup sorts a pair's frames in LDS
 constexpr double BD_FLOOR = 1e-10;    // of a band energy and of a bin's power before the logarithm
 constexpr double BD_ERR_FLOOR = 0x1p-52;
 
-struct BandsGeom {
-    int n, hop, n_fft, log2n, h, bands;  // frame length, hop, transform length and its logarithm, bins kept, bands (0: none)
-    int wpf, g, pitch, lds_bytes;        // waves of a frame, frames per group, min(hop, n), dynamic LDS of the launch
+struct BandsGeom : SpectralGeom {
+    int bands, lds_bytes;  // bands (0: none), dynamic LDS of the launch
 };
 
-constexpr int bands_lds(int n_fft, int wpf, int g, int pitch, int n) {
-    return (4 / wpf) * (3 * n_fft + BD_SMALL) * 8 + 128 * 4 + (n + 2 * ((g - 1) * pitch + n)) * 4;
-}
-// the largest launches: a hop at or above the frame, the longest frame the transform takes
-constexpr int BD_LDS_MAX = std::max(std::max(bands_lds(4096, 4, 2, 2048, 2048), bands_lds(2048, 4, 4, 2048, 2048)),
-                                    std::max(bands_lds(1024, 4, 8, 1024, 1024), bands_lds(256, 1, 16, 256, 256)));
-static_assert(BD_LDS_MAX <= 160 * 1024, "a group lives in one workgroup's LDS");
-static_assert(BQ_MAX_FRAMES * 8 + BQ_MAX_FRAMES + 256 <= 160 * 1024, "a pair's values and flags live in one workgroup's LDS");
+// a team's small rows beside its three arrays, then the bands' runs [64][2] int32
+constexpr int BD_LDS_MAX = spectral_lds_max<BD_SMALL, 128 * 4>();
 
 int bands_geom(int32_t frame, int32_t hop, int32_t n_fft, int32_t bands, BandsGeom* p) {
-    L3AC_REQUIRE(frame >= BD_MIN_FRAME && frame <= BD_MAX_FRAME, "bands: frame %d outside %d..%d", frame, BD_MIN_FRAME, BD_MAX_FRAME);
-    L3AC_REQUIRE(hop >= 1, "bands: hop %d must be at least 1", hop);
-    L3AC_REQUIRE(n_fft >= BD_MIN_FFT && n_fft <= BD_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "bands: n_fft %d is not a power of two in %d..%d", n_fft,
-                 BD_MIN_FFT, BD_MAX_FFT);
-    L3AC_REQUIRE(n_fft >= frame, "bands: n_fft %d is below the frame %d", n_fft, frame);
-    L3AC_REQUIRE(bands == 0 || (bands >= BD_MIN_BANDS && bands <= BD_MAX_BANDS), "bands: %d bands outside %d..%d", bands, BD_MIN_BANDS, BD_MAX_BANDS);
-    p->n = frame, p->hop = hop, p->n_fft = n_fft, p->h = n_fft / 2, p->bands = bands;
-    p->log2n = 0;
-    while ((1 << p->log2n) < n_fft) ++p->log2n;
-    p->wpf = n_fft <= 256 ? 1 : 4;
-    p->g = n_fft <= 256 ? 16 : (n_fft <= 1024 ? 8 : (n_fft == 2048 ? 4 : 2));
-    p->pitch = std::min(hop, frame);
-    p->lds_bytes = bands_lds(n_fft, p->wpf, p->g, p->pitch, frame);
+    L3AC_TRY(spectral_geom("bands", frame, hop, n_fft, p));
+    L3AC_REQUIRE(bands == 0 || (bands >= SP_MIN_BANDS && bands <= SP_MAX_BANDS), "bands: %d bands outside %d..%d", bands, SP_MIN_BANDS, SP_MAX_BANDS);
+    p->bands = bands;
+    p->lds_bytes = spectral_lds(n_fft, p->wpf, p->g, p->pitch, frame, BD_SMALL, 128 * 4);
     return L3AC_OK;
 }
-
-int64_t frames_of(int64_t samples, const BandsGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
-
-__device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }  // (NaN stays NaN)
 
 struct BandsIo {
     const float* ref;
@@ -124,7 +100,6 @@ __global__ __launch_bounds__(BD_THREADS) void bands_frame_kernel(BandsIo io, Ban
     const int n_frame = p.n, nf = p.n_fft, h = p.h, nb = p.bands;
     const bool pair = io.est != nullptr;
     const int sides = pair ? 2 : 1;
-    const int span_max = (p.g - 1) * p.pitch + n_frame;
     double* zre = lds_raw + team * (3 * nf + BD_SMALL);  // [nf] each; after the bins the upper halves hold P and A
     double* zim = zre + nf;
     double* q0 = zim + nf;  // P [h], A [h] of a pair's first side
@@ -132,16 +107,15 @@ __global__ __launch_bounds__(BD_THREADS) void bands_frame_kernel(BandsIo io, Ban
     int* runs = reinterpret_cast<int*>(lds_raw + teams * (3 * nf + BD_SMALL));  // [64][2]: band i's non-zero weights are [lo, hi)
     float* win = reinterpret_cast<float*>(runs + 128);                           // [n]
     float* xs0 = win + n_frame;                                                  // [span_max]: frame k of the group starts at k pitch
-    float* xs1 = xs0 + span_max;
-    const int64_t n = io.lens ? io.lens[b] : io.max_samples;
-    const int64_t frames = n < n_frame ? 0 : 1 + (n - n_frame) / p.hop;
+    float* xs1 = xs0 + p.span_max();
+    const int64_t frames = p.frames(io.lens ? io.lens[b] : io.max_samples);
     const int64_t f_max = io.f_max;
     const double nan = __builtin_nan("");
     if (io.frames_out && blockIdx.x == 0 && tid == 0) io.frames_out[b] = (int)frames;
 
     const int64_t t0 = (int64_t)blockIdx.x * p.g;
     if (t0 >= f_max) return;  // (the one workgroup of a batch without any frame)
-    const int cnt = t0 >= frames ? 0 : (frames - t0 < p.g ? (int)(frames - t0) : p.g);
+    const int cnt = p.count(t0, frames);
     // rows at and after the clip's own frames
     for (int k = cnt + team; k < p.g && t0 + k < f_max; k += teams) {
         const int64_t row = (int64_t)b * f_max + t0 + k;
@@ -161,23 +135,9 @@ __global__ __launch_bounds__(BD_THREADS) void bands_frame_kernel(BandsIo io, Ban
     }
     if (cnt == 0) return;  // (the whole workgroup)
 
-    // stage: sample k of the stage is sample src(k) of the clip; every one lies inside a frame below `frames`
-    const int floats = (cnt - 1) * p.pitch + n_frame;
-    const float* x0 = io.ref + (int64_t)b * io.ref_stride;
-    const float* x1 = pair ? io.est + (int64_t)b * io.est_stride : nullptr;
-    for (int k = tid; k < floats; k += BD_THREADS) {
-        const int64_t src = p.hop <= n_frame ? t0 * p.hop + k : (t0 + k / n_frame) * p.hop + k % n_frame;
-        xs0[k] = x0[src];
-        if (pair) xs1[k] = x1[src];
-    }
-    for (int i = tid; i < n_frame; i += BD_THREADS) win[i] = io.window ? io.window[i] : 1.f;
-    if (io.weights && tid < nb) {  // the band's run of non-zero weights
-        const double* wrow = io.weights + (int64_t)tid * h;
-        int lo = h, hi = 0;
-        for (int k = 0; k < h; ++k)
-            if (wrow[k] != 0.0) lo = k < lo ? k : lo, hi = k + 1;
-        runs[2 * tid] = lo < hi ? lo : 0, runs[2 * tid + 1] = hi;
-    }
+    stage_group<BD_THREADS>(p, t0, cnt, io.ref + (int64_t)b * io.ref_stride, pair ? io.est + (int64_t)b * io.est_stride : nullptr, xs0, xs1);
+    stage_window<BD_THREADS>(n_frame, io.window, win);
+    band_runs(io.weights, nb, h, runs);
     __syncthreads();
 
     for (int k0 = 0; k0 < cnt; k0 += teams) {  // the teams in step: every barrier below is reached by all of them
@@ -302,54 +262,28 @@ __global__ __launch_bounds__(BD_THREADS) void bands_frame_kernel(BandsIo io, Ban
 }
 
 // ---- the pair: one workgroup per pair -----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BQ_THREADS) void bands_pair_kernel(const double* __restrict__ vals, const int* __restrict__ flags, int64_t f_max,
+__global__ __launch_bounds__(PAIR_THREADS) void bands_pair_kernel(const double* __restrict__ vals, const int* __restrict__ flags, int64_t f_max,
                                                               int64_t max_samples, const int* __restrict__ lens, BandsGeom p, double trim,
                                                               double* __restrict__ out, int* __restrict__ counts) {
-    __shared__ double buf[BQ_MAX_FRAMES];
-    __shared__ unsigned char fl[BQ_MAX_FRAMES];
-    __shared__ int wave_count[BQ_THREADS / 64];
+    __shared__ double buf[PAIR_MAX_FRAMES];
+    __shared__ unsigned char fl[PAIR_MAX_FRAMES];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t n = lens ? lens[b] : max_samples;
-    int64_t f64 = n < p.n ? 0 : 1 + (n - p.n) / p.hop;
-    f64 = f64 < f_max ? f64 : f_max;
-    const int frames = (int)(f64 < BQ_MAX_FRAMES ? f64 : BQ_MAX_FRAMES);  // (the host checked it; the clamp bounds every index)
-    const int64_t row0 = (int64_t)b * f_max;
-    int n_pad = 1;
-    while (n_pad < frames) n_pad <<= 1;
+    const int frames = pair_frames(p.frames(lens ? lens[b] : max_samples), f_max);
+    const double* row = vals + (int64_t)b * f_max * 3;
     int v_snr = 0;
-    for (int f = tid; f < frames; f += BQ_THREADS) {
-        const int g = flags[row0 + f];
+    for (int f = tid; f < frames; f += PAIR_THREADS) {
+        const int g = flags[(int64_t)b * f_max + f];
         fl[f] = (unsigned char)g;
         v_snr += g & 1;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v_snr += __shfl_xor(v_snr, o, 64);
-    if ((tid & 63) == 0) wave_count[tid >> 6] = v_snr;
-    __syncthreads();
-    v_snr = 0;
-    for (int w = 0; w < BQ_THREADS / 64; ++w) v_snr += wave_count[w];
+    v_snr = block_count<PAIR_THREADS>(v_snr);
     const int keep = (int)floor(trim * (double)frames + 0.5);
-    const double nan = __builtin_nan("");
-    for (int f = tid; f < n_pad; f += BQ_THREADS) buf[f] = f < frames ? vals[(row0 + f) * 3 + 1] : __builtin_huge_val();
-    __syncthreads();
-    lds_sort<BQ_THREADS>(buf, n_pad);
-    if (tid == 0) {
-        double s = 0.0;
-        for (int f = 0; f < keep; ++f) s = s + buf[f];
-        out[(int64_t)b * 3 + 1] = (frames == 0 || keep == 0) ? nan : s / (double)keep;
-    }
-    __syncthreads();
+    const double wss = lds_trimmed_mean<PAIR_THREADS>(buf, frames, keep, [&](int f) { return row[f * 3 + 1]; }, [](int) { return true; });
+    if (tid == 0) out[(int64_t)b * 3 + 1] = (frames == 0 || keep == 0) ? __builtin_nan("") : wss;
     for (int m = 0; m < 3; m += 2) {  // the fwSegSNR over its counted frames, the LSD over all, in frame order
-        for (int f = tid; f < frames; f += BQ_THREADS) buf[f] = (m == 2 || (fl[f] & 1)) ? vals[(row0 + f) * 3 + m] : 0.0;
-        __syncthreads();
-        if (tid == 0) {
-            const int v = m == 0 ? v_snr : frames;
-            double s = 0.0;
-            for (int f = 0; f < frames; ++f)
-                if (m == 2 || (fl[f] & 1)) s = s + buf[f];
-            out[(int64_t)b * 3 + m] = v == 0 ? nan : s / (double)v;
-        }
-        __syncthreads();
+        const double mean = lds_ordered_mean<PAIR_THREADS>(buf, frames, m == 0 ? v_snr : frames, [&](int f) { return row[f * 3 + m]; },
+                                                         [&](int f) { return m == 2 || (fl[f] & 1); });
+        if (tid == 0) out[(int64_t)b * 3 + m] = mean;
     }
     if (tid == 0) counts[(int64_t)b * 2] = frames, counts[(int64_t)b * 2 + 1] = v_snr;
 }
@@ -363,23 +297,16 @@ int configure_frame_kernel() {
     return L3AC_OK;
 }
 
-struct BandsScratch {  // byte offsets into the caller's scratch, after the clips' lengths
-    int64_t vals, flags, need;
-};
-
 // the parameters checked, then (metrics) the frames' three values [batch][F][3] fp64 and the frames' flags [batch][F] int32
 int bands_scratch(const char* what, bool metrics, int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft, int32_t bands,
-                  BandsGeom* p, BandsScratch* sc) {
+                  BandsGeom* p, PairScratch* sc) {
     L3AC_TRY(bands_geom(frame, hop, n_fft, bands, p));
     L3AC_TRY(check_clip_batch(what, batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, *p);
     ScratchPlan plan(batch);
     sc->vals = sc->flags = 0;
     if (metrics) {
-        L3AC_REQUIRE(bands != 0, "%s: %d bands outside %d..%d", what, bands, BD_MIN_BANDS, BD_MAX_BANDS);
-        L3AC_REQUIRE(f_max <= BQ_MAX_FRAMES, "%s: %lld frames are more than the %d of a pair", what, (long long)f_max, BQ_MAX_FRAMES);
-        sc->vals = plan.take((int64_t)batch * f_max * 24);
-        sc->flags = plan.take((int64_t)batch * f_max * 4);
+        L3AC_REQUIRE(bands != 0, "%s: %d bands outside %d..%d", what, bands, SP_MIN_BANDS, SP_MAX_BANDS);
+        L3AC_TRY(pair_frames_plan(what, batch, p->frames(max_samples), 24, plan, &sc->vals, &sc->flags));
     }
     sc->need = plan.bytes;
     return L3AC_OK;
@@ -408,15 +335,14 @@ const double BD_WIDTH[BD_TABLE_BANDS] = {70.0,    70.0,    70.0,    70.0,    70.
 extern "C" {
 
 int32_t l3ac_bands_default_fft(int32_t frame) {
-    L3AC_REQUIRE(frame >= BD_MIN_FRAME && frame <= BD_MAX_FRAME, "bands: frame %d outside %d..%d", frame, BD_MIN_FRAME, BD_MAX_FRAME);
-    int32_t n_fft = BD_MIN_FFT;
+    L3AC_REQUIRE(frame >= SP_MIN_FRAME && frame <= SP_MAX_FRAME, "bands: frame %d outside %d..%d", frame, SP_MIN_FRAME, SP_MAX_FRAME);
+    int32_t n_fft = SP_MIN_FFT;
     while (n_fft < 2 * frame) n_fft <<= 1;
     return n_fft;
 }
 
 int64_t l3ac_bands_twiddles(int32_t n_fft, double* out, int64_t cap) {
-    L3AC_REQUIRE(n_fft >= BD_MIN_FFT && n_fft <= BD_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "bands: n_fft %d is not a power of two in %d..%d", n_fft,
-                 BD_MIN_FFT, BD_MAX_FFT);
+    L3AC_TRY(check_n_fft("bands", n_fft));
     if (!out || cap < n_fft) return n_fft;
     const long double two_pi = 2.0L * acosl(-1.0L);
     const int half = n_fft / 2, quarter = n_fft / 4, eighth = n_fft / 8;
@@ -445,9 +371,8 @@ int64_t l3ac_band_weights(int32_t sample_rate, int32_t n_fft, int32_t bands, con
                           int64_t cap) {
     L3AC_REQUIRE(sample_rate >= BD_MIN_RATE && sample_rate <= BD_MAX_RATE, "band_weights: sample_rate %d outside %d..%d", sample_rate, BD_MIN_RATE,
                  BD_MAX_RATE);
-    L3AC_REQUIRE(n_fft >= BD_MIN_FFT && n_fft <= BD_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "band_weights: n_fft %d is not a power of two in %d..%d",
-                 n_fft, BD_MIN_FFT, BD_MAX_FFT);
-    L3AC_REQUIRE(bands >= BD_MIN_BANDS && bands <= BD_MAX_BANDS, "band_weights: %d bands outside %d..%d", bands, BD_MIN_BANDS, BD_MAX_BANDS);
+    L3AC_TRY(check_n_fft("band_weights", n_fft));
+    L3AC_REQUIRE(bands >= SP_MIN_BANDS && bands <= SP_MAX_BANDS, "band_weights: %d bands outside %d..%d", bands, SP_MIN_BANDS, SP_MAX_BANDS);
     L3AC_REQUIRE(centre_hz && bandwidth_hz, "band_weights: null centre_hz or bandwidth_hz");
     const int h = n_fft / 2;
     const double nyquist = sample_rate / 2.0;
@@ -479,7 +404,7 @@ int64_t l3ac_band_weights(int32_t sample_rate, int32_t n_fft, int32_t bands, con
 
 int64_t l3ac_frame_spectrum_scratch_bytes(int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft) {
     BandsGeom p;
-    BandsScratch sc;
+    PairScratch sc;
     L3AC_TRY(bands_scratch("frame_spectrum", false, batch, max_samples, frame, hop, n_fft, 0, &p, &sc));
     return sc.need;  // the clips' lengths
 }
@@ -489,9 +414,9 @@ int l3ac_frame_spectrum(const float* audio, int64_t audio_stride, int32_t batch,
                         double* magnitude_sum, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     BandsGeom p;
-    BandsScratch sc;
+    PairScratch sc;
     L3AC_TRY(bands_scratch("frame_spectrum", false, batch, max_samples, frame, hop, n_fft, 0, &p, &sc));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     L3AC_REQUIRE(audio, "frame_spectrum: null audio");
     L3AC_REQUIRE(twiddles, "frame_spectrum: null twiddles");
     L3AC_REQUIRE(f_max == 0 || spectrum, "frame_spectrum: null output buffer");
@@ -511,10 +436,10 @@ int l3ac_band_energies(const float* audio, int64_t audio_stride, int32_t batch, 
                        double* magnitude, int32_t* frames, void* scratch, int64_t scratch_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     BandsGeom p;
-    BandsScratch sc;
-    L3AC_REQUIRE(bands != 0, "band_energies: %d bands outside %d..%d", bands, BD_MIN_BANDS, BD_MAX_BANDS);
+    PairScratch sc;
+    L3AC_REQUIRE(bands != 0, "band_energies: %d bands outside %d..%d", bands, SP_MIN_BANDS, SP_MAX_BANDS);
     L3AC_TRY(bands_scratch("band_energies", false, batch, max_samples, frame, hop, n_fft, bands, &p, &sc));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     L3AC_REQUIRE(audio, "band_energies: null audio");
     L3AC_REQUIRE(twiddles && weights, "band_energies: null twiddles or weights");
     L3AC_REQUIRE(f_max == 0 || (power && magnitude), "band_energies: null output buffer");
@@ -531,7 +456,7 @@ int l3ac_band_energies(const float* audio, int64_t audio_stride, int32_t batch, 
 
 int64_t l3ac_band_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft, int32_t bands) {
     BandsGeom p;
-    BandsScratch sc;
+    PairScratch sc;
     L3AC_TRY(bands_scratch("band_metrics", true, batch, max_samples, frame, hop, n_fft, bands, &p, &sc));
     return sc.need;
 }
@@ -543,7 +468,7 @@ int l3ac_band_metrics(const float* ref, int64_t ref_stride, const float* est, in
                       int64_t scratch_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     BandsGeom p;
-    BandsScratch sc;
+    PairScratch sc;
     L3AC_TRY(bands_scratch("band_metrics", true, batch, max_samples, frame, hop, n_fft, bands, &p, &sc));
     L3AC_REQUIRE(std::isfinite(gamma), "band_metrics: gamma %g must be finite", gamma);
     L3AC_REQUIRE(normalize == 0 || normalize == 1, "band_metrics: normalize %d must be 0 or 1", normalize);
@@ -556,7 +481,7 @@ int l3ac_band_metrics(const float* ref, int64_t ref_stride, const float* est, in
     L3AC_TRY(check_clip_lengths("band_metrics", samples, batch, max_samples));
     int* lens;
     L3AC_TRY(stage_clip_lengths(s, "band_metrics", "band_metrics", samples, batch, scratch, scratch_bytes, sc.need, &lens));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     char* base = static_cast<char*>(scratch);
     double* vals = frame_values ? frame_values : reinterpret_cast<double*>(base + sc.vals);
     int* flags = reinterpret_cast<int*>(base + sc.flags);
@@ -566,7 +491,7 @@ int l3ac_band_metrics(const float* ref, int64_t ref_stride, const float* est, in
     io.mag_sum = magnitude_sum, io.band_p = band_power, io.band_m = band_magnitude, io.peaks = peaks, io.vals = vals, io.flags = flags;
     L3AC_TRY(launch_frames(s, io, p, batch, false));
     ProfScope prof(s, "bands_pair_kernel", 0.0, 28.0 * batch * (double)f_max);
-    hipLaunchKernelGGL(bands_pair_kernel, dim3((unsigned)batch), dim3(BQ_THREADS), 0, s, vals, flags, f_max, max_samples, lens, p, trim, out, counts);
+    hipLaunchKernelGGL(bands_pair_kernel, dim3((unsigned)batch), dim3(PAIR_THREADS), 0, s, vals, flags, f_max, max_samples, lens, p, trim, out, counts);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }

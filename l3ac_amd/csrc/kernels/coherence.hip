@@ -7,14 +7,14 @@
 //   coh_class_kernel   one wave a pair: S = sum_t E_t (frame t in partial t mod 64, fold64), M = S / F, the class of every frame (0: E >= M,
 //                      1: E >= 0.1 M, 2: E >= 0.001 M, 3: below; all 3 where S == 0) and the four counts.
 //   coh_chunk_kernel   grid (chunks, batch), 4 waves.  A chunk is four groups of G consecutive frames of one pair, with G and the waves of a
-//                      frame the functions of n_fft that bands.hip uses (one wave a frame and G = 16 up to n_fft = 256, the workgroup a
-//                      frame above, G = 8 up to 1024, 4 at 2048, 2 at 4096).  A group's samples of both sides and the window go to LDS
-//                      once.  Per frame the two transforms of fft_f64.hpp, then per kept bin k the four products Pxx = Xr Xr + Xi Xi, Pyy,
+//                      frame those of SpectralGeom (spectral_frames.hpp, shared with bands.hip: one wave a frame and G = 16 up to n_fft =
+//                      256, the workgroup a frame above, G = 8 up to 1024, 4 at 2048, 2 at 4096).  A group's samples of both sides go to
+//                      LDS once (stage_group of frame_groups.hpp, which owns the framing), the window once per chunk.  Per frame the two transforms of fft_f64.hpp, then per kept bin k the four products Pxx = Xr Xr + Xi Xi, Pyy,
 //                      Cre = Xr Yr + Xi Yi, Cim = Xi Yr - Xr Yi through LDS; the thread that owns bin k adds them to its registers of the
 //                      frame's class, the frames of the chunk in order.  The chunk's sums [4 classes][4][h] go to the scratch.
 //   coh_finish_kernel  one workgroup a pair: the chunks in order; "all frames" = ((c0 + c1) + (c2 + c3)); g = min((Cre^2 + Cim^2) / (Sxx Syy),
 //                      1), 0 where Sxx Syy == 0; with band weights, lane i the chains N_i, D_i of band i over its run of non-zero weights
-//                      and T_i, thread 0 the class value in band order; then I3 and the intelligibility.
+//                      (band_runs) and T_i, thread 0 the class value in band order; then I3 and the intelligibility.
 //
 // A pair's values depend on its own samples only — never on the batch, the pair's row, the row strides, the scratch size, the grid or what
 // lies at or after the clip's length, which is never read; no atomics.  Non-finite samples make unspecified values in their own pair only:
@@ -22,7 +22,7 @@
 //
 // Contraction is off for this whole file: every product and sum rounds on its own, in the order DESIGN.md states.
 #include "fft_f64.hpp"
-#include "metric_common.hpp"
+#include "spectral_frames.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,48 +32,25 @@
 namespace {
 
 constexpr int CO_THREADS = 256;
-constexpr int CO_MIN_FRAME = 2, CO_MAX_FRAME = 2048;
-constexpr int CO_MIN_FFT = 16, CO_MAX_FFT = 4096;
-constexpr int CO_MIN_BANDS = 2, CO_MAX_BANDS = 64;
-constexpr int CO_MAX_FRAMES = 16384;  // of a pair, as band_metrics
 constexpr int CO_GROUPS = 4;          // groups of a chunk
 constexpr int CO_MAX_CHUNK = 64;
 constexpr int CO_CLASSES = 4;
 constexpr int CO_TABLE_BANDS = 21;
 
-struct CohGeom {
-    int n, hop, n_fft, log2n, h;             // frame length, hop, transform length and its logarithm, bins kept
-    int wpf, g, chunk, pitch, bpt, lds_bytes;  // waves of a frame, frames of a group and of a chunk, min(hop, n), bins a thread, dynamic LDS
+struct CohGeom : SpectralGeom {
+    int chunk, bpt, lds_bytes;  // frames of a chunk, bins a thread, dynamic LDS of the launch
 };
 
-// per team three arrays of n_fft doubles (re, im, and the first side's bins; after the products they hold the four products), the chunk's
-// classes, the window and the group's samples of both sides
-constexpr int coh_lds(int n_fft, int wpf, int g, int pitch, int n) {
-    return (4 / wpf) * 3 * n_fft * 8 + CO_MAX_CHUNK * 4 + (n + 2 * ((g - 1) * pitch + n)) * 4;
-}
-constexpr int CO_LDS_MAX = std::max(std::max(coh_lds(4096, 4, 2, 2048, 2048), coh_lds(2048, 4, 4, 2048, 2048)),
-                                    std::max(coh_lds(1024, 4, 8, 1024, 1024), coh_lds(256, 1, 16, 256, 256)));
-static_assert(CO_LDS_MAX <= 160 * 1024, "a group lives in one workgroup's LDS");
+// a team's three arrays hold re, im and the first side's bins, after the products the four products; then the chunk's classes
+constexpr int CO_LDS_MAX = spectral_lds_max<0, CO_MAX_CHUNK * 4>();
 
 int coh_geom(const char* what, int32_t frame, int32_t hop, int32_t n_fft, CohGeom* p) {
-    L3AC_REQUIRE(frame >= CO_MIN_FRAME && frame <= CO_MAX_FRAME, "%s: frame %d outside %d..%d", what, frame, CO_MIN_FRAME, CO_MAX_FRAME);
-    L3AC_REQUIRE(hop >= 1, "%s: hop %d must be at least 1", what, hop);
-    L3AC_REQUIRE(n_fft >= CO_MIN_FFT && n_fft <= CO_MAX_FFT && (n_fft & (n_fft - 1)) == 0, "%s: n_fft %d is not a power of two in %d..%d", what,
-                 n_fft, CO_MIN_FFT, CO_MAX_FFT);
-    L3AC_REQUIRE(n_fft >= frame, "%s: n_fft %d is below the frame %d", what, n_fft, frame);
-    p->n = frame, p->hop = hop, p->n_fft = n_fft, p->h = n_fft / 2;
-    p->log2n = 0;
-    while ((1 << p->log2n) < n_fft) ++p->log2n;
-    p->wpf = n_fft <= 256 ? 1 : 4;
-    p->g = n_fft <= 256 ? 16 : (n_fft <= 1024 ? 8 : (n_fft == 2048 ? 4 : 2));
+    L3AC_TRY(spectral_geom(what, frame, hop, n_fft, p));
     p->chunk = CO_GROUPS * p->g;
-    p->pitch = std::min(hop, frame);
     p->bpt = std::max(p->h / CO_THREADS, 1);
-    p->lds_bytes = coh_lds(n_fft, p->wpf, p->g, p->pitch, frame);
+    p->lds_bytes = spectral_lds(n_fft, p->wpf, p->g, p->pitch, frame, 0, CO_MAX_CHUNK * 4);
     return L3AC_OK;
 }
-
-int64_t frames_of(int64_t samples, const CohGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
 
 struct CohIo {
     const float* ref;
@@ -104,8 +81,7 @@ struct CohIo {
 };
 
 __device__ __forceinline__ int64_t clip_frames(const CohIo& io, const CohGeom& p, int b) {
-    const int64_t n = io.lens ? io.lens[b] : io.max_samples;
-    const int64_t f = n < p.n ? 0 : 1 + (n - p.n) / p.hop;
+    const int64_t f = p.frames(io.lens ? io.lens[b] : io.max_samples);
     return f < io.f_max ? f : io.f_max;  // (the host checked the lengths; the clamp bounds every index)
 }
 
@@ -168,14 +144,13 @@ __global__ __launch_bounds__(CO_THREADS) void coh_chunk_kernel(CohIo io, CohGeom
     const int ts = 64 * p.wpf, teams = CO_THREADS / ts, team = tid / ts, tl = tid % ts;
     const int b = blockIdx.y;
     const int n_frame = p.n, nf = p.n_fft, h = p.h;
-    const int span_max = (p.g - 1) * p.pitch + n_frame;
     double* zre = lds_raw + team * 3 * nf;  // [nf] each
     double* zim = zre + nf;
     double* q0 = zim + nf;                                          // the first side's re [h], im [h]
     int* cls_s = reinterpret_cast<int*>(lds_raw + teams * 3 * nf);  // [CO_MAX_CHUNK]
     float* win = reinterpret_cast<float*>(cls_s + CO_MAX_CHUNK);    // [n]
     float* xs0 = win + n_frame;                                     // [span_max]: frame k of the group starts at k pitch
-    float* xs1 = xs0 + span_max;
+    float* xs1 = xs0 + p.span_max();
     const int64_t frames = clip_frames(io, p, b);
     const int64_t c0 = (int64_t)blockIdx.x * p.chunk;
     if (c0 >= frames) return;  // (the whole workgroup: the finish reads the clip's own chunks only)
@@ -190,22 +165,14 @@ __global__ __launch_bounds__(CO_THREADS) void coh_chunk_kernel(CohIo io, CohGeom
         const int c = c0 + i < frames ? io.cls[(int64_t)b * io.f_max + c0 + i] : 3;
         cls_s[i] = c < 0 ? 0 : (c > 3 ? 3 : c);
     }
-    for (int i = tid; i < n_frame; i += CO_THREADS) win[i] = io.window ? io.window[i] : 1.f;
-    const float* x0 = io.ref + (int64_t)b * io.ref_stride;
-    const float* x1 = io.est + (int64_t)b * io.est_stride;
+    stage_window<CO_THREADS>(n_frame, io.window, win);
 
     for (int sg = 0; sg < CO_GROUPS; ++sg) {
         const int64_t t0 = c0 + (int64_t)sg * p.g;
         if (t0 >= frames) break;  // (uniform)
-        const int cnt = frames - t0 < p.g ? (int)(frames - t0) : p.g;
-        // stage: sample k of the stage is sample src(k) of the clip; every one lies inside a frame below `frames`.  (The previous group's
-        // frames are done with the stage: their last step ended with a barrier.)
-        const int floats = (cnt - 1) * p.pitch + n_frame;
-        for (int k = tid; k < floats; k += CO_THREADS) {
-            const int64_t src = p.hop <= n_frame ? t0 * p.hop + k : (t0 + k / n_frame) * p.hop + k % n_frame;
-            xs0[k] = x0[src];
-            xs1[k] = x1[src];
-        }
+        const int cnt = p.count(t0, frames);
+        // (the previous group's frames are done with the stage: their last step ended with a barrier)
+        stage_group<CO_THREADS>(p, t0, cnt, io.ref + (int64_t)b * io.ref_stride, io.est + (int64_t)b * io.est_stride, xs0, xs1);
         __syncthreads();
 
         for (int k0 = 0; k0 < cnt; k0 += teams) {  // the teams in step: every barrier below is reached by all of them
@@ -266,9 +233,9 @@ __global__ __launch_bounds__(CO_THREADS) void coh_chunk_kernel(CohIo io, CohGeom
 
 // ---- the pair: one workgroup a pair ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CO_THREADS) void coh_finish_kernel(CohIo io, CohGeom p) {
-    __shared__ double sig[CO_MAX_FFT / 2], dis[CO_MAX_FFT / 2];  // g Syy and (1 - g) Syy of the row in hand
-    __shared__ double tv[CO_MAX_BANDS], vals[4];
-    __shared__ int runs[2 * CO_MAX_BANDS];  // band i's non-zero weights are [lo, hi)
+    __shared__ double sig[SP_MAX_FFT / 2], dis[SP_MAX_FFT / 2];  // g Syy and (1 - g) Syy of the row in hand
+    __shared__ double tv[SP_MAX_BANDS], vals[4];
+    __shared__ int runs[2 * SP_MAX_BANDS];  // band i's non-zero weights are [lo, hi)
     const int b = blockIdx.x, tid = threadIdx.x, h = p.h, nb = io.bands;
     const int* counts = io.counts + (int64_t)b * 5;
     const int frames = counts[0];
@@ -282,13 +249,7 @@ __global__ __launch_bounds__(CO_THREADS) void coh_finish_kernel(CohIo io, CohGeo
             for (int c = 0; c < chunks; ++c) s = s + part[((int64_t)c * 16 + cv) * h + k];
             sums[cv * h + k] = s;
         }
-    if (io.weights && tid < nb) {
-        const double* wrow = io.weights + (int64_t)tid * h;
-        int lo = h, hi = 0;
-        for (int k = 0; k < h; ++k)
-            if (wrow[k] != 0.0) lo = k < lo ? k : lo, hi = k + 1;
-        runs[2 * tid] = lo < hi ? lo : 0, runs[2 * tid + 1] = hi;
-    }
+    band_runs(io.weights, nb, h, runs);
     __syncthreads();
 
     for (int r = 0; r < 5; ++r) {  // the classes 0..3, then all frames
@@ -320,9 +281,7 @@ __global__ __launch_bounds__(CO_THREADS) void coh_finish_kernel(CohIo io, CohGeo
             } else if (d_i == 0.0 && n_i > 0.0) {
                 t_i = 1.0;
             } else {
-                const double db = 10.0 * log10(n_i / d_i);
-                const double cl = db < -15.0 ? -15.0 : (db > 15.0 ? 15.0 : db);  // (NaN stays NaN)
-                t_i = (cl + 15.0) / 30.0;
+                t_i = (clamp_to(10.0 * log10(n_i / d_i), -15.0, 15.0) + 15.0) / 30.0;
             }
             tv[tid] = t_i;
             const int64_t at = ((int64_t)b * 4 + row) * nb + tid;
@@ -367,9 +326,9 @@ struct CohScratch {  // byte offsets into the caller's scratch, after the clips'
 int coh_scratch(const char* what, int32_t batch, int64_t max_samples, int32_t frame, int32_t hop, int32_t n_fft, CohGeom* p, CohScratch* sc) {
     L3AC_TRY(coh_geom(what, frame, hop, n_fft, p));
     L3AC_TRY(check_clip_batch(what, batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, *p);
-    L3AC_REQUIRE(f_max <= CO_MAX_FRAMES, "%s: %lld frames are more than the %d of a pair", what, (long long)f_max, CO_MAX_FRAMES);
+    const int64_t f_max = p->frames(max_samples);
     ScratchPlan plan(batch);
+    L3AC_TRY(pair_frames_plan(what, batch, f_max, 0, plan, nullptr, nullptr));  // (the check alone: a pair's frames are capped as band_metrics')
     sc->energy = plan.take((int64_t)batch * f_max * 8);
     sc->cls = plan.take((int64_t)batch * f_max * 4);
     sc->counts = plan.take((int64_t)batch * 5 * 4);
@@ -404,7 +363,7 @@ int coh_run(const char* what, hipStream_t s, CohIo io, const float* ref, int64_t
     char* base = static_cast<char*>(scratch);
     io.ref = ref, io.ref_stride = ref_stride, io.est = est, io.est_stride = est_stride, io.max_samples = max_samples, io.lens = lens;
     io.window = window, io.tw = twiddles;
-    io.f_max = frames_of(max_samples, p), io.chunks_max = ceil_div64(io.f_max, p.chunk);
+    io.f_max = p.frames(max_samples),io.chunks_max = ceil_div64(io.f_max, p.chunk);
     io.energy = frame_energy ? frame_energy : reinterpret_cast<double*>(base + sc.energy);
     io.cls = reinterpret_cast<int*>(base + sc.cls), io.cls_out = frame_class;
     io.counts = counts ? counts : reinterpret_cast<int*>(base + sc.counts);
@@ -476,7 +435,7 @@ int l3ac_csii(const float* ref, int64_t ref_stride, const float* est, int64_t es
               int32_t frame, int32_t hop, int32_t n_fft, const float* window, const double* twiddles, const double* weights,
               const double* importance, int32_t bands, double* out, int32_t* counts, double* band_signal, double* band_distortion,
               double* band_value, double* sums, void* scratch, int64_t scratch_bytes, void* stream) {
-    L3AC_REQUIRE(bands >= CO_MIN_BANDS && bands <= CO_MAX_BANDS, "csii: %d bands outside %d..%d", bands, CO_MIN_BANDS, CO_MAX_BANDS);
+    L3AC_REQUIRE(bands >= SP_MIN_BANDS && bands <= SP_MAX_BANDS, "csii: %d bands outside %d..%d", bands, SP_MIN_BANDS, SP_MAX_BANDS);
     L3AC_REQUIRE(weights && importance, "csii: null weights or importance");
     L3AC_REQUIRE(out, "csii: null output buffer");
     CohIo io{};

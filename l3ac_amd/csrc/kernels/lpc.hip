@@ -4,8 +4,9 @@
 //
 //   lpc_frame_kernel   grid (groups of frames, batch), 4 waves.  A group is G consecutive frames of one clip (G = 16, halved until the group
 //                      fits the LDS budget; a function of the parameters alone).  The group's samples of the one or two sides, (G - 1)
-//                      min(hop, N) + N floats a side, and the window go to LDS once; the frames overlap, so every sample is read from
-//                      memory once per group and up to N / hop times from LDS.  Then one wave per frame, the four waves in step:
+//                      min(hop, N) + N floats a side, and the window go to LDS once (stage_group of frame_groups.hpp, which owns the
+//                      framing); the frames overlap, so every sample is read from memory once per group and up to N / hop times from
+//                      LDS.  Then one wave per frame, the four waves in step:
 //     autocorrelation  fp64 from here on.  xw[i] = (double)x[i] (double)w[i], exact.  For each lag k lane l sums the terms i = l, l + 64, ...
 //                      of xw[i] xw[i + k] in increasing i from +0, and the 64 partial sums are folded s[l] += s[l + h], h = 32 .. 1: the
 //                      reads of a term are consecutive across the lanes (no bank conflict), the order depends on N and k alone.  The
@@ -14,17 +15,19 @@
 //                      and every E_m > 0
 //     forms            pairs only.  Lane i: the inner sums sum_j r[|i - j|] a[j] of the three quadratic forms in increasing j; lane 0: the
 //                      outer sums in increasing i, the cepstra of 1 / A, the four values and their clamps
-//   lpc_pair_kernel    one workgroup per pair: the frames' values of a measure go to LDS (+inf where the frame is not valid on both
-//                      sides, and up to the next power of two), a bitonic sort orders them (lds_sort of metric_common.hpp) — the sorted
-//                      sequence of a set of numbers does not depend on how it was reached — and lane 0 sums the first k = floor(trim V + 0.5) in that order.  16384 fp64
-//                      values are 128 KiB of the CU's 160 KiB of LDS: this is what caps a pair at 16384 frames.  The segmental SNR is
-//                      the sum of the counted frames' values in frame order over their count.
+//   lpc_pair_kernel    one workgroup per pair, built on the pair pieces of metric_common.hpp: the frames' values of a measure go to LDS
+//                      (+inf where the frame is not valid on both sides, and up to the next power of two), a bitonic sort orders them —
+//                      the sorted sequence of a set of numbers does not depend on how it was reached — and lane 0 sums the first
+//                      k = floor(trim V + 0.5) in that order (lds_trimmed_mean).  16384 fp64 values are 128 KiB of the CU's 160 KiB of
+//                      LDS: this is what caps a pair at 16384 frames.  The segmental SNR is the sum of the counted frames' values in
+//                      frame order over their count (lds_ordered_mean).
 //
 // A frame's values depend on its own N samples a side only — never on the batch, the clip's row, the row stride, the scratch size, the
 // frame's place in its group or what lies after the clip's length, which is never read; no atomics.  Non-finite samples make unspecified
 // values in the frames that read them, and in their pair's means; every index is bounded by the parameters, whatever the values.
 //
 // Contraction is off for this whole file: every product and sum rounds on its own, in the order DESIGN.md states.
+#include "frame_groups.hpp"
 #include "metric_common.hpp"
 
 #include <algorithm>
@@ -46,17 +49,11 @@ constexpr int LP_LDS_TARGET = 48 << 10;  // a group of more than one frame stays
 enum { W_R0 = 0, W_R1, W_A0, W_A1, W_K0, W_K1, W_C0, W_C1, W_TMP, W_Q0, W_Q1, W_Q2, W_ROWS };
 constexpr int LP_WORK = W_ROWS * LP_ROW;  // doubles per wave
 constexpr int LP_LDS_MAX = LP_WAVES * LP_WORK * 8 + 3 * LP_MAX_FRAME * 4;  // one frame of 8192 samples, two sides and the window
-
-constexpr int LQ_THREADS = 1024;
-constexpr int LQ_MAX_FRAMES = 16384;  // one workgroup sorts a pair's frames in LDS
 constexpr double LP_DB = 4.342944819032518;  // 10 / ln 10
-
-static_assert(LQ_MAX_FRAMES * 8 + LQ_MAX_FRAMES + 256 <= 160 * 1024, "a pair's values and flags live in one workgroup's LDS");
 static_assert(LP_LDS_MAX <= 160 * 1024, "a group lives in one workgroup's LDS");
 
-struct LpcGeom {
-    int n, hop, p;               // frame length, hop, order
-    int g, pitch, lds_bytes;     // frames per group, min(hop, n), dynamic LDS of the launch
+struct LpcGeom : FrameGroups {
+    int p, lds_bytes;  // order, dynamic LDS of the launch
 };
 
 struct LpcClamp {
@@ -70,17 +67,12 @@ int lpc_geom(int32_t fs, int32_t order, int32_t frame, int32_t hop, LpcGeom* p) 
     L3AC_REQUIRE(order >= 1 && order <= LP_MAX_ORDER, "lpc: order %d outside 1..%d", order, LP_MAX_ORDER);
     L3AC_REQUIRE(frame > order && frame <= LP_MAX_FRAME, "lpc: frame %d outside order + 1 = %d .. %d", frame, order + 1, LP_MAX_FRAME);
     L3AC_REQUIRE(hop >= 1, "lpc: hop %d must be at least 1", hop);
-    p->n = frame, p->hop = hop, p->p = order;
-    p->pitch = std::min(hop, frame);
+    p->set_frames(frame, hop), p->p = order;
     p->g = LP_FRAMES;
     while (p->g > 1 && lds_need(p->g, p->pitch, frame) > LP_LDS_TARGET) p->g >>= 1;
     p->lds_bytes = lds_need(p->g, p->pitch, frame);
     return L3AC_OK;
 }
-
-int64_t frames_of(int64_t samples, const LpcGeom& p) { return samples < p.n ? 0 : 1 + (samples - p.n) / p.hop; }
-
-__device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }  // (NaN stays NaN)
 
 // Levinson-Durbin on r[0..p] -> a[0..p], refl[0..p-1], *err = E_p; false where r[0] > 0 or an E_m > 0 fails (the arrays are then partial)
 __device__ bool levinson(const double* r, double* a, double* tmp, double* refl, int p, double* err) {
@@ -123,20 +115,18 @@ __global__ __launch_bounds__(LP_THREADS) void lpc_frame_kernel(const float* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
     const int n_frame = p.n, order = p.p, rows = order + 1;
-    const int span_max = (p.g - 1) * p.pitch + n_frame;
     double* work = lds_raw + wave * LP_WORK;
     float* win = reinterpret_cast<float*>(lds_raw + LP_WAVES * LP_WORK);  // [n]
     float* xs0 = win + n_frame;                                           // [span_max]: frame k of the group starts at k pitch
-    float* xs1 = xs0 + span_max;
+    float* xs1 = xs0 + p.span_max();
     const bool pair = est != nullptr;
-    const int64_t n = lens ? lens[b] : max_samples;
-    const int64_t frames = n < n_frame ? 0 : 1 + (n - n_frame) / p.hop;
+    const int64_t frames = p.frames(lens ? lens[b] : max_samples);
     const double nan = __builtin_nan("");
     if (frames_out && blockIdx.x == 0 && tid == 0) frames_out[b] = (int)frames;
 
     const int64_t t0 = (int64_t)blockIdx.x * p.g;
     if (t0 >= f_max) return;  // (the one workgroup of a batch without any frame)
-    const int cnt = t0 >= frames ? 0 : (frames - t0 < p.g ? (int)(frames - t0) : p.g);
+    const int cnt = p.count(t0, frames);
     // rows at and after the clip's own frames
     for (int k = cnt + wave; k < p.g && t0 + k < f_max; k += LP_WAVES) {
         const int64_t row = (int64_t)b * f_max + t0 + k;
@@ -152,16 +142,8 @@ __global__ __launch_bounds__(LP_THREADS) void lpc_frame_kernel(const float* __re
     }
     if (cnt == 0) return;  // (the whole workgroup)
 
-    // stage: sample k of the stage is sample src(k) of the clip; every one lies inside a frame below `frames`
-    const int floats = (cnt - 1) * p.pitch + n_frame;
-    const float* x0 = ref + (int64_t)b * ref_stride;
-    const float* x1 = pair ? est + (int64_t)b * est_stride : nullptr;
-    for (int k = tid; k < floats; k += LP_THREADS) {
-        const int64_t src = p.hop <= n_frame ? t0 * p.hop + k : (t0 + k / n_frame) * p.hop + k % n_frame;
-        xs0[k] = x0[src];
-        if (pair) xs1[k] = x1[src];
-    }
-    for (int i = tid; i < n_frame; i += LP_THREADS) win[i] = window ? window[i] : 1.f;
+    stage_group<LP_THREADS>(p, t0, cnt, ref + (int64_t)b * ref_stride, pair ? est + (int64_t)b * est_stride : nullptr, xs0, xs1);
+    stage_window<LP_THREADS>(n_frame, window, win);
     __syncthreads();
 
     for (int k0 = 0; k0 < cnt; k0 += LP_WAVES) {  // the four waves in step: every barrier below is reached by all of them
@@ -260,52 +242,31 @@ __global__ __launch_bounds__(LP_THREADS) void lpc_frame_kernel(const float* __re
 }
 
 // ---- the pair: one workgroup per pair -----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(LQ_THREADS) void lpc_pair_kernel(const double* __restrict__ vals, const int* __restrict__ flags, int64_t f_max,
+__global__ __launch_bounds__(PAIR_THREADS) void lpc_pair_kernel(const double* __restrict__ vals, const int* __restrict__ flags, int64_t f_max,
                                                             int64_t max_samples, const int* __restrict__ lens, LpcGeom p, LpcClamp cl,
                                                             double* __restrict__ out, int* __restrict__ counts) {
-    __shared__ double buf[LQ_MAX_FRAMES];
-    __shared__ unsigned char fl[LQ_MAX_FRAMES];
-    __shared__ int wave_count[2][LQ_THREADS / 64];
+    __shared__ double buf[PAIR_MAX_FRAMES];
+    __shared__ unsigned char fl[PAIR_MAX_FRAMES];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t n = lens ? lens[b] : max_samples;
-    int64_t f64 = n < p.n ? 0 : 1 + (n - p.n) / p.hop;
-    f64 = f64 < f_max ? f64 : f_max;
-    const int frames = (int)(f64 < LQ_MAX_FRAMES ? f64 : LQ_MAX_FRAMES);  // (the host checked it; the clamp bounds every index)
-    const int64_t row0 = (int64_t)b * f_max;
-    int n_pad = 1;
-    while (n_pad < frames) n_pad <<= 1;
-    int v_lpc = 0, v_snr = 0;
-    for (int f = tid; f < frames; f += LQ_THREADS) {
-        const int g = flags[row0 + f];
+    const int frames = pair_frames(p.frames(lens ? lens[b] : max_samples), f_max);
+    const double* row = vals + (int64_t)b * f_max * 4;
+    int both = 0;  // the frames valid on both sides in the low half, the frames counted for the segmental SNR in the high half: 16384 at most each
+    for (int f = tid; f < frames; f += PAIR_THREADS) {
+        const int g = flags[(int64_t)b * f_max + f];
         fl[f] = (unsigned char)g;
-        v_lpc += g & 1, v_snr += (g >> 1) & 1;
+        both += (g & 1) + ((g & 2) << 15);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v_lpc += __shfl_xor(v_lpc, o, 64), v_snr += __shfl_xor(v_snr, o, 64);
-    if ((tid & 63) == 0) wave_count[0][tid >> 6] = v_lpc, wave_count[1][tid >> 6] = v_snr;
-    __syncthreads();
-    v_lpc = 0, v_snr = 0;
-    for (int w = 0; w < LQ_THREADS / 64; ++w) v_lpc += wave_count[0][w], v_snr += wave_count[1][w];
+    both = block_count<PAIR_THREADS>(both);
+    const int v_lpc = both & 0xffff, v_snr = both >> 16;
     const int keep = (int)floor(cl.trim * (double)v_lpc + 0.5);
     const double nan = __builtin_nan("");
-    for (int m = 0; m < 3; ++m) {
-        for (int f = tid; f < n_pad; f += LQ_THREADS) buf[f] = (f < frames && (fl[f] & 1)) ? vals[(row0 + f) * 4 + m] : __builtin_huge_val();
-        __syncthreads();
-        lds_sort<LQ_THREADS>(buf, n_pad);
-        if (tid == 0) {
-            double s = 0.0;
-            for (int f = 0; f < keep; ++f) s = s + buf[f];
-            out[(int64_t)b * 4 + m] = (v_lpc == 0 || keep == 0) ? nan : s / (double)keep;
-        }
-        __syncthreads();
+    for (int m = 0; m < 3; ++m) {  // the three envelope measures over the frames valid on both sides
+        const double mean = lds_trimmed_mean<PAIR_THREADS>(buf, frames, keep, [&](int f) { return row[f * 4 + m]; }, [&](int f) { return fl[f] & 1; });
+        if (tid == 0) out[(int64_t)b * 4 + m] = (v_lpc == 0 || keep == 0) ? nan : mean;
     }
-    for (int f = tid; f < frames; f += LQ_THREADS) buf[f] = (fl[f] & 2) ? vals[(row0 + f) * 4 + 3] : 0.0;
-    __syncthreads();
+    const double snr = lds_ordered_mean<PAIR_THREADS>(buf, frames, v_snr, [&](int f) { return row[f * 4 + 3]; }, [&](int f) { return fl[f] & 2; });
     if (tid == 0) {
-        double s = 0.0;
-        for (int f = 0; f < frames; ++f)
-            if (fl[f] & 2) s = s + buf[f];
-        out[(int64_t)b * 4 + 3] = v_snr == 0 ? nan : s / (double)v_snr;
+        out[(int64_t)b * 4 + 3] = snr;
         counts[(int64_t)b * 3] = frames, counts[(int64_t)b * 3 + 1] = v_lpc, counts[(int64_t)b * 3 + 2] = v_snr;
     }
 }
@@ -319,20 +280,13 @@ int configure_frame_kernel() {
     return L3AC_OK;
 }
 
-struct LpcMetricsScratch {  // byte offsets into the caller's scratch, after the clips' lengths
-    int64_t vals, flags, need;
-};
-
 // the parameters checked, then the frames' four values [batch][F][4] fp64 and the frames' flags [batch][F] int32
 int lpc_metrics_scratch(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop, LpcGeom* p,
-                        LpcMetricsScratch* sc) {
+                        PairScratch* sc) {
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, p));
     L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, *p);
-    L3AC_REQUIRE(f_max <= LQ_MAX_FRAMES, "lpc_metrics: %lld frames are more than the %d of a pair", (long long)f_max, LQ_MAX_FRAMES);
     ScratchPlan plan(batch);
-    sc->vals = plan.take((int64_t)batch * f_max * 32);
-    sc->flags = plan.take((int64_t)batch * f_max * 4);
+    L3AC_TRY(pair_frames_plan("lpc_metrics", batch, p->frames(max_samples), 32, plan, &sc->vals, &sc->flags));
     sc->need = plan.bytes;
     return L3AC_OK;
 }
@@ -360,7 +314,7 @@ int64_t l3ac_lpc_frames(int64_t samples, int32_t frame, int32_t hop) {
     L3AC_REQUIRE(samples >= 0, "lpc_frames: samples %lld must not be negative", (long long)samples);
     L3AC_REQUIRE(frame >= 2 && frame <= LP_MAX_FRAME, "lpc_frames: frame %d outside 2..%d", frame, LP_MAX_FRAME);
     L3AC_REQUIRE(hop >= 1, "lpc_frames: hop %d must be at least 1", hop);
-    return samples < frame ? 0 : 1 + (samples - frame) / hop;
+    return uncentred_frames(samples, frame, hop);
 }
 
 int64_t l3ac_lpc_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
@@ -377,7 +331,7 @@ int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t ma
     LpcGeom p;
     L3AC_TRY(lpc_geom(sample_rate, order, frame, hop, &p));
     L3AC_TRY(check_clip_batch("lpc", batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     L3AC_REQUIRE(audio, "lpc: null audio");
     L3AC_REQUIRE(f_max == 0 || (a && reflection && error && autocorr && valid), "lpc: null output buffer");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "lpc: row stride %lld below max_samples %lld", (long long)audio_stride,
@@ -398,7 +352,7 @@ int l3ac_lpc(const float* audio, int64_t audio_stride, int32_t batch, int64_t ma
 
 int64_t l3ac_lpc_metrics_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, int32_t order, int32_t frame, int32_t hop) {
     LpcGeom p;
-    LpcMetricsScratch sc;
+    PairScratch sc;
     L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
     return sc.need;
 }
@@ -409,7 +363,7 @@ int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int
                      int64_t scratch_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     LpcGeom p;
-    LpcMetricsScratch sc;
+    PairScratch sc;
     L3AC_TRY(lpc_metrics_scratch(batch, max_samples, sample_rate, order, frame, hop, &p, &sc));
     L3AC_REQUIRE(trim > 0.0 && trim <= 1.0, "lpc_metrics: trim %g outside (0, 1]", trim);
     L3AC_REQUIRE(llr_max >= 0.0 && std::isfinite(llr_max), "lpc_metrics: llr_max %g must be finite and not negative", llr_max);
@@ -422,7 +376,7 @@ int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int
     L3AC_TRY(check_clip_lengths("lpc_metrics", samples, batch, max_samples));
     int* lens;
     L3AC_TRY(stage_clip_lengths(s, "lpc_metrics", "lpc_metrics", samples, batch, scratch, scratch_bytes, sc.need, &lens));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     char* base = static_cast<char*>(scratch);
     double* vals = frame_values ? frame_values : reinterpret_cast<double*>(base + sc.vals);
     int* flags = reinterpret_cast<int*>(base + sc.flags);
@@ -436,7 +390,7 @@ int l3ac_lpc_metrics(const float* ref, int64_t ref_stride, const float* est, int
         L3AC_LAUNCH_CHECK();
     }
     ProfScope prof(s, "lpc_pair_kernel", 0.0, 36.0 * batch * (double)f_max);
-    hipLaunchKernelGGL(lpc_pair_kernel, dim3((unsigned)batch), dim3(LQ_THREADS), 0, s, vals, flags, f_max, max_samples, lens, p, cl, out, counts);
+    hipLaunchKernelGGL(lpc_pair_kernel, dim3((unsigned)batch), dim3(PAIR_THREADS), 0, s, vals, flags, f_max, max_samples, lens, p, cl, out, counts);
     L3AC_LAUNCH_CHECK();
     return L3AC_OK;
 }

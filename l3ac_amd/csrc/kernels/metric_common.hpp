@@ -1,6 +1,7 @@
 // What the metric families share (metrics, stoi, loudness, iir, pitch, align, mcd, lpc, sdr, bands, coherence .hip): the fixed-order workgroup
-// reductions and the LDS sort on the device, and on the host the scratch layout, the checks of a batch of clips and the staging of their lengths.  Each
-// family's arithmetic, geometry and parameter checks are its own.
+// reductions, the LDS sort and the trimmed and ordered means of the pair kernels (lpc, bands) on the device, and on the host the scratch layout, the checks
+// of a batch of clips, the staging of their lengths and the frame scratch of a pair.  Each family's arithmetic, geometry and parameter checks are its own;
+// the un-centred framing of lpc, bands, coherence and pitch lives in frame_groups.hpp, what the two spectral families share in spectral_frames.hpp.
 #pragma once
 
 #include "../kernels.hpp"
@@ -62,6 +63,60 @@ __device__ __forceinline__ void lds_sort(double* buf, int n_pad) {
     }
 }
 
+__device__ __forceinline__ double clamp_to(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }  // (NaN stays NaN)
+
+// ---- device: the pieces of a pair kernel (lpc.hip, bands.hip): one workgroup of THREADS holds a pair's frames in LDS ---------------------------
+constexpr int PAIR_THREADS = 1024, PAIR_MAX_FRAMES = 16384;  // 16384 fp64 values are 128 KiB of the CU's 160 KiB of LDS
+static_assert(PAIR_MAX_FRAMES * 8 + PAIR_MAX_FRAMES + 256 <= 160 * 1024, "a pair's values and flags live in one workgroup's LDS");
+
+// The pair's frames: the clip's own, at most f_max and PAIR_MAX_FRAMES (the host checked both; the clamp bounds every index).
+__device__ __forceinline__ int pair_frames(int64_t frames, int64_t f_max) { return (int)std::min(std::min(frames, f_max), (int64_t)PAIR_MAX_FRAMES); }
+
+// The integer sum of v over the workgroup; every thread gets it.  Contains barriers, which also publish what the caller wrote to LDS before.
+template <int THREADS>
+__device__ __forceinline__ int block_count(int v) {
+    __shared__ int wave_count[THREADS / 64];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();  // the previous use of wave_count is over
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = 0;
+    for (int w = 0; w < THREADS / 64; ++w) s += wave_count[w];
+    return s;
+}
+
+// The mean of the `keep` smallest of the values value_of(f) of the frames f < frames with kept(f): they go to buf, +inf elsewhere up to the next
+// power of two, lds_sort orders them and thread 0 adds the first `keep` in sorted order from +0 (the other threads' result means nothing).
+// Whether the mean is defined is the caller's rule.  Ends with a barrier.
+template <int THREADS, typename Value, typename Kept>
+__device__ __forceinline__ double lds_trimmed_mean(double* buf, int frames, int keep, Value value_of, Kept kept) {
+    int n_pad = 1;
+    while (n_pad < frames) n_pad <<= 1;
+    for (int f = threadIdx.x; f < n_pad; f += THREADS) buf[f] = (f < frames && kept(f)) ? value_of(f) : __builtin_huge_val();
+    __syncthreads();
+    lds_sort<THREADS>(buf, n_pad);
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int f = 0; f < keep; ++f) s = s + buf[f];
+    __syncthreads();  // buf is read before the next use overwrites it
+    return s / (double)keep;
+}
+
+// The sum of value_of(f) over the frames f < frames with counted(f), added by thread 0 in frame order from +0, over `count`; NaN where count
+// is 0 (the other threads' result means nothing).  Ends with a barrier.
+template <int THREADS, typename Value, typename Counted>
+__device__ __forceinline__ double lds_ordered_mean(double* buf, int frames, int count, Value value_of, Counted counted) {
+    for (int f = threadIdx.x; f < frames; f += THREADS) buf[f] = counted(f) ? value_of(f) : 0.0;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int f = 0; f < frames; ++f)
+            if (counted(f)) s = s + buf[f];
+    __syncthreads();  // buf is read before the next use overwrites it
+    return count == 0 ? __builtin_nan("") : s / (double)count;
+}
+
 // ---- host: the caller's scratch ---------------------------------------------------------------------------------------------------------
 inline int64_t align256(int64_t v) { return round_up64(v, 256); }
 
@@ -81,6 +136,17 @@ struct ScratchPlan {
         return at;
     }
 };
+
+struct PairScratch {  // byte offsets into the caller's scratch, after the clips' lengths, and its size
+    int64_t vals, flags, need;
+};
+// A pair's frames: at most the PAIR_MAX_FRAMES that one workgroup holds in LDS, then (vals != nullptr) the scratch regions of the frames'
+// values [batch][f_max] of value_bytes each and of their flags [batch][f_max] int32.
+inline int pair_frames_plan(const char* what, int32_t batch, int64_t f_max, int value_bytes, ScratchPlan& plan, int64_t* vals, int64_t* flags) {
+    L3AC_REQUIRE(f_max <= PAIR_MAX_FRAMES, "%s: %lld frames are more than the %d of a pair", what, (long long)f_max, PAIR_MAX_FRAMES);
+    if (vals) *vals = plan.take((int64_t)batch * f_max * value_bytes), *flags = plan.take((int64_t)batch * f_max * 4);
+    return L3AC_OK;
+}
 
 // ---- host: a batch of clips [batch][max_samples] and their optional lengths; `what` is the prefix of the entry's messages -------------------
 inline int check_clip_batch(const char* what, int32_t batch, int64_t max_samples) {

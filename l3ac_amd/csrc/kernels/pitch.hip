@@ -3,7 +3,8 @@
 //
 //   pitch_kernel          grid (runs of PT_GROUPS frame groups, batch), 4 waves.  A group is G consecutive frames of one clip (G = 8, halved
 //                         until the group fits the LDS budget; a function of the parameters alone).  Per group:
-//     stage               the group's samples, (G - 1) min(hop, span) + span floats, go to LDS once; the loads run along the row at any
+//     stage               the group's samples, (G - 1) min(hop, span) + span floats (FrameGroups of frame_groups.hpp, which owns the
+//                         framing; its frame length n is the span here), go to LDS once; the loads run along the row at any
 //                         alignment and any hop, and the NEXT group's first PT_PRE x 256 samples are loaded into registers before the
 //                         current group is worked on
 //     difference          an item is (frame, 64 lags); the waves take the items in turn.  Lane l holds lag tau = 64 chunk + l: the read of
@@ -21,6 +22,7 @@
 // make NaN values in the frames that read them; every index is bounded by the parameters, whatever the values.
 //
 // Contraction is off for this whole file: the one fused operation, the fmaf of the difference function, is spelled out.
+#include "frame_groups.hpp"
 #include "metric_common.hpp"
 
 #include <algorithm>
@@ -40,9 +42,8 @@ constexpr int PT_MAX_SPAN = 4000;      // one frame's samples, d row and c row: 
 constexpr int PT_MIN_RATE = 8000, PT_MAX_RATE = 192000;
 constexpr int PM_THREADS = 256;
 
-struct PitchGeom {
-    int fs, tau_min, tau_max, t, w, hop, span;  // t = tau_max + 1: lags 0 .. t
-    int g, pitch, lds_bytes;                    // frames per group, min(hop, span), dynamic LDS of the launch
+struct PitchGeom : FrameGroups {  // n: the span = w + t samples a frame reads
+    int fs, tau_min, tau_max, t, w, lds_bytes;  // t = tau_max + 1: lags 0 .. t; dynamic LDS of the launch
     double threshold;
 };
 
@@ -62,20 +63,16 @@ int pitch_geom(int32_t fs, double fmin, double fmax, int32_t window, int32_t hop
     p->t = p->tau_max + 1;
     L3AC_REQUIRE(hop >= 1 || hop == -1, "pitch: hop %d must be at least 1 (-1: sample_rate / 100)", hop);
     L3AC_REQUIRE(window >= 1 || window == -1, "pitch: window %d must be at least 1 (-1: tau_max)", window);
-    p->hop = hop == -1 ? fs / 100 : hop;
     p->w = window == -1 ? p->tau_max : window;
     L3AC_REQUIRE((int64_t)p->w + p->t <= PT_MAX_SPAN, "pitch: span = window + tau_max + 1 = %lld above the cap of %d samples", (long long)p->w + p->t,
                  PT_MAX_SPAN);
-    p->span = p->w + p->t;
-    p->pitch = std::min(p->hop, p->span);
+    p->set_frames(p->w + p->t, hop == -1 ? fs / 100 : hop);
     p->g = PT_FRAMES;
-    while (p->g > 1 && lds_need(p->g, p->pitch, p->span, p->t + 1) > PT_LDS_TARGET) p->g >>= 1;
-    p->lds_bytes = lds_need(p->g, p->pitch, p->span, p->t + 1);
+    while (p->g > 1 && lds_need(p->g, p->pitch, p->n, p->t + 1) > PT_LDS_TARGET) p->g >>= 1;
+    p->lds_bytes = lds_need(p->g, p->pitch, p->n, p->t + 1);
     p->threshold = 0.0;
     return L3AC_OK;
 }
-
-int64_t frames_of(int64_t n, const PitchGeom& p) { return n < p.span ? 0 : 1 + (n - p.span) / p.hop; }
 
 __device__ __forceinline__ int wave_min_int(int v) {
 #pragma unroll
@@ -95,34 +92,27 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_kernel(const float* __restri
     float* xs = dd + (int64_t)p.g * lags;                               // [(g - 1) pitch + span]: frame k of the group starts at k pitch
     const int b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t n = lens ? lens[b] : max_samples;
-    const int64_t frames = n < p.span ? 0 : 1 + (n - p.span) / p.hop;
+    const int64_t frames = p.frames(lens ? lens[b] : max_samples);
     const float* x = audio + (int64_t)b * stride;
     const double nan = __builtin_nan("");
     if (frames_out && blockIdx.x == 0 && tid == 0) frames_out[b] = (int)frames;
 
     const int64_t run0 = (int64_t)blockIdx.x * (PT_GROUPS * p.g);
-    // what frame group `t0` stages: sample k of the stage is sample src(t0, k) of the clip; every one lies inside a frame below `frames`
-    auto count_of = [&](int64_t t0) { return t0 >= frames ? 0 : (frames - t0 < p.g ? (int)(frames - t0) : p.g); };
-    auto src = [&](int64_t t0, int k) -> int64_t {
-        if (p.hop <= p.span) return t0 * p.hop + k;
-        return (t0 + k / p.span) * p.hop + k % p.span;
-    };
     float pre[PT_PRE];
-    auto fetch = [&](int64_t t0) {
-        const int cnt = count_of(t0);
-        const int floats = cnt ? (cnt - 1) * p.pitch + p.span : 0;
+    auto fetch = [&](int64_t t0) {  // the first samples that frame group t0 stages
+        const int cnt = p.count(t0, frames);
+        const int floats = cnt ? p.floats(cnt) : 0;
 #pragma unroll
         for (int i = 0; i < PT_PRE; ++i) {
             const int k = tid + i * PT_THREADS;
-            pre[i] = k < floats ? x[src(t0, k)] : 0.f;
+            pre[i] = k < floats ? x[p.src(t0, k)] : 0.f;
         }
     };
     fetch(run0);
     for (int gi = 0; gi < PT_GROUPS; ++gi) {
         const int64_t t0 = run0 + (int64_t)gi * p.g;
         if (t0 >= f_max) break;  // (the whole workgroup)
-        const int cnt = count_of(t0);
+        const int cnt = p.count(t0, frames);
         // rows at and after the clip's own frames
         for (int k = cnt + wave; k < p.g && t0 + k < f_max; k += PT_WAVES) {
             const int64_t row = (int64_t)b * f_max + t0 + k;
@@ -131,14 +121,14 @@ __global__ __launch_bounds__(PT_THREADS) void pitch_kernel(const float* __restri
                 for (int tau = lane; tau < lags; tau += 64) cmnd[row * lags + tau] = nan;
         }
         if (cnt == 0) continue;  // (the whole workgroup; no later group of this clip has a frame either)
-        const int floats = (cnt - 1) * p.pitch + p.span;
+        const int floats = p.floats(cnt);
         __syncthreads();  // the previous group's reads of xs, dd and cm are over
 #pragma unroll
         for (int i = 0; i < PT_PRE; ++i) {
             const int k = tid + i * PT_THREADS;
             if (k < floats) xs[k] = pre[i];
         }
-        for (int k = PT_PRE * PT_THREADS + tid; k < floats; k += PT_THREADS) xs[k] = x[src(t0, k)];
+        for (int k = PT_PRE * PT_THREADS + tid; k < floats; k += PT_THREADS) xs[k] = x[p.src(t0, k)];
         __syncthreads();
         if (gi + 1 < PT_GROUPS && t0 + p.g < f_max) fetch(t0 + p.g);
 
@@ -288,7 +278,7 @@ int l3ac_pitch_lags(int32_t sample_rate, double fmin, double fmax, int32_t windo
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(out, "pitch_lags: null out");
-    out[0] = p.tau_min, out[1] = p.tau_max, out[2] = p.w, out[3] = p.hop, out[4] = p.span;
+    out[0] = p.tau_min, out[1] = p.tau_max, out[2] = p.w, out[3] = p.hop, out[4] = p.n;
     return L3AC_OK;
 }
 
@@ -296,7 +286,7 @@ int64_t l3ac_pitch_frames(int64_t samples, int32_t sample_rate, double fmin, dou
     PitchGeom p;
     L3AC_TRY(pitch_geom(sample_rate, fmin, fmax, window, hop, &p));
     L3AC_REQUIRE(samples >= 0, "pitch_frames: samples %lld must not be negative", (long long)samples);
-    return frames_of(samples, p);
+    return p.frames(samples);
 }
 
 int64_t l3ac_pitch_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate, double fmin, double fmax, int32_t window, int32_t hop) {
@@ -315,7 +305,7 @@ int l3ac_pitch(const float* audio, int64_t audio_stride, int32_t batch, int64_t 
     L3AC_REQUIRE(threshold > 0.0 && threshold < 1.0, "pitch: threshold %g outside (0, 1)", threshold);
     p.threshold = threshold;
     L3AC_TRY(check_clip_batch("pitch", batch, max_samples));
-    const int64_t f_max = frames_of(max_samples, p);
+    const int64_t f_max = p.frames(max_samples);
     L3AC_REQUIRE(audio, "pitch: null audio");
     L3AC_REQUIRE(f_max == 0 || (f0 && voiced && aperiodicity), "pitch: null output buffer");
     L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "pitch: row stride %lld below max_samples %lld", (long long)audio_stride,
