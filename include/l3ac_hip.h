@@ -494,6 +494,46 @@ int l3ac_loudness_gain(const double* stats, int32_t batch, double target_lufs, d
 int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_t out_stride, int32_t batch, int64_t max_samples,
                     const int32_t* samples, const double* gain, int64_t gain_stride, void* stream);
 
+/* ---- EBU R128: block loudness series, loudness range and true peak -------------------------------------------------
+ * On the step energies e_s of the loudness meter above (the same rates, steps, filter and kernels): a block of W steps that starts at
+ * step k has z_k = (((e_k + e_{k+1}) + ...) + e_{k+W-1}) / (W step), summed left to right (W = 4: the meter's own block, bit for bit), and
+ * l_k = -0.691 + 10 log10 z_k.  A clip of S whole steps has K = max(S - W + 1, 0) such blocks, one every 100 ms.
+ *   l3ac_r128_scratch_bytes: the minimum scratch of l3ac_r128_series and l3ac_r128_range (that of l3ac_loudness); the same refusals.
+ *   l3ac_r128_series:        window_steps = W in 1..600 -> lufs [batch][K(max_samples)] fp64 = l_k, -inf at and after a clip's own K;
+ *                            mean_square (or NULL) [batch][K(max_samples)] = z_k, 0 there; energies (or NULL) [batch][S(max_samples)] = e_s,
+ *                            0 at and after a clip's own S; blocks (or NULL) [batch] int32 = the clip's own K.  lufs may be NULL only when
+ *                            K(max_samples) = 0.
+ *   l3ac_r128_range:         EBU Tech 3342 on the short-term blocks, W = 30 (3 s) every step (100 ms: 2.9 s of overlap, where Tech 3342 asks
+ *                            for at least 2 s).  The gates decide on l as the meter's do: the absolute gate l_k > -70, the relative gate
+ *                            l_k > G, G = -0.691 + 10 log10(mean of the absolutely gated z) - 20.  The g survivors' z are sorted ascending;
+ *                            low = l of z[((g - 1) 10 + 50) / 100], high = l of z[((g - 1) 95 + 50) / 100] (integer division), lra = high -
+ *                            low; g = 0: lra = 0 exactly, low = high = -inf.  stats [batch][5] fp64 = lra, low, high, the largest l_k
+ *                            (short-term maximum), the largest l of the W = 4 blocks (momentary maximum), both -inf without a block;
+ *                            counts [batch][3] int32 = K, the blocks above the absolute gate, g.  A clip of more than 16384 short-term
+ *                            blocks (27 min) is refused before any device work.
+ * True peak: the largest magnitude of the clip oversampled L times by l3ac_resample's own filter for fs -> L fs (21 taps a phase, the
+ * same host design, the same fp32 fmaf chain per output: the bits of max |l3ac_resample(clip alone)|), L = 4 for 8000 <= fs < 96000,
+ * L = 2 for 96000 <= fs <= 192000; samples before the clip and at and after its length are zero.
+ *   l3ac_true_peak_factor:        HOST only: L; < 0 with a message for a rate outside 8000..192000.
+ *   l3ac_true_peak_tile:          HOST only: the input positions one workgroup evaluates (no part of the bits).
+ *   l3ac_true_peak_scratch_bytes: the minimum scratch of l3ac_true_peak; < 0 for batch outside 1..65535, max_samples outside 1..2^31 - 1
+ *                                 or an unsupported rate.
+ *   l3ac_true_peak:               stats [batch][2] fp64 (device) = max(peak, os), peak: os the oversampled maximum, peak = max |x|.
+ * Every bad argument is L3AC_EINVAL before any device work, with a message naming it.  Bit guarantee and calling convention: as the
+ * loudness meter's.  No device table: the taps travel as kernel arguments, so l3ac_true_peak can be captured as a process' first call.
+ * Non-finite samples leave their own clip's results unspecified and no other clip's. */
+int64_t l3ac_r128_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate);
+int l3ac_r128_series(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                     int32_t window_steps, double* lufs, double* mean_square, double* energies, int32_t* blocks, void* scratch, int64_t scratch_bytes,
+                     void* stream);
+int l3ac_r128_range(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                    double* stats, int32_t* counts, void* scratch, int64_t scratch_bytes, void* stream);
+int32_t l3ac_true_peak_factor(int32_t sample_rate);
+int32_t l3ac_true_peak_tile(void);
+int64_t l3ac_true_peak_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate);
+int l3ac_true_peak(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                   double* stats, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- IIR filtering: scipy.signal.sosfilt one-shot and streaming, Butterworth designs -----------------------------
  * A cascade of 1 <= sections <= 8 second-order sections filters MONO clips, in fp64 throughout (the fp32 samples convert exactly).  `sos`
  * is a HOST array [sections][5] = b0 b1 b2 a1 a2 (a0 = 1: the caller has divided by it).  One sample through one section is one

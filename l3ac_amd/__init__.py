@@ -40,7 +40,8 @@ from .chunking import ChunkData, _chunk_cut, _chunk_groups, _chunk_merge, _group
 from .metrics import (DEFAULT_SCALES, _check_params as _check_metric_params, _scales as _metric_scales, log_mel, mel_distance, mel_weights,
                       signal_metrics, stft, stft_basis, stft_frames, stoi, stoi_bands, stoi_basis, stoi_frames)
 from .loudness import (_check_rate as _check_loudness_rate, apply_gain, loudness, loudness as _loudness, loudness_blocks, loudness_coeffs, loudness_gain,
-                       normalize_loudness)
+                       loudness_range, loudness_range as _loudness_range, normalize_loudness, short_term_loudness, true_peak, true_peak as _true_peak,
+                       true_peak_factor)
 from .pitch import _check_params as _check_pitch_params, pitch, pitch_frames, pitch_lags, pitch_metrics, pitch_metrics as _pitch_metrics
 from .align import align, apply_delay, delay
 from .mcd import _check_mfcc_params, _mfcc_hop, dct_table, dtw, mcd, mcd as _mcd, mfcc
@@ -66,7 +67,7 @@ __all__ = ["set_gemm_split", "get_gemm_split", "gemm_split_routes", "restore_gem
            "apply_delay", "align", "mfcc", "dtw", "mcd", "dct_table", "lpc", "lpc_metrics", "lpc_frames", "lpc_defaults", "lpc_window",
            "sdr", "correlate", "toeplitz_solve", "frame_spectrum", "band_energies", "band_metrics", "band_weights", "critical_bands",
            "coherence", "csii", "sii_bands", "sosfilt", "sosfilt_segment", "sosfilt_matrix", "butter_sos", "k_weighting_sos", "highpass",
-           "StreamFilter", "stream_filter", "filter_advance"]
+           "StreamFilter", "stream_filter", "filter_advance", "true_peak", "true_peak_factor", "short_term_loudness", "loudness_range"]
 __version__ = "0.1.0"
 
 log = logging.getLogger("L3AC")
@@ -557,7 +558,7 @@ class L3AC:
     def evaluate(self, audio_data: torch.Tensor, lengths=None, sample_rate: Optional[int] = None, process_window: int = 5 * 16000,
                  prefix_tokens: Optional[int] = None, chunks_per_call: Optional[int] = None, scales=None, intelligibility: bool = False, loudness: bool = False,
                  pitch: bool = False, mcd: bool = False, lpc: bool = False, sdr: bool = False, bands: bool = False,
-                 coherence: bool = False) -> dict:
+                 coherence: bool = False, r128: bool = False) -> dict:
         """How well this codec reproduces a batch of recordings: ``encode_long``, ``decode_long`` of the indices, then ``mel_distance``
         and ``signal_metrics`` between each recording and its decoded audio over the recording's own samples, all on the GPU.  With
         ``sample_rate`` the reference signal is the recording converted to the codec's rate (``resample``, each recording as it would
@@ -577,9 +578,14 @@ class L3AC:
         ``"fw_seg_snr_db"``, ``"wss"`` and ``"lsd_db"``: ``l3ac_amd.band_metrics`` of the same pairs at the codec's rate with its default
         parameters (section 3.22); a recording may then have at most 16384 frames.  ``coherence=True`` adds ``"csii"``, ``"csii_high"``,
         ``"csii_mid"``, ``"csii_low"`` and ``"csii_i3"``: ``l3ac_amd.csii`` of the same pairs at the codec's rate with its default parameters
-        (section 3.23), under the same limit of 16384 frames.  Every value equals composing those public calls by
-        hand, bit for bit."""
+        (section 3.23), under the same limit of 16384 frames.  ``r128=True`` adds ``"lra_reference"``, ``"lra_decoded"`` and ``"lra_shift"``
+        (decoded - reference, in LU), ``l3ac_amd.loudness_range`` of each side, and ``"true_peak_reference_db"`` and
+        ``"true_peak_decoded_db"`` in dBTP, ``l3ac_amd.true_peak`` of each side, at the codec's rate (section 3.25).  Every value equals
+        composing those public calls by hand, bit for bit."""
         scales = _metric_scales(scales)
+        if r128:  # a rate the meter or the oversampler is not defined for raises before any device work
+            _check_loudness_rate(self.config.sample_rate)
+            true_peak_factor(self.config.sample_rate)
         if coherence:  # a rate the defaults do not fit, or a batch too long for a pair, raises before any device work
             _, coh_frame, coh_hop, _, _ = _check_band_params(self.config.sample_rate, bands=sii_bands(self.config.sample_rate)[:2])
             longest = audio_data.shape[-1] if self._rate(sample_rate) is None else resample_length(int(sample_rate), self.config.sample_rate,
@@ -630,6 +636,12 @@ class L3AC:
             l_ref = _loudness(reference, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
             l_dec = _loudness(decoded, sample_rate=self.config.sample_rate, lengths=lens)["lufs"]
             out.update({"loudness_reference": l_ref, "loudness_decoded": l_dec, "loudness_shift": l_dec - l_ref})
+        if r128:
+            lra_ref = _loudness_range(reference, sample_rate=self.config.sample_rate, lengths=lens)["lra"]
+            lra_dec = _loudness_range(decoded, sample_rate=self.config.sample_rate, lengths=lens)["lra"]
+            out.update({"lra_reference": lra_ref, "lra_decoded": lra_dec, "lra_shift": lra_dec - lra_ref,
+                        "true_peak_reference_db": _true_peak(reference, sample_rate=self.config.sample_rate, lengths=lens)["true_peak_db"],
+                        "true_peak_decoded_db": _true_peak(decoded, sample_rate=self.config.sample_rate, lengths=lens)["true_peak_db"]})
         if pitch:
             pm = _pitch_metrics(reference, decoded, sample_rate=self.config.sample_rate, lengths=lens)
             out.update({"f0_rmse_cents": pm["f0_rmse_cents"], "gpe": pm["gpe"], "vde": pm["vde"], "ffe": pm["ffe"], "pitch_frames": pm["frames"],

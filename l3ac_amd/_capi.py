@@ -169,6 +169,13 @@ SIGNATURES = {
     "l3ac_loudness": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _P, _I64, _P]),
     "l3ac_loudness_gain": (C.c_int, [_P, _I32, C.c_double, C.c_double, _P, _P]),
     "l3ac_apply_gain": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, C.POINTER(_I32), _P, _I64, _P]),
+    "l3ac_r128_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_r128_series": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
+    "l3ac_r128_range": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _P, _I64, _P]),
+    "l3ac_true_peak_factor": (_I32, [_I32]),
+    "l3ac_true_peak_tile": (_I32, []),
+    "l3ac_true_peak_scratch_bytes": (_I64, [_I32, _I64, _I32]),
+    "l3ac_true_peak": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), _I32, _P, _P, _I64, _P]),
     "l3ac_sosfilt_segment": (_I32, []),
     "l3ac_sosfilt_scratch_bytes": (_I64, [_I32, _I64, _I32]),
     "l3ac_sosfilt": (C.c_int, [_P, _I64, _I32, _I64, C.POINTER(_I32), C.POINTER(C.c_double), _I32, _P, _I64, _I32, _P, _I64, _P]),

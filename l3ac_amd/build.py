@@ -52,6 +52,7 @@ SOURCES = [
     "kernels/metrics.hip",
     "kernels/stoi.hip",
     "kernels/loudness.hip",
+    "kernels/true_peak.hip",
     "kernels/iir.hip",
     "kernels/pitch.hip",
     "kernels/align.hip",

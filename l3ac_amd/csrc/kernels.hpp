@@ -186,7 +186,8 @@ struct ResamplePlan {
 int resample_plan(int32_t in_rate, int32_t out_rate, ResamplePlan* p);  // L3AC_EINVAL (message set) on unsupported rates
 int64_t resample_length(const ResamplePlan& p, int64_t n_in);
 int64_t resample_bank_floats(const ResamplePlan& p);                     // 0 when up == down (a copy needs no filter)
-void resample_fill_bank(const ResamplePlan& p, float* bank);             // host: [up][2][KE] fp32, each tap rounded once from fp64
+void resample_phase_taps(const ResamplePlan& p, float* taps);            // host: THE filter design: g_p[t] as [up][K] fp32, each tap rounded once from fp64
+void resample_fill_bank(const ResamplePlan& p, float* bank);             // host: [up][4][KE] fp32, the same taps laid out for resample_poly_kernel
 int64_t resample_stream_state_floats(const ResamplePlan& p);             // a stream's carried inputs: K - 1 rounded up to a multiple of 4
 // ragged batches (kernels/ragged.hip): per-clip counts reach the device as kernel arguments, CAP values per launch
 struct RaggedUpload {

@@ -11,6 +11,9 @@
 //                                   M and the running state are pairs of doubles (hi + lo), see pair.hpp
 //   3. loudness_pass_kernel<true>   every (clip, step) reruns the recursion from its true start state and sums y^2 in sample order: e_s
 //   4. loudness_gate_kernel         one workgroup per clip: z_j, l_j, the absolute and the relative gate, L, the sample peak, the counts
+// The EBU R128 entries run phases 1 to 3 through the same host helper and read the step energies instead of phase 4:
+//   loudness_series_kernel  the blocks of any window of 1 .. 600 steps: z_k, l_k, and a copy of the step energies
+//   loudness_range_kernel   one workgroup per clip: EBU Tech 3342 loudness range on 3 s blocks, the short-term and momentary maxima
 // The coefficients and M are designed on the host in fp64 (loudness_coeffs) and travel as kernel arguments: no device table, nothing to
 // warm up before a capture.  A step's values depend on its own samples and on the steps before it in its own clip only — never on the
 // batch, the clip's row, the row stride or the scratch size; no atomics; the sums of the gate kernel run over fixed strides and a fixed tree.
@@ -296,6 +299,157 @@ int filter_design(int32_t fs, LoudFilter* f) {
     return L3AC_OK;
 }
 
+// ---- phases 1 to 3 of every entry that needs the step energies: energy[clip][s] and step_max[clip][s] in the caller's scratch ----------------
+struct LoudBuffers {
+    double *state, *energy;
+    float* step_max;
+};
+
+int launch_step_energies(hipStream_t s, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int* lens,
+                         const LoudFilter& f, int64_t s_max, const LoudScratch& sc, void* scratch, LoudBuffers* w) {
+    char* base = static_cast<char*>(scratch);
+    double* state = w->state = reinterpret_cast<double*>(base + sc.state);
+    double* energy = w->energy = reinterpret_cast<double*>(base + sc.energy);
+    float* step_max = w->step_max = reinterpret_cast<float*>(base + sc.step_max);
+    if (s_max <= 0) return L3AC_OK;
+    const dim3 grid((unsigned)ceil_div64(s_max, LD_STEPS), (unsigned)batch);
+    const double flops = 22.0 * batch * (double)max_samples, bytes = 4.0 * batch * (double)max_samples;
+    {
+        ProfScope prof(s, "loudness_pass_kernel<state>", flops, bytes);
+        hipLaunchKernelGGL(loudness_pass_kernel<false>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
+                           step_max);
+        L3AC_LAUNCH_CHECK();
+    }
+    {
+        ProfScope prof(s, "loudness_scan_kernel", 32.0 * batch * (double)s_max, 64.0 * batch * (double)s_max);
+        hipLaunchKernelGGL(loudness_scan_kernel, dim3((unsigned)ceil_div64(batch, 64)), dim3(64), 0, s, batch, max_samples, lens, f, s_max, state);
+        L3AC_LAUNCH_CHECK();
+    }
+    {
+        ProfScope prof(s, "loudness_pass_kernel<energy>", flops, bytes);
+        hipLaunchKernelGGL(loudness_pass_kernel<true>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
+                           step_max);
+        L3AC_LAUNCH_CHECK();
+    }
+    return L3AC_OK;
+}
+
+// ---- EBU R128 on the step energies: the block series of any window, and the loudness range ---------------------------------
+// A block of W steps that starts at step k: z_k = (((e_k + e_{k+1}) + ...) + e_{k+W-1}) / (W step), summed left to right (W = 4: the
+// mean_square of loudness_gate_kernel bit for bit), l_k = -0.691 + 10 log10 z_k.  A clip of `steps` whole steps has max(steps - W + 1, 0).
+constexpr int LD_SERIES_THREADS = 256;
+constexpr int LD_MAX_WINDOW = 600;       // steps: 60 s
+constexpr int LD_SHORT_STEPS = 30;       // the short-term window, 3 s
+constexpr int LD_RANGE_THREADS = PAIR_THREADS;
+
+__device__ __forceinline__ double block_mean_square(const double* __restrict__ e, int64_t k, int w, double norm) {
+    double sum = e[k];
+    for (int i = 1; i < w; ++i) sum = sum + e[k + i];
+    return sum / norm;
+}
+
+__device__ __forceinline__ double lkfs_of(double z) { return -0.691 + 10.0 * log10(z); }  // (-inf for z = 0)
+
+// grid (ceil(max(k_max, s_max) / 256), batch): lufs [batch][k_max] (-inf at and after the clip's own blocks), mean_square [batch][k_max] or
+// null (0 there), energies [batch][s_max] or null (the step energies, 0 at and after the clip's own steps), blocks_out [batch] or null
+__global__ __launch_bounds__(LD_SERIES_THREADS) void loudness_series_kernel(int64_t max_samples, const int* __restrict__ lens, int step, int window,
+                                                                          int64_t s_max, int64_t k_max, const double* __restrict__ energy,
+                                                                          double* __restrict__ lufs, double* __restrict__ mean_square,
+                                                                          double* __restrict__ energies, int* __restrict__ blocks_out) {
+    const int b = blockIdx.y;
+    const int64_t steps = (lens ? lens[b] : max_samples) / step;
+    const int64_t blocks = steps >= window ? steps - window + 1 : 0;
+    const double* e = energy + (int64_t)b * s_max;
+    const int64_t k = (int64_t)blockIdx.x * LD_SERIES_THREADS + threadIdx.x;
+    if (k < k_max) {
+        const double z = k < blocks ? block_mean_square(e, k, window, (double)window * (double)step) : 0.0;
+        lufs[(int64_t)b * k_max + k] = k < blocks ? lkfs_of(z) : -__builtin_huge_val();
+        if (mean_square) mean_square[(int64_t)b * k_max + k] = z;
+    }
+    if (energies && k < s_max) energies[(int64_t)b * s_max + k] = k < steps ? e[k] : 0.0;
+    if (blocks_out && k == 0) blocks_out[b] = (int)blocks;
+}
+
+// One workgroup per clip, the clip's short-term z_k in LDS (at most PAIR_MAX_FRAMES of them: the host checked): EBU Tech 3342 on blocks of
+// 3 s every 100 ms.  The gates decide on l values as loudness_gate_kernel does; the relative gate lies 20 LU below the absolutely gated level.
+// The survivors' z, +inf elsewhere up to n_pad, are sorted ascending; the percentiles are picks, in integer arithmetic.
+// stats [b][5] = lra, low, high, short_term_max, momentary_max; counts [b][3] = blocks, above the absolute gate, gated.
+__global__ __launch_bounds__(LD_RANGE_THREADS) void loudness_range_kernel(int64_t max_samples, const int* __restrict__ lens, int step, int64_t s_max,
+                                                                        int n_pad_max, const double* __restrict__ energy, double* __restrict__ stats,
+                                                                        int* __restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) double range_z[];  // [n_pad_max]
+    __shared__ double lds[LD_RANGE_THREADS / 64];
+    const int b = blockIdx.x;
+    const int64_t steps = (lens ? lens[b] : max_samples) / step;
+    const int blocks = (int)std::min<int64_t>(steps >= LD_SHORT_STEPS ? steps - LD_SHORT_STEPS + 1 : 0, n_pad_max);  // (the clamp bounds every index)
+    const int64_t blocks4 = steps > 3 ? steps - 3 : 0;
+    const double* e = energy + (int64_t)b * s_max;
+    const double ninf = -__builtin_huge_val();
+    int n_pad = 1;
+    while (n_pad < blocks) n_pad <<= 1;
+
+    // the momentary maximum over the 400 ms blocks
+    double mom = ninf;
+    for (int64_t j = threadIdx.x; j < blocks4; j += LD_RANGE_THREADS) mom = fmax(mom, lkfs_of(block_mean_square(e, j, 4, 4.0 * (double)step)));
+    mom = block_max<LD_RANGE_THREADS>(mom, lds);
+
+    // the short-term blocks, their maximum, the absolute gate
+    double st = ninf, sum = 0.0, cnt = 0.0;
+    for (int k = threadIdx.x; k < blocks; k += LD_RANGE_THREADS) {
+        const double z = block_mean_square(e, k, LD_SHORT_STEPS, (double)LD_SHORT_STEPS * (double)step), l = lkfs_of(z);
+        range_z[k] = z;
+        st = fmax(st, l);
+        if (l > -70.0) sum += z, cnt += 1.0;
+    }
+    st = block_max<LD_RANGE_THREADS>(st, lds);
+    sum = block_sum<LD_RANGE_THREADS>(sum, lds);
+    cnt = block_sum<LD_RANGE_THREADS>(cnt, lds);  // (whole numbers below 2^31: exact)
+    // the relative gate (no absolutely gated block: nothing passes); every thread rewrites the elements it wrote
+    const double gamma = lkfs_of(sum / cnt) - 20.0;
+    double kept = 0.0;
+    for (int k = threadIdx.x; k < n_pad; k += LD_RANGE_THREADS) {
+        double keep = __builtin_huge_val();
+        if (k < blocks && cnt > 0.0) {
+            const double z = range_z[k], l = lkfs_of(z);
+            if (l > -70.0 && l > gamma) keep = z, kept += 1.0;
+        }
+        range_z[k] = keep;
+    }
+    kept = block_sum<LD_RANGE_THREADS>(kept, lds);  // (its barriers publish range_z)
+    lds_sort<LD_RANGE_THREADS>(range_z, n_pad);
+    if (threadIdx.x == 0) {
+        const int g = (int)kept;
+        double low = ninf, high = ninf, lra = 0.0;
+        if (g > 0) {
+            low = lkfs_of(range_z[((g - 1) * 10 + 50) / 100]);
+            high = lkfs_of(range_z[((g - 1) * 95 + 50) / 100]);
+            lra = high - low;
+        }
+        double* out = stats + 5 * (int64_t)b;
+        out[0] = lra, out[1] = low, out[2] = high, out[3] = st, out[4] = mom;
+        counts[3 * (int64_t)b] = blocks, counts[3 * (int64_t)b + 1] = (int)cnt, counts[3 * (int64_t)b + 2] = g;
+    }
+}
+
+int configure_range_kernel() {
+    static PerDeviceOnce configured;
+    if (configured.first()) {
+        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(loudness_range_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           PAIR_MAX_FRAMES * 8));
+        configured.done();
+    }
+    return L3AC_OK;
+}
+
+// what the series and the range share with l3ac_loudness: the checks, the staged lengths, the design, phases 1 to 3
+int step_energies_of(hipStream_t s, const char* what, const char* entry, const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples,
+                     const int32_t* samples, int32_t sample_rate, void* scratch, int64_t scratch_bytes, int64_t s_max, const LoudScratch& sc,
+                     LoudFilter* f, int** lens, LoudBuffers* w) {
+    L3AC_TRY(stage_clip_lengths(s, what, entry, samples, batch, scratch, scratch_bytes, sc.total_min, lens));
+    L3AC_TRY(filter_design(sample_rate, f));
+    return launch_step_energies(s, audio, audio_stride, batch, max_samples, *lens, *f, s_max, sc, scratch, w);
+}
+
 }  // namespace
 
 extern "C" {
@@ -341,33 +495,12 @@ int l3ac_loudness(const float* audio, int64_t audio_stride, int32_t batch, int64
     L3AC_TRY(stage_clip_lengths(s, "loudness", "loudness", samples, batch, scratch, scratch_bytes, sc.total_min, &lens));
     LoudFilter f;
     L3AC_TRY(filter_design(sample_rate, &f));
-    char* base = static_cast<char*>(scratch);
-    double* state = reinterpret_cast<double*>(base + sc.state);
-    double* energy = reinterpret_cast<double*>(base + sc.energy);
-    float* step_max = reinterpret_cast<float*>(base + sc.step_max);
+    LoudBuffers w;
+    L3AC_TRY(launch_step_energies(s, audio, audio_stride, batch, max_samples, lens, f, s_max, sc, scratch, &w));
+    double* energy = w.energy;
+    float* step_max = w.step_max;
     const int64_t j_max = std::max<int64_t>(s_max - 3, 0);
 
-    if (s_max > 0) {
-        const dim3 grid((unsigned)ceil_div64(s_max, LD_STEPS), (unsigned)batch);
-        const double flops = 22.0 * batch * (double)max_samples, bytes = 4.0 * batch * (double)max_samples;
-        {
-            ProfScope prof(s, "loudness_pass_kernel<state>", flops, bytes);
-            hipLaunchKernelGGL(loudness_pass_kernel<false>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
-                               step_max);
-            L3AC_LAUNCH_CHECK();
-        }
-        {
-            ProfScope prof(s, "loudness_scan_kernel", 32.0 * batch * (double)s_max, 64.0 * batch * (double)s_max);
-            hipLaunchKernelGGL(loudness_scan_kernel, dim3((unsigned)ceil_div64(batch, 64)), dim3(64), 0, s, batch, max_samples, lens, f, s_max, state);
-            L3AC_LAUNCH_CHECK();
-        }
-        {
-            ProfScope prof(s, "loudness_pass_kernel<energy>", flops, bytes);
-            hipLaunchKernelGGL(loudness_pass_kernel<true>, grid, dim3(LD_STEPS), 0, s, audio, audio_stride, max_samples, lens, f, s_max, state, energy,
-                               step_max);
-            L3AC_LAUNCH_CHECK();
-        }
-    }
     ProfScope prof(s, "loudness_gate_kernel", 0.0, 12.0 * batch * (double)s_max);
     hipLaunchKernelGGL(loudness_gate_kernel, dim3((unsigned)batch), dim3(LD_GATE_THREADS), 0, s, audio, audio_stride, max_samples, lens, f.step, s_max,
                        j_max, energy, step_max, stats, counts, j_max > 0 ? momentary : nullptr);
@@ -410,6 +543,70 @@ int l3ac_apply_gain(const float* audio, int64_t audio_stride, float* out, int64_
         L3AC_LAUNCH_CHECK();
         return L3AC_OK;
     });
+}
+
+int64_t l3ac_r128_scratch_bytes(int32_t batch, int64_t max_samples, int32_t sample_rate) {
+    int64_t s_max;
+    LoudScratch sc;
+    L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
+    return sc.total_min;
+}
+
+int l3ac_r128_series(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                     int32_t window_steps, double* lufs, double* mean_square, double* energies, int32_t* blocks, void* scratch, int64_t scratch_bytes,
+                     void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int64_t s_max;
+    LoudScratch sc;
+    L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
+    L3AC_REQUIRE(window_steps >= 1 && window_steps <= LD_MAX_WINDOW, "r128_series: window_steps %d outside 1..%d", window_steps, LD_MAX_WINDOW);
+    const int64_t k_max = std::max<int64_t>(s_max - window_steps + 1, 0);
+    L3AC_REQUIRE(audio && (lufs || k_max == 0), "r128_series: null buffer");
+    L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "r128_series: row stride %lld below max_samples %lld", (long long)audio_stride,
+                 (long long)max_samples);
+    L3AC_TRY(check_clip_lengths("r128_series", samples, batch, max_samples));
+    LoudFilter f;
+    int* lens;
+    LoudBuffers w;
+    L3AC_TRY(step_energies_of(s, "r128_series", "r128", audio, audio_stride, batch, max_samples, samples, sample_rate, scratch, scratch_bytes, s_max, sc,
+                              &f, &lens, &w));
+    const int64_t cells = std::max<int64_t>(std::max(k_max, energies ? s_max : 0), 1);  // (one workgroup a clip at least: the block counts)
+    ProfScope prof(s, "loudness_series_kernel", 1.0 * window_steps * batch * (double)k_max, 24.0 * batch * (double)s_max);
+    hipLaunchKernelGGL(loudness_series_kernel, dim3((unsigned)ceil_div64(cells, LD_SERIES_THREADS), (unsigned)batch), dim3(LD_SERIES_THREADS), 0, s,
+                       max_samples, lens, f.step, window_steps, s_max, k_max, w.energy, lufs, k_max > 0 ? mean_square : nullptr,
+                       s_max > 0 ? energies : nullptr, blocks);
+    L3AC_LAUNCH_CHECK();
+    return L3AC_OK;
+}
+
+int l3ac_r128_range(const float* audio, int64_t audio_stride, int32_t batch, int64_t max_samples, const int32_t* samples, int32_t sample_rate,
+                    double* stats, int32_t* counts, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int64_t s_max;
+    LoudScratch sc;
+    L3AC_TRY(loud_geom(batch, max_samples, sample_rate, &s_max, &sc));
+    L3AC_REQUIRE(audio && stats && counts, "r128_range: null buffer");
+    L3AC_REQUIRE(batch == 1 || audio_stride >= max_samples, "r128_range: row stride %lld below max_samples %lld", (long long)audio_stride,
+                 (long long)max_samples);
+    L3AC_TRY(check_clip_lengths("r128_range", samples, batch, max_samples));
+    // the short-term blocks of the longest clip live in one workgroup's LDS
+    int64_t longest = samples ? 0 : max_samples;
+    for (int i = 0; samples && i < batch; ++i) longest = std::max<int64_t>(longest, samples[i]);
+    const int64_t k_most = std::max<int64_t>(longest / (sample_rate / 10) - LD_SHORT_STEPS + 1, 0);
+    L3AC_REQUIRE(k_most <= PAIR_MAX_FRAMES, "r128_range: %lld short-term blocks are more than the %d of a clip", (long long)k_most, PAIR_MAX_FRAMES);
+    int n_pad = 1;
+    while (n_pad < k_most) n_pad <<= 1;
+    LoudFilter f;
+    int* lens;
+    LoudBuffers w;
+    L3AC_TRY(step_energies_of(s, "r128_range", "r128", audio, audio_stride, batch, max_samples, samples, sample_rate, scratch, scratch_bytes, s_max, sc,
+                              &f, &lens, &w));
+    L3AC_TRY(configure_range_kernel());
+    ProfScope prof(s, "loudness_range_kernel", 34.0 * batch * (double)s_max, 8.0 * 34 * batch * (double)s_max);
+    hipLaunchKernelGGL(loudness_range_kernel, dim3((unsigned)batch), dim3(LD_RANGE_THREADS), (size_t)n_pad * 8, s, max_samples, lens, f.step, s_max, n_pad,
+                       w.energy, stats, counts);
+    L3AC_LAUNCH_CHECK();
+    return L3AC_OK;
 }
 
 }  // extern "C"

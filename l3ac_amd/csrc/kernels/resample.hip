@@ -174,7 +174,7 @@ int64_t resample_length(const ResamplePlan& p, int64_t n_in) { return ceil_div64
 
 int64_t resample_bank_floats(const ResamplePlan& p) { return p.up == p.down ? 0 : (int64_t)p.up * 4 * p.KE; }
 
-void resample_fill_bank(const ResamplePlan& p, float* bank) {
+void resample_phase_taps(const ResamplePlan& p, float* taps) {
     const int M = std::max(p.up, p.down);
     const int n = 2 * p.half_len + 1;
     // firwin(n, 1 / M, window=('kaiser', 5.0)), scipy's arithmetic: h = c sinc(c (k - alpha)) w[k], normalised to unit sum
@@ -190,15 +190,22 @@ void resample_fill_bank(const ResamplePlan& p, float* bank) {
         sum += h[k];
     }
     for (int k = 0; k < n; ++k) h[k] = h[k] / sum * p.up;
+    for (int ph = 0; ph < p.up; ++ph)
+        for (int t = 0; t < p.K; ++t) {
+            const int64_t j = ph + (int64_t)(p.K - 1 - t) * p.up;
+            taps[(int64_t)ph * p.K + t] = j < n ? (float)h[j] : 0.f;
+        }
+}
+
+void resample_fill_bank(const ResamplePlan& p, float* bank) {
+    std::vector<float> taps((size_t)p.up * p.K);
+    resample_phase_taps(p, taps.data());
     // bank[phase][v][KE], v = 0 .. 3: v zeros, then g_p[0 .. K), zero-padded to KE
     for (int ph = 0; ph < p.up; ++ph) {
         float* rows = bank + (int64_t)ph * 4 * p.KE;
         for (int t = 0; t < 4 * p.KE; ++t) rows[t] = 0.f;
-        for (int t = 0; t < p.K; ++t) {
-            const int64_t j = ph + (int64_t)(p.K - 1 - t) * p.up;
-            const float tap = j < n ? (float)h[j] : 0.f;
-            for (int v = 0; v < 4; ++v) rows[v * p.KE + v + t] = tap;
-        }
+        for (int t = 0; t < p.K; ++t)
+            for (int v = 0; v < 4; ++v) rows[v * p.KE + v + t] = taps[(size_t)ph * p.K + t];
     }
 }
 

@@ -1,6 +1,8 @@
 """Loudness on the GPU (csrc/kernels/loudness.hip): ITU-R BS.1770-4 integrated loudness of mono clips
 (``loudness``), the gain to a target (``loudness_gain``), its application (``apply_gain``) and the three composed
-(``normalize_loudness``); and the host accessors of the K-weighting design."""
+(``normalize_loudness``); the host accessors of the K-weighting design; and the EBU R128 measures of section 3.25 on the same base: the true
+peak (``true_peak``, csrc/kernels/true_peak.hip), the block loudness series (``short_term_loudness``) and the loudness range
+(``loudness_range``)."""
 from __future__ import annotations
 
 import math
@@ -132,17 +134,135 @@ def apply_gain(audio: torch.Tensor, gain: torch.Tensor, lengths=None) -> torch.T
     return out
 
 
+def true_peak_factor(sample_rate: int) -> int:
+    """The oversampling factor of ``true_peak``: 4 for 8000 <= sample_rate < 96000, 2 up to 192000.  Raises ValueError outside that range."""
+    return _metric.lib_value("l3ac_true_peak_factor", int(sample_rate))
+
+
+@torch.no_grad()
+def true_peak(audio: torch.Tensor, sample_rate: int = 16000, lengths=None) -> dict:
+    """The true peak of (B, T) fp32 CUDA mono clips after BS.1770-4 annex 2 -> ``{"true_peak": (B,) fp64, "true_peak_db": (B,) fp64,
+    "peak": (B,) fp64}`` on the device: ``true_peak = max(peak, max |resample(clip alone, sample_rate, L * sample_rate)|)`` bit for bit,
+    ``L = true_peak_factor(sample_rate)``, with zeros at and after the clip's length; ``peak`` is the sample peak ``max |x|``;
+    ``true_peak_db = 20 log10(true_peak)`` in dBTP, -inf for a silent clip.  The oversampled signal is never written.  ``lengths``: B ints
+    in 1..T; samples at or after a clip's length are ignored, whatever they hold.  A clip's bits do not depend on the batch it is in.  No
+    table is uploaded: the call can be captured as the first of a process.  No CPU path: CPU tensors raise."""
+    sample_rate = int(sample_rate)
+    true_peak_factor(sample_rate)
+    x = _metric.audio(audio, "true_peak")
+    b, t = x.shape
+    lens, c_lens = _metric.lengths(lengths, b, t)
+    dev = x.device
+    need = _metric.lib_value("l3ac_true_peak_scratch_bytes", b, t, sample_rate)
+    stats = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        scratch = _metric.scratch(dev, need)
+        _capi.check(_capi.load_library().l3ac_true_peak(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, stats.data_ptr(), scratch.data_ptr(),
+                                                        scratch.numel(), _metric.stream(dev)))
+    out = _metric.columns(stats, ("true_peak", "peak"))
+    return {"true_peak": out["true_peak"], "true_peak_db": 20.0 * torch.log10(out["true_peak"]), "peak": out["peak"]}
+
+
+def _window_steps(window) -> int:
+    """``window=`` in seconds -> whole steps of 100 ms, 1..600."""
+    try:
+        steps = round(float(window) * 10.0)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("window must be a number of seconds") from None
+    if not 1 <= steps <= 600 or abs(float(window) * 10.0 - steps) > 1e-9:
+        raise ValueError(f"window must be a multiple of 0.1 s in 0.1..60, got {window}")
+    return steps
+
+
+@torch.no_grad()
+def short_term_loudness(audio: torch.Tensor, sample_rate: int = 16000, lengths=None, window: float = 3.0, return_parts: bool = False) -> dict:
+    """The loudness of the blocks of ``window`` seconds, one every 100 ms, of (B, T) fp32 CUDA mono clips (EBU Tech 3341: 3 s is the
+    short-term loudness, 0.4 the momentary one, which is ``loudness(return_momentary=True)["momentary"]`` bit for bit) -> ``{"lufs": (B,
+    K(T)) fp64, "blocks": (B,) int32}`` on the device; a clip of n samples has ``K(n) = max(n // (sample_rate // 10) - W + 1, 0)`` blocks,
+    ``W = 10 window``, and ``lufs`` is -inf at and after them.  ``window``: a multiple of 0.1 s in 0.1..60.  ``return_parts`` adds
+    ``"mean_square"`` (B, K(T)), the blocks' K-weighted mean squares summed left to right over the steps (0 after a clip's blocks), and
+    ``"energies"`` (B, T // (sample_rate // 10)), the 100 ms step energies (0 after a clip's steps).  ``sample_rate``, ``lengths``, the bit
+    guarantee and capture: as ``loudness``."""
+    sample_rate = int(sample_rate)
+    _check_rate(sample_rate)
+    steps = _window_steps(window)
+    x = _metric.audio(audio, "short_term_loudness")
+    b, t = x.shape
+    lens, c_lens = _metric.lengths(lengths, b, t)
+    dev = x.device
+    step = sample_rate // 10
+    s_max = t // step
+    k_max = max(s_max - steps + 1, 0)
+    need = _metric.lib_value("l3ac_r128_scratch_bytes", b, t, sample_rate)
+    lufs = torch.empty((b, k_max), dtype=torch.float64, device=dev)
+    blocks = torch.empty((b,), dtype=torch.int32, device=dev)
+    mean_square = torch.empty((b, k_max), dtype=torch.float64, device=dev) if return_parts else None
+    energies = torch.empty((b, s_max), dtype=torch.float64, device=dev) if return_parts else None
+    with torch.cuda.device(dev):
+        scratch = _metric.scratch(dev, need)
+        _capi.check(_capi.load_library().l3ac_r128_series(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, steps, lufs.data_ptr() if k_max else None,
+                                                          mean_square.data_ptr() if return_parts and k_max else None,
+                                                          energies.data_ptr() if return_parts and s_max else None, blocks.data_ptr(),
+                                                          scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
+    out = {"lufs": lufs, "blocks": blocks}
+    if return_parts:
+        out["mean_square"], out["energies"] = mean_square, energies
+    return out
+
+
+@torch.no_grad()
+def loudness_range(audio: torch.Tensor, sample_rate: int = 16000, lengths=None) -> dict:
+    """EBU Tech 3342 loudness range of (B, T) fp32 CUDA mono clips, in fp64 -> ``{"lra", "low_lufs", "high_lufs", "short_term_max",
+    "momentary_max": (B,) fp64, "blocks", "above_absolute", "gated": (B,) int32}`` on the device.  Short-term blocks of 3 s every 100 ms
+    (``short_term_loudness``); those above -70 LUFS set the relative gate 20 LU below their mean level; of the ``gated`` blocks above both,
+    sorted by level, ``low_lufs`` is the 10th and ``high_lufs`` the 95th percentile (the blocks at ``((gated - 1) * 10 + 50) // 100`` and
+    ``((gated - 1) * 95 + 50) // 100``) and ``lra = high_lufs - low_lufs`` in LU; no gated block: ``lra`` is exactly 0 and both bounds
+    -inf.  ``short_term_max`` and ``momentary_max`` are the largest 3 s and 400 ms block loudness (EBU Tech 3341), -inf for a clip
+    without such a block.  A clip may have at most 16384 blocks (27 min).  ``sample_rate``, ``lengths``, the bit guarantee and capture:
+    as ``loudness``."""
+    sample_rate = int(sample_rate)
+    _check_rate(sample_rate)
+    x = _metric.audio(audio, "loudness_range")
+    b, t = x.shape
+    lens, c_lens = _metric.lengths(lengths, b, t)
+    dev = x.device
+    need = _metric.lib_value("l3ac_r128_scratch_bytes", b, t, sample_rate)
+    stats = torch.empty((b, 5), dtype=torch.float64, device=dev)
+    counts = torch.empty((b, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        scratch = _metric.scratch(dev, need)
+        _capi.check(_capi.load_library().l3ac_r128_range(x.data_ptr(), row_stride(x), b, t, c_lens, sample_rate, stats.data_ptr(), counts.data_ptr(),
+                                                         scratch.data_ptr(), scratch.numel(), _metric.stream(dev)))
+    return dict(_metric.columns(stats, ("lra", "low_lufs", "high_lufs", "short_term_max", "momentary_max")),
+                **_metric.columns(counts, ("blocks", "above_absolute", "gated")))
+
+
+def _peak_mode(peak) -> bool:
+    if peak not in ("sample", "true"):
+        raise ValueError(f"peak must be 'sample' or 'true', got {peak!r}")
+    return peak == "true"
+
+
 @torch.no_grad()
 def normalize_loudness(audio: torch.Tensor, target_lufs: float = -23.0, sample_rate: int = 16000, lengths=None,
-                       peak_limit_db: Optional[float] = -1.0):
+                       peak_limit_db: Optional[float] = -1.0, peak: str = "sample"):
     """(B, T) fp32 CUDA audio brought to ``target_lufs`` -> ``(audio_out, {"lufs", "peak", "gain_db", "gain"})``: ``loudness``,
     ``loudness_gain`` and ``apply_gain`` composed, bit for bit.  ``lufs`` and ``peak`` are the INPUT's.  The gain never reaches the host;
-    hand ``1 / info["gain"]`` to ``apply_gain`` after decoding to restore the level.  ``peak_limit_db=None``: no peak limit."""
+    hand ``1 / info["gain"]`` to ``apply_gain`` after decoding to restore the level.  ``peak_limit_db=None``: no peak limit.
+    ``peak="true"``: the limit is in dBTP; it applies to ``true_peak(audio)["true_peak"]``, which takes the place of the sample peak in
+    ``loudness_gain``'s input, and ``info`` gains ``"true_peak"`` (``"peak"`` stays the sample peak)."""
     sample_rate = int(sample_rate)
     _check_rate(sample_rate)
     _finite(target_lufs, "target_lufs")
     _limit(peak_limit_db)
+    if _peak_mode(peak):
+        true_peak_factor(sample_rate)
     stats = loudness(audio, sample_rate=sample_rate, lengths=lengths)
-    gain = loudness_gain(stats, target_lufs=target_lufs, peak_limit_db=peak_limit_db)
+    info = {"lufs": stats["lufs"], "peak": stats["peak"]}
+    limited = stats["peak"]
+    if peak == "true":
+        limited = info["true_peak"] = true_peak(audio, sample_rate=sample_rate, lengths=lengths)["true_peak"]
+    gain = loudness_gain({"lufs": stats["lufs"], "peak": limited}, target_lufs=target_lufs, peak_limit_db=peak_limit_db)
     out = apply_gain(audio, gain["gain"], lengths=lengths)
-    return out, {"lufs": stats["lufs"], "peak": stats["peak"], "gain_db": gain["gain_db"], "gain": gain["gain"]}
+    info.update({"gain_db": gain["gain_db"], "gain": gain["gain"]})
+    return out, info
