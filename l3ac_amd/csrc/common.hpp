@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "l3ac_hip.h"
 
@@ -60,6 +61,21 @@ struct PerDeviceOnce {  // `if (once.first()) { ...configure...; once.done(); }`
         if (s >= 0) flag[s].store(true, std::memory_order_release);
     }
 };
+// Raise kernels' dynamic LDS limits once per device, in front of their first launch there:
+//   static PerDeviceOnce configured;  // (one per launcher instantiation)
+//   L3AC_TRY(raise_dynamic_lds(configured, {{kernel_a, bytes_a}, {kernel_b<C, 2>, bytes_b}}));
+struct LdsLimit {
+    const void* kernel;
+    int bytes;
+    template <class K>
+    LdsLimit(K* k, size_t b) : kernel(reinterpret_cast<const void*>(k)), bytes((int)b) {}
+};
+static inline int raise_dynamic_lds(PerDeviceOnce& once, std::initializer_list<LdsLimit> limits) {
+    if (!once.first()) return L3AC_OK;
+    for (const LdsLimit& l : limits) L3AC_HIP_CHECK(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
+    once.done();
+    return L3AC_OK;
+}
 int l3ac_device_cu_count();  // multiprocessor count of the current device (cached per device; 256 if the query fails)
 static inline int64_t round_up64(int64_t a, int64_t b) { return ceil_div64(a, b) * b; }
 

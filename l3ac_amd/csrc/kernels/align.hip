@@ -25,6 +25,7 @@
 //
 // Contraction is off for this whole file: the only fused operations are those of the matrix instruction.
 #include "metric_common.hpp"
+#include "split_bf16.hpp"
 
 #include <algorithm>
 
@@ -47,7 +48,6 @@ constexpr int AP_THREADS = 256;
 static_assert(32 * XC_COLS <= XC_S + XC_EST, "the block's 32 x XC_COLS result tile reuses the LDS of the staged samples");
 static_assert(XC_TILES % XC_WAVES == 0 && XC_DIAGS <= XC_THREADS, "two tiles per wave, one lane per lag");
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 int64_t segments_of(int64_t n) { return ceil_div64(n, XC_S); }
 
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_kernel(const float* __restri
     // lane l holds A[l & 31][2 kp + (l >> 5)] and B[2 kp + (l >> 5)][l & 31]
     const int col = lane & 31, half = lane >> 5;
     const int t0 = wave, t1 = wave + XC_WAVES;
-    f32x16 acc0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 acc1 = acc0;
+    f32x16_t acc0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16_t acc1 = acc0;
     if (t0 < tiles) {  // (the whole wave)
         const float* ap = as + 32 * half + col;
         const float* bp = bs + 32 * half + col;

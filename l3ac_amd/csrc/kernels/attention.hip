@@ -11,6 +11,7 @@
 // wave-wide broadcasts; scores are evaluated twice (max pass, then exp/sum pass) rather than rescaled online,
 // to stay close to the reference's softmax.  <1 % of the path's FLOPs.
 #include "../kernels.hpp"
+#include "split_bf16.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -132,13 +133,10 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
 //      lanes; one cross-half shuffle per tile for the running max), and the probability tile is used directly as
 //   the B operand of  O^T[d][query] += V^T[d][key] . P[key][query]  (reduction over the accumulator's row index).
 // ---------------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 // KC: keys per LDS chunk = queries per workgroup (KC / 32 waves): 64 for clips of at most 64 frames (a 1 s chunk at 60 fps: half
 // the staging of the 128-key form), 192 for 129-192 frames (one workgroup and ONE staging pass per (clip, head) instead of two
 // workgroups and three), else 128.  Key tiles of 32 are visited in ascending order whatever KC is: the results do not depend on it.
 constexpr int KS_STRIDE = 36;  // K rows: 32 + 4 floats (odd number of 16-B slots)
-
-__device__ __forceinline__ int rowmap(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int KC>
 __global__ __launch_bounds__(2 * KC) void attention_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out,
@@ -174,7 +172,7 @@ __global__ __launch_bounds__(2 * KC) void attention_mfma_kernel(const float* __r
         qv[4 * q] = v.x * scale; qv[4 * q + 1] = v.y * scale; qv[4 * q + 2] = v.z * scale; qv[4 * q + 3] = v.w * scale;
     }
     float m_run = -INFINITY, l_run = 0.f;
-    f32x16 oacc;
+    f32x16_t oacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[r] = 0.f;
     const int w_lo = (q0 / window) > 0 ? (q0 / window - 1) * window : 0;  // first key any query of this wave can see
@@ -200,7 +198,7 @@ __global__ __launch_bounds__(2 * KC) void attention_mfma_kernel(const float* __r
         for (int kt = 0; kt < KC / 32; ++kt) {
             const int key0 = c0 + 32 * kt;
             if (key0 > q0 + 31 || key0 > jhi || key0 + 31 < w_lo) continue;  // wave-uniform: nothing visible in this tile
-            f32x16 sacc;
+            f32x16_t sacc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
@@ -214,7 +212,7 @@ __global__ __launch_bounds__(2 * KC) void attention_mfma_kernel(const float* __r
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = key0 + rowmap(r, lh);
+                const int key = key0 + split_rowmap(r, lh);
                 const bool vis = key <= i && key <= jhi && (key / window) >= wi - 1;
                 const float sv = vis ? sacc[r] + bias_s[vis ? i - key : 0] : -INFINITY;
                 sacc[r] = sv;

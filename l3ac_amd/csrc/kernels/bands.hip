@@ -290,11 +290,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void bands_pair_kernel(const double* 
 
 int configure_frame_kernel() {
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bands_frame_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BD_LDS_MAX));
-        configured.done();
-    }
-    return L3AC_OK;
+    return raise_dynamic_lds(configured, {{bands_frame_kernel, BD_LDS_MAX}});
 }
 
 // the parameters checked, then (metrics) the frames' three values [batch][F][3] fp64 and the frames' flags [batch][F] int32

@@ -307,10 +307,7 @@ __global__ __launch_bounds__(CO_THREADS) void coh_finish_kernel(CohIo io, CohGeo
 template <int BPT>
 int launch_chunks(hipStream_t s, const CohIo& io, const CohGeom& p, int32_t batch) {
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coh_chunk_kernel<BPT>), hipFuncAttributeMaxDynamicSharedMemorySize, CO_LDS_MAX));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{coh_chunk_kernel<BPT>, CO_LDS_MAX}}));
     ProfScope prof(s, "coh_chunk_kernel", 2.0 * batch * (double)io.f_max * 5.0 * p.n_fft * p.log2n, 8.0 * batch * (double)io.max_samples);
     hipLaunchKernelGGL(coh_chunk_kernel<BPT>, dim3((unsigned)io.chunks_max, (unsigned)batch), dim3(CO_THREADS), (size_t)p.lds_bytes, s, io, p);
     L3AC_LAUNCH_CHECK();

@@ -25,25 +25,21 @@
 // is the fp32 MFMA rate (16 C^2 FLOP per frame, + the channel padding of the second product to 32 ceil(C/32)).
 #include "../kernels.hpp"
 #include "../network.hpp"
+#include "conv_unit_front32.hpp"
 #include "device_math.hpp"
 #include "lane_sums.hpp"
+#include "split_bf16.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int C, int HC, int XH>  // XH: the input rows are staged in XH channel slices (LDS budget at C = 96)
-struct Geo {
-    static constexpr int H4 = 4 * C;          // hidden width
+template <int C, int HC, int XH>
+struct Geo : Front32Geo<C, XH> {
+    using F = Front32Geo<C, XH>;
+    static constexpr int H4 = F::H4, CT = F::CT;
     static constexpr int NCH = H4 / HC;       // weight chunks (1 = resident)
     static constexpr int NTC = HC / 32;       // hidden tiles per chunk
-    static constexpr int CT = (C + 31) / 32;  // output-channel tiles
-    static constexpr int KQ = C / 8;          // k groups of the first product
-    static constexpr int XC = C / XH;         // channels per staged slice
-    static constexpr int XS = XC + 4;         // padded row strides (odd number of 16-B slots: conflict-free b128)
-    static constexpr int W1S = C + 4;
+    static constexpr int W1S = C + 4;         // padded row strides (odd number of 16-B slots: conflict-free b128)
     static constexpr int W2S = HC + 4;
-    static constexpr int ROWS = 38;           // 32 frames + 3 + 3 halo
     // LDS carve (floats)
     static constexpr int NBUF = NCH == 1 ? 1 : 2;             // streamed weight chunks are double-buffered
     static constexpr int OFF_W1 = 0;                          // [HC][W1S]
@@ -54,12 +50,9 @@ struct Geo {
     static constexpr int OFF_B2 = OFF_B1 + H4;
     static constexpr int OFF_DW = OFF_B2 + 32 * CT;           // dw_w [7][C], dw_b, ln_w, ln_b
     static constexpr int OFF_XS = OFF_DW + 10 * C;
-    static constexpr int xs_floats = ROWS * XS;
-    static constexpr int lds_floats(int waves) { return OFF_XS + waves * xs_floats; }
-    static_assert(H4 % HC == 0 && HC % 32 == 0 && C % (8 * XH) == 0 && (NCH == 1 || NCH % 2 == 0), "bad geometry");
+    static constexpr int lds_floats(int waves) { return OFF_XS + waves * F::xs_floats; }
+    static_assert(H4 % HC == 0 && HC % 32 == 0 && (NCH == 1 || NCH % 2 == 0), "bad geometry");
 };
-
-__device__ __forceinline__ int rowmap(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int C, int WAVES, int HC, int XH>
 __global__ __launch_bounds__(64 * WAVES) void conv_unit_fused_kernel(const ConvUnitW w, const float* __restrict__ x,
@@ -273,11 +266,11 @@ __global__ __launch_bounds__(64 * WAVES) void conv_unit_fused_kernel(const ConvU
         }
 
         // ---- output accumulators start at the pw_conv2 bias ---------------------------------------------
-        f32x16 yacc[G::CT];
+        f32x16_t yacc[G::CT];
 #pragma unroll
         for (int ct = 0; ct < G::CT; ++ct)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) yacc[ct][r] = B2s[32 * ct + rowmap(r, lh)];
+            for (int r = 0; r < 16; ++r) yacc[ct][r] = B2s[32 * ct + split_rowmap(r, lh)];
 
 #pragma unroll 1
         for (int chunk = 0; chunk < G::NCH; ++chunk) {
@@ -291,10 +284,10 @@ __global__ __launch_bounds__(64 * WAVES) void conv_unit_fused_kernel(const ConvU
             }
             const int n_base = chunk * HC;
             // X[n][m] = b1[n] + sum_k W1[n][k] a[m][k] for hidden tile ntl of this chunk
-            auto first_product = [&](int ntl) -> f32x16 {
-                f32x16 acc;
+            auto first_product = [&](int ntl) -> f32x16_t {
+                f32x16_t acc;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = B1s[n_base + 32 * ntl + rowmap(r, lh)];
+                for (int r = 0; r < 16; ++r) acc[r] = B1s[n_base + 32 * ntl + split_rowmap(r, lh)];
 #pragma unroll
                 for (int q = 0; q < G::KQ; ++q) {
                     const float4 wf = *reinterpret_cast<const float4*>(W1s + (32 * ntl + lj) * G::W1S + 8 * q + 4 * lh);
@@ -306,16 +299,16 @@ __global__ __launch_bounds__(64 * WAVES) void conv_unit_fused_kernel(const ConvU
                 return acc;
             };
             // software pipeline: tile ntl+1's first product (MFMA pipe) runs beside tile ntl's activation (VALU)
-            f32x16 xnext = first_product(0);
+            f32x16_t xnext = first_product(0);
 #pragma unroll 1
             for (int ntl = 0; ntl < G::NTC; ++ntl) {
-                f32x16 xacc = xnext;
+                f32x16_t xacc = xnext;
                 if (ntl + 1 < G::NTC) xnext = first_product(ntl + 1);
                 // snake + GRN (normaliser == 1) on the accumulator registers (layers.py:29-33, :112-115)
                 // registers (r, r+1), r even, are adjacent hidden channels: packed fp32 math on register pairs
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    const float* pp = Ps + n_base + 32 * ntl + rowmap(r, lh);
+                    const float* pp = Ps + n_base + 32 * ntl + split_rowmap(r, lh);
                     const f32x2 al = *reinterpret_cast<const f32x2*>(pp);
                     const f32x2 ia = *reinterpret_cast<const f32x2*>(pp + G::H4);
                     const f32x2 ga = *reinterpret_cast<const f32x2*>(pp + 2 * G::H4);
@@ -374,11 +367,7 @@ int launch_fused(hipStream_t s, const ConvUnitW& w, const float* x, float* y, in
     const size_t lds = (size_t)G::lds_floats(WAVES) * sizeof(float);
     static_assert(G::lds_floats(WAVES) * sizeof(float) <= 160 * 1024, "LDS budget exceeded");
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_unit_fused_kernel<C, WAVES, HC, XH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{conv_unit_fused_kernel<C, WAVES, HC, XH>, lds}}));
     const int64_t tiles = (int64_t)batch * ((frames + 31) / 32);
     const int per_cu = lds > 80 * 1024 ? 1 : 2;
     int64_t blocks = ceil_div64(tiles, WAVES);

@@ -31,10 +31,6 @@
 
 namespace {
 
-__device__ __forceinline__ f32x4_t ring_mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4_t acc) {
-    return mfma6(a, b, acc);
-}
-
 // WAVES_ waves per workgroup, PER_CU workgroups per CU (register budget 512 / (WAVES_ PER_CU / 4) per lane), SP_ pieces per ring
 // slot, RSLOTS_ ring slots.  RESIDENT: the unit's whole stream fits LDS (C = 24: 36 KB, C = 48: 126 KB) — loaded once per
 // workgroup, then no DMA, no barrier: the waves run independently of each other.
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
                 const unsigned char* src = w.ring_img + (int64_t)dma_slot * G::SLOT + 1024 * wave;
                 const unsigned dst = ring_lds + (unsigned)(ring_pos_w * G::SLOT + 1024 * wave);
 #pragma unroll
-                for (int i = 0; i < G::SP; ++i) ring_dma_1k(src + 3072 * i, lane_off, dst + 3072u * (unsigned)i);
+                for (int i = 0; i < G::SP; ++i) dma_1k(src + 3072 * i, lane_off, dst + 3072u * (unsigned)i);
             }
             dma_slot = dma_slot + 1 == G::SLOTS_PER_TILE ? 0 : dma_slot + 1;
             ring_pos_w = ring_pos_w + 1 == G::RSLOTS ? 0 : ring_pos_w + 1;
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
         static_assert((G::RSLOTS * G::SLOT) % 1024 == 0, "whole DMA blocks");
         const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_ring;
         for (int blk = __builtin_amdgcn_readfirstlane(tid >> 6); blk < G::RSLOTS * G::SLOT / 1024; blk += G::WAVES)
-            ring_dma_1k(w.ring_img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
+            dma_1k(w.ring_img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     } else {
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
                 constexpr int q = decltype(q_)::value;
                 if constexpr (q < 2 * G::K1) {
 #pragma unroll
-                    for (int ft = 0; ft < G::FT; ++ft) hx[ft][q / G::K1] = ring_mfma6(fr, ap[ft][q % G::K1], hx[ft][q / G::K1]);
+                    for (int ft = 0; ft < G::FT; ++ft) hx[ft][q / G::K1] = mfma6(fr, ap[ft][q % G::K1], hx[ft][q / G::K1]);
                     if constexpr (q == 2 * G::K1 - 1) {
                         // snake + GRN (normaliser 1) on the accumulator registers (layers.py:29-33, :112-115), then the planes
 #pragma unroll
@@ -298,10 +294,10 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
                 } else {
                     constexpr int rt = q - 2 * G::K1;
 #pragma unroll
-                    for (int ft = 0; ft < G::FT; ++ft) yacc[ft][rt] = ring_mfma6(fr, hb[ft], yacc[ft][rt]);
+                    for (int ft = 0; ft < G::FT; ++ft) yacc[ft][rt] = mfma6(fr, hb[ft], yacc[ft][rt]);
                 }
             };
-            ring_static_for<G::PP>([&](auto q_) {
+            static_for<G::PP>([&](auto q_) {
                 constexpr int q = decltype(q_)::value;
                 if constexpr (G::PRE) {
                     bf16x8 fnext[3];
@@ -364,10 +360,7 @@ __global__ __launch_bounds__(64 * G::WAVES, G::WAVES * G::PER_CU / 4) void conv_
 template <class G, int C>
 int launch_ring(hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames, const char* name) {
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_unit_ring_kernel<G, C>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{conv_unit_ring_kernel<G, C>, G::LDS}}));
     const int tiles_per_clip = (frames + G::TF - 1) / G::TF;
     const int64_t tiles = (int64_t)batch * tiles_per_clip;
     L3AC_REQUIRE(tiles < ((int64_t)1 << 31) - 65536, "conv_unit_ring: too many tiles");

@@ -20,6 +20,7 @@
 // fp32 kernel (C = 96: 27.6 k vs 73.7 k).
 #include "../kernels.hpp"
 #include "../network.hpp"
+#include "conv_unit_front32.hpp"
 #include "device_math.hpp"
 #include "lane_sums.hpp"
 #include "split_bf16.hpp"
@@ -29,16 +30,12 @@
 namespace {
 
 template <int C, int HC, int XH>
-struct SGeo {
-    static constexpr int H4 = 4 * C;
+struct SplitGeo : Front32Geo<C, XH> {
+    using F = Front32Geo<C, XH>;
+    static constexpr int H4 = F::H4, CT = F::CT;
     static constexpr int NCH = H4 / HC;        // weight chunks (1 = resident)
     static constexpr int NTC = HC / 32;        // hidden tiles per chunk
-    static constexpr int CT = (C + 31) / 32;   // output-channel tiles
-    static constexpr int KQ = C / 8;
     static constexpr int NS1 = (C + 15) / 16;  // k steps of the first product
-    static constexpr int XC = C / XH;
-    static constexpr int XS = XC + 4;
-    static constexpr int ROWS = 38;
     // image geometry, bytes per hidden tile
     static constexpr int W1_TILE = NS1 * 3 * 1024;
     static constexpr int W2_TILE = 192 * C;    // sum over output tiles of 2 steps x 3 planes x 2 halves x rows x 16 B
@@ -52,17 +49,14 @@ struct SGeo {
     static constexpr int OFF_B2 = OFF_B1 + H4;
     static constexpr int OFF_DW = OFF_B2 + 32 * CT;           // dw_w [7][C], dw_b, ln_w, ln_b
     static constexpr int OFF_XS = OFF_DW + 10 * C;
-    static constexpr int xs_floats = ROWS * XS;
-    static constexpr int lds_floats(int waves) { return OFF_XS + waves * xs_floats; }
-    static_assert(H4 % HC == 0 && HC % 32 == 0 && C % (8 * XH) == 0 && WBUF % 16 == 0, "bad geometry");
+    static constexpr int lds_floats(int waves) { return OFF_XS + waves * F::xs_floats; }
+    static_assert(H4 % HC == 0 && HC % 32 == 0 && WBUF % 16 == 0, "bad geometry");
 };
-
-__device__ __forceinline__ int rowmap(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int C, int WAVES, int HC, int XH>
 __global__ __launch_bounds__(64 * WAVES, 2) void conv_unit_split_kernel(const ConvUnitW w, const float* __restrict__ x,
                                                                     float* __restrict__ y, int batch, int frames) {
-    using G = SGeo<C, HC, XH>;
+    using G = SplitGeo<C, HC, XH>;
     constexpr bool RESIDENT = G::NCH == 1;
     constexpr int THREADS = 64 * WAVES;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_unit_split_kernel(const Co
 #pragma unroll
         for (int ct = 0; ct < G::CT; ++ct)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) yacc[ct][r] = B2s[32 * ct + rowmap(r, lh)];
+            for (int r = 0; r < 16; ++r) yacc[ct][r] = B2s[32 * ct + split_rowmap(r, lh)];
 
 #pragma unroll 1
         for (int chunk = 0; chunk < G::NCH; ++chunk) {
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_unit_split_kernel(const Co
             auto first_product = [&](int ntl) __attribute__((always_inline)) -> f32x16_t {
                 f32x16_t acc;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = B1s[n_base + 32 * ntl + rowmap(r, lh)];
+                for (int r = 0; r < 16; ++r) acc[r] = B1s[n_base + 32 * ntl + split_rowmap(r, lh)];
                 const unsigned char* w1p = wb + ntl * G::W1_TILE + w1_lane;
 #pragma unroll
                 for (int s = 0; s < G::NS1; ++s) {
@@ -299,7 +293,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_unit_split_kernel(const Co
                 // snake + GRN (normaliser == 1) on the accumulator registers (layers.py:29-33, :112-115)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    const float* pp = Ps + n_base + 32 * ntl + rowmap(r, lh);
+                    const float* pp = Ps + n_base + 32 * ntl + split_rowmap(r, lh);
                     const f32x2 al = *reinterpret_cast<const f32x2*>(pp);
                     const f32x2 ia = *reinterpret_cast<const f32x2*>(pp + G::H4);
                     const f32x2 ga = *reinterpret_cast<const f32x2*>(pp + 2 * G::H4);
@@ -360,15 +354,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_unit_split_kernel(const Co
 
 template <int C, int WAVES, int HC, int XH>
 int launch_split(hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames, const char* name) {
-    using G = SGeo<C, HC, XH>;
+    using G = SplitGeo<C, HC, XH>;
     const size_t lds = (size_t)G::lds_floats(WAVES) * sizeof(float);
     static_assert(G::lds_floats(WAVES) * sizeof(float) <= 160 * 1024, "LDS budget exceeded");
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_unit_split_kernel<C, WAVES, HC, XH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{conv_unit_split_kernel<C, WAVES, HC, XH>, lds}}));
     const int64_t tiles = (int64_t)batch * ((frames + 31) / 32);
     L3AC_REQUIRE(tiles < ((int64_t)1 << 31) - 65536, "conv_unit_split: too many tiles");
     const int per_cu = lds > 80 * 1024 ? 1 : 2;

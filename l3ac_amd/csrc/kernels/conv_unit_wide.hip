@@ -93,60 +93,6 @@ struct WGeo {
 };
 
 
-__device__ __forceinline__ int rowmap(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-// this wave's quarter of one ring slot: N 1-KB LDS-DMA pieces, lane l copying 16 B from base + 16 l + 1024 i to lds_dst + 16 l + 1024 i.
-// One statement = one M0 write for all pieces (the instruction offset is added to the global AND the LDS address; both are
-// passed pre-biased by +3072 when N = 6 so that the offsets fit the signed 13-bit field), a wave-uniform 64-bit base in SGPRs
-// and one loop-invariant 32-bit lane offset: no vector address arithmetic per piece (guide 5.7: M0 is written in the statement
-// that uses it; the copies are invisible to hipcc's s_waitcnt bookkeeping and are counted by hand).
-// NT: non-temporal policy on the copies (aux = nt).  For a stream that ONE workgroup per XCD or so reads once from beyond L2 (the
-// half-tile form: a single clip) the copies land sooner (guide, price list 'nt-weights'); never for the batch form, whose 256
-// workgroups re-read the image from L2 in step.
-template <int N, bool NT = false>
-__device__ __forceinline__ void dma_slot_quarter(const unsigned char* base, unsigned lane_off, unsigned lds_dst) {
-    static_assert(N == 3 || N == 6, "3 KB or 6 KB per wave");
-    unsigned keep;
-#define L3AC_DMA3(POL)                                                     \
-    asm volatile(                                                          \
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"             \
-        "global_load_lds_dwordx4 %1, %2" POL "\n\t"                        \
-        "global_load_lds_dwordx4 %1, %2 offset:1024" POL "\n\t"            \
-        "global_load_lds_dwordx4 %1, %2 offset:2048" POL "\n\t"            \
-        "s_mov_b32 m0, %0"                                                 \
-        : "=&s"(keep)                                                      \
-        : "v"(lane_off), "s"(base), "s"(lds_dst)                           \
-        : "memory")
-#define L3AC_DMA6(POL)                                                     \
-    asm volatile(                                                          \
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"             \
-        "global_load_lds_dwordx4 %1, %2 offset:-3072" POL "\n\t"           \
-        "global_load_lds_dwordx4 %1, %2 offset:-2048" POL "\n\t"           \
-        "global_load_lds_dwordx4 %1, %2 offset:-1024" POL "\n\t"           \
-        "global_load_lds_dwordx4 %1, %2" POL "\n\t"                        \
-        "global_load_lds_dwordx4 %1, %2 offset:1024" POL "\n\t"            \
-        "global_load_lds_dwordx4 %1, %2 offset:2048" POL "\n\t"            \
-        "s_mov_b32 m0, %0"                                                 \
-        : "=&s"(keep)                                                      \
-        : "v"(lane_off), "s"(base + 3072), "s"(lds_dst + 3072u)            \
-        : "memory")
-    if constexpr (N == 3) {
-        if constexpr (NT) L3AC_DMA3(" nt"); else L3AC_DMA3("");
-    } else {
-        if constexpr (NT) L3AC_DMA6(" nt"); else L3AC_DMA6("");
-    }
-#undef L3AC_DMA3
-#undef L3AC_DMA6
-}
-
-template <int N, class F, int I = 0>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, F, I + 1>(static_cast<F&&>(f));
-    }
-}
-
 // ---- the activation of one PAIR of hidden rows (two elements per lane), cut into stages of at most three single-issue vector
 // instructions so that the kernel can place them one by one into the gaps behind its MFMAs (one wave per SIMD: ~5
 // single-issue instructions hide behind a 32-cycle MFMA; packed-fp32 instructions are an anti-lever there — guide,
@@ -164,13 +110,12 @@ constexpr int ACT_STAGES = 27;
 // beta'); h0/h1: the pair's pre-activations; out0..2: the pair's packed bf16 planes
 template <int T>
 __device__ __forceinline__ void act_stage(ActPair& a, const float* tab, float h0, float h1, unsigned& out0, unsigned& out1, unsigned& out2) {
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define L3AC_BOTH(expr) _Pragma("unroll") for (int e = 0; e < 2; ++e) { expr; }
     if constexpr (T == 0) {
-        const f32x4v v = *reinterpret_cast<const f32x4v*>(tab);
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(tab);
         a.al[0] = v.x, a.al[1] = v.y, a.ia[0] = v.z, a.ia[1] = v.w;
     } else if constexpr (T == 1) {
-        const f32x4v v = *reinterpret_cast<const f32x4v*>(tab + 4);
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(tab + 4);
         a.ga[0] = v.x, a.ga[1] = v.y, a.be[0] = v.z, a.be[1] = v.w;
     } else if constexpr (T == 2) {
         a.h[0] = h0, a.h[1] = h1;
@@ -233,15 +178,6 @@ __device__ __forceinline__ void act_stage(ActPair& a, const float* tab, float h0
         out2 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
     }
 #undef L3AC_BOTH
-}
-
-// one of the six plane products of a fragment pair, in mfma_split's order (split_bf16.hpp), on v_mfma_f32_16x16x32_bf16: D[16 x 16]
-// += A[16 x 32] B[32 x 16]; A: lane (row = lane & 15, k group = lane >> 4) holds 8 k values; B: lane (column = lane & 15, k group);
-// D: lane (column = lane & 15), registers = rows 4 (lane >> 4) .. + 3.  (Why this shape: DESIGN.md 3.1, 'MFMA shape'.)
-template <int M>
-__device__ __forceinline__ f32x4_t mfma_plane(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4_t acc) {
-    constexpr int IA[6] = {2, 1, 0, 1, 0, 0}, IB[6] = {0, 1, 2, 0, 1, 0};
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[IA[M]], b[IB[M]], acc, 0, 0, 0);
 }
 
 // The front end inside the main kernel (WGeo::FRONT): LayerNorm(dw_conv7(x)) of this wave's frames, computed directly in the B-operand
@@ -721,9 +657,8 @@ __global__ __launch_bounds__(256, WGeo<C>::WG_PER_CU) void conv_unit_wide_kernel
                 const int64_t rr = row0 + 8 * i + er;
                 const bool ok = tile_ok && rr < rows;
                 {
-                    typedef float f4nt __attribute__((ext_vector_type(4)));
-                    const f4nt* q = reinterpret_cast<const f4nt*>(x + (ok ? rr : 0) * C + 32 * ct + 4 * es);
-                    const f4nt v = __builtin_nontemporal_load(q);
+                    const f32x4_t* q = reinterpret_cast<const f32x4_t*>(x + (ok ? rr : 0) * C + 32 * ct + 4 * es);
+                    const f32x4_t v = __builtin_nontemporal_load(q);
                     xres[ct][i] = make_float4(v.x, v.y, v.z, v.w);
                 }
             }
@@ -774,9 +709,8 @@ __global__ __launch_bounds__(256, WGeo<C>::WG_PER_CU) void conv_unit_wide_kernel
                     const int64_t rr = row0 + r;
                     const float4 v = *reinterpret_cast<const float4*>(tb + 128 * r + 16 * (es ^ ((r ^ (r >> 3)) & 7)));
                     if (tile_ok && rr < rows) {
-                        typedef float f4nt __attribute__((ext_vector_type(4)));
-                        const f4nt o = {xres[ct][i].x + v.x, xres[ct][i].y + v.y, xres[ct][i].z + v.z, xres[ct][i].w + v.w};
-                        __builtin_nontemporal_store(o, reinterpret_cast<f4nt*>(y + rr * C + 32 * ct + 4 * es));
+                        const f32x4_t o = {xres[ct][i].x + v.x, xres[ct][i].y + v.y, xres[ct][i].z + v.z, xres[ct][i].w + v.w};
+                        __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t*>(y + rr * C + 32 * ct + 4 * es));
                     }
                 }
             }
@@ -1123,17 +1057,10 @@ template <int C>
 int launch_wide(hipStream_t s, const ConvUnitW& w, const float* x, float* y, unsigned char* planes, int64_t rows, int frames, int sliced_mode, int* counters) {
     using G = WGeo<C>;
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_unit_wide_kernel<C, 2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_unit_wide_kernel<C, 1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wide_sliced_hidden_kernel<C>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SGeo<C>::LDS1));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wide_sliced_out_kernel<C>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SGeo<C>::LDS2));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{conv_unit_wide_kernel<C, 2>, G::LDS},
+                                            {conv_unit_wide_kernel<C, 1>, G::LDS},
+                                            {wide_sliced_hidden_kernel<C>, SGeo<C>::LDS1},
+                                            {wide_sliced_out_kernel<C>, SGeo<C>::LDS2}}));
     char name[64];
     const int64_t tiles16 = ceil_div64(rows, 16);
     const bool sliced = sliced_exists(C, rows) && (sliced_mode == 2 || (sliced_mode == 1 && tiles16 <= SLICED_AUTO_TILES));

@@ -18,6 +18,7 @@
 
 #include "../kernels.hpp"
 #include "lane_sums.hpp"
+#include "split_bf16.hpp"
 
 namespace {
 
@@ -34,7 +35,6 @@ __device__ __forceinline__ float vq_min(float a, float b) {
 
 constexpr int THREADS = 256;
 constexpr int MAXD = L3AC_MAX_LEVELS;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct FsqDev {
     const float* x;
@@ -57,13 +57,12 @@ struct FsqDev {
 };
 
 // streamed once: non-temporal accesses keep the rows out of the way of L2 / MALL residents
-typedef float f32x4_nt __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 nt_load4(const float* p) {
-    const f32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
+    const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void nt_store4(float* p, const float4& v) {
-    __builtin_nontemporal_store(f32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_nt*>(p));
+    __builtin_nontemporal_store(f32x4_t{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_t*>(p));
 }
 
 // Every mode: forward, quantise-from-activations, decode-from-indices, latents in / out; any feat = 8 * 2^j.
@@ -836,7 +835,7 @@ __global__ __launch_bounds__(256) void vq_screen_kernel(const float* __restrict_
     fetch(t_begin);
     for (int t = t_begin; t < t_end; ++t) {
         float a[KS];
-        f32x16 cn;  // accumulator register r of lane (col, h) is code row 8 (r / 4) + 4 h + r % 4 of the tile
+        f32x16_t cn;  // accumulator register r of lane (col, h) is code row 8 (r / 4) + 4 h + r % 4 of the tile
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[s] = a_nx[s];
 #pragma unroll
@@ -848,7 +847,7 @@ __global__ __launch_bounds__(256) void vq_screen_kernel(const float* __restrict_
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
-            f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], bq[j][0], cn, 0, 0, 0);
+            f32x16_t acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], bq[j][0], cn, 0, 0, 0);
 #pragma unroll
             for (int s = 1; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], bq[j][s], acc, 0, 0, 0);
             // (minimumNumber is the hardware's v_min / v_min3 as it stands: fminf would first quiet every operand with a v_max)

@@ -4,12 +4,12 @@
 
 #include "../kernels.hpp"
 #include "device_math.hpp"
+#include "split_bf16.hpp"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- epilogue: lane holds column n = n0 + 32 nt + li, rows m0 + 32 wave + (r&3) + 8 (r>>2) + 4 lh ----
 template <int NT>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[NT], int64_t m0, int n0, int wave, int li, int lh) {
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16_t (&acc)[NT], int64_t m0, int n0, int wave, int li, int lh) {
     const int64_t mw = m0 + 32 * wave + 4 * lh;
     if (p.epi == EPI_GEGLU) {
         // column tiles come in (value, gate) pairs; output column j = n0/2 + 32 (nt/2) + li

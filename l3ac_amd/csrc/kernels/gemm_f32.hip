@@ -172,7 +172,7 @@ __global__ __launch_bounds__(THREADS, BK == 16 ? 3 : 2) void gemm_f32_kernel(con
             if (r0 + RP * i < BN) *reinterpret_cast<float4*>(ws + lds_off<BK>(r0 + RP * i, cc)) = w_reg[i];
     };
 
-    f32x16 acc[NT];
+    f32x16_t acc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -223,7 +223,6 @@ __global__ __launch_bounds__(THREADS, BK == 16 ? 3 : 2) void gemm_f32_kernel(con
 // through four register sets (nothing else covers a fetch with one wave per SIMD), the same LDS tiles and swizzle as above.  The k
 // sequence of the kernel above is kept — inside a group of 8: 0, 4, 1, 5, 2, 6, 3, 7 — by giving lane group g of instruction j the
 // element k = 8 q + 4 (g & 1) + (g >> 1) + 2 j of the 16 B it reads: same bits (tested against the large-grid form).
-typedef float f32x4acc __attribute__((ext_vector_type(4)));
 template <int NT, bool CONV, bool FULLK>
 __global__ __launch_bounds__(THREADS, 1) void gemm_f32_small_kernel(const GemmArgs p) {
     constexpr int BK = 32, BMS = 64, BN = 32 * NT, D = 4;
@@ -310,9 +309,9 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_f32_small_kernel(const GemmAr
         for (int i = 0; i < WP; ++i)
             if (r0 + RP * i < BN) *reinterpret_cast<float4*>(ws + lds_off<BK>(r0 + RP * i, cc)) = w_reg[i];
     };
-    f32x4acc acc[2 * NT];
+    f32x4_t acc[2 * NT];
 #pragma unroll
-    for (int i = 0; i < 2 * NT; ++i) acc[i] = f32x4acc{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 2 * NT; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const int li = lane & 15, lg = lane >> 4;
     const int lh = lg & 1;         // which 16-B half of a group of 8 this lane reads
     const bool odd = (lg >> 1) != 0;  // elements 1, 3 of it (else 0, 2)

@@ -160,11 +160,11 @@ __device__ __forceinline__ void gemm_split_body16(const GemmArgs& p, const int g
         for (int pl = 2; pl >= 0; --pl) b[pl] = *reinterpret_cast<const bf16x8*>(ws + pl * W_PLANE + tile_off(16 * t + ln, lg));
     };
 
-    f32x4a acc[RG][8];
+    f32x4_t acc[RG][8];
 #pragma unroll
     for (int h = 0; h < RG; ++h)
 #pragma unroll
-        for (int t = 0; t < 8; ++t) acc[h][t] = f32x4a{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 8; ++t) acc[h][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     load_a(0, a_pre[0]);
     load_a(last < 1 ? last : 1, a_pre[1]);
@@ -209,7 +209,6 @@ __device__ __forceinline__ void gemm_split_body16(const GemmArgs& p, const int g
             bf16x8 bq[2 * UT][3];
 #pragma unroll
             for (int u = 0; u < UT; ++u) read_b(ws, u, bq[u]);
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
             for (int t = 0; t < 8; t += UT) {
                 const int cur = (t / UT) & 1;
@@ -222,9 +221,7 @@ __device__ __forceinline__ void gemm_split_body16(const GemmArgs& p, const int g
 #pragma unroll
                     for (int u = 0; u < UT; ++u)
 #pragma unroll
-                        for (int h = 0; h < RG; ++h)
-                            acc[h][t + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[h][PA[q]]),
-                                                                                   bq[UT * cur + u][PB[q]], acc[h][t + u], 0, 0, 0);
+                        for (int h = 0; h < RG; ++h) acc[h][t + u] = mfma_plane(q, af[h], bq[UT * cur + u], acc[h][t + u]);
                 if (t + UT == 4) store_w(buf ^ 1, Next{});
             }
         } else {
@@ -233,18 +230,13 @@ __device__ __forceinline__ void gemm_split_body16(const GemmArgs& p, const int g
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             if (t + 1 < 8) read_b(ws, t + 1, bq[(t + 1) & 1]);
-            const bf16x8 b0 = bq[t & 1][0], b1 = bq[t & 1][1], b2 = bq[t & 1][2];
+            // (the planes as values and the six products as straight-line code: mfma6 on the arrays in place is the same arithmetic, but
+            // hipcc then allocates this loop's registers differently)
+            const bf16x8 b[3] = {bq[t & 1][0], bq[t & 1][1], bq[t & 1][2]};
 #pragma unroll
             for (int h = 0; h < RG; ++h) {
-                const bf16x8 a0 = __builtin_bit_cast(bf16x8, af[h][0]);
-                const bf16x8 a1 = __builtin_bit_cast(bf16x8, af[h][1]);
-                const bf16x8 a2 = __builtin_bit_cast(bf16x8, af[h][2]);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0, acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2, acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[h][t], 0, 0, 0);
+                const bf16x8 a[3] = {__builtin_bit_cast(bf16x8, af[h][0]), __builtin_bit_cast(bf16x8, af[h][1]), __builtin_bit_cast(bf16x8, af[h][2])};
+                static_for<6>([&](auto q_) __attribute__((always_inline)) { acc[h][t] = mfma_plane<decltype(q_)::value>(a, b, acc[h][t]); });
             }
             if (t == 3) store_w(buf ^ 1, Next{});
         }
@@ -271,7 +263,7 @@ __device__ __forceinline__ void gemm_split_body16(const GemmArgs& p, const int g
             // computed behind the loop; hoisted above it those values cost the 168-register loop 29 spilled registers: 1.56 -> 2.27 ms)
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));
-            epilogue_rows<RG, 2>(p, [&](int sq, int h, int tt) __attribute__((always_inline)) -> f32x4a& { return acc[h][4 * sq + tt]; }, m0, n0, wave, lane_e,
+            epilogue_rows<RG, 2>(p, [&](int sq, int h, int tt) __attribute__((always_inline)) -> f32x4_t& { return acc[h][4 * sq + tt]; }, m0, n0, wave, lane_e,
                                  reinterpret_cast<float*>(smem_split + 12288 * wave));
             return;
         }
@@ -332,7 +324,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel_slices(const Gem
 #pragma unroll
         for (int pl = 2; pl >= 0; --pl) b[pl] = *reinterpret_cast<const bf16x8*>(ws + pl * W_PLANE + tile_off(16 * t + ln, lg));
     };
-    f32x4a acc[1][2] = {{f32x4a{0.f, 0.f, 0.f, 0.f}, f32x4a{0.f, 0.f, 0.f, 0.f}}};
+    f32x4_t acc[1][2] = {{f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}}};
 #pragma unroll
     for (int j = 0; j < AHEAD; ++j) {
         load_a(j < last ? j : last, a_pre[j]);
@@ -365,12 +357,10 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel_slices(const Gem
         bf16x8 bq[2][3];
         read_b(ws, 2 * c, bq[0]);
         read_b(ws, 2 * c + 1, bq[1]);
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
-                acc[0][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[PA[q]]), bq[u][PB[q]], acc[0][u], 0, 0, 0);
+            for (int u = 0; u < 2; ++u) acc[0][u] = mfma_plane(q, af, bq[u], acc[0][u]);
         __syncthreads();
     };
     for (int kt = 0; kt < n_tiles; kt += AHEAD) {
@@ -391,16 +381,6 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel_slices(const Gem
 // swizzle only depends on row / 4 mod 4).  PF = 7 or 8 slots stay in flight behind counted waits (four copies per wave and slot), the
 // fragments of tile kt + 1 are read while tile kt multiplies.  Same k order, same six plane products per accumulator in the same order
 // as every other form of this GEMM: same bits.
-__device__ __forceinline__ void dma_1k(const unsigned char* base, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(lane_off), "s"(base), "s"(lds_dst)
-        : "memory");
-}
 constexpr int ST_SLOT = 16384, ST_RING = 9;  // A 4 KB | W plane 0 | plane 1 | plane 2 (4 KB each: 64 rows x 64 B)
 // CONV (three taps): the A rows of k tile kt are those of frame t + (tap - 1) dil, tap = kt / (cin / 32).  A copy cannot write zeros, so
 // the copying lane fetches a CLAMPED row (any valid address) and the multiplying wave zeroes the fragment of a frame whose tap falls outside
@@ -504,7 +484,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream(const Gem
             for (int pl = 2; pl >= 0; --pl)
                 fw[P][u][pl] = *reinterpret_cast<const bf16x8*>(slot + 4096 + pl * 4096 + tile_off(32 * cg + 16 * u + ln, lg));
     };
-    f32x4a acc[1][2] = {{f32x4a{0.f, 0.f, 0.f, 0.f}, f32x4a{0.f, 0.f, 0.f, 0.f}}};
+    f32x4_t acc[1][2] = {{f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}}};
     auto multiply = [&](auto par_) __attribute__((always_inline)) {
         constexpr int P = decltype(par_)::value;
         unsigned x0, x1, x2, y0, y1, y2, z0, z1, z2, u0, u1, u2;
@@ -513,12 +493,10 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream(const Gem
         split2(fa[P][1].x, fa[P][1].y, z0, z1, z2);
         split2(fa[P][1].z, fa[P][1].w, u0, u1, u2);
         const u32x4 af[3] = {u32x4{x0, y0, z0, u0}, u32x4{x1, y1, z1, u1}, u32x4{x2, y2, z2, u2}};
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
-                acc[0][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[PA[q]]), fw[P][u][PB[q]], acc[0][u], 0, 0, 0);
+            for (int u = 0; u < 2; ++u) acc[0][u] = mfma_plane(q, af, fw[P][u], acc[0][u]);
     };
     // this wave's copies of slot kt have landed when at most 4 x `after` newer ones are outstanding; then everybody's have, and
     // everybody's reads of the slot before it are complete (its ring position is the next one to be overwritten)
@@ -545,7 +523,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream(const Gem
         multiply(P1{});
     }
     // the last PF tiles: nothing left to request, the counted waits shrink
-    tail_for<PF>([&](auto j_) __attribute__((always_inline)) {
+    static_for<PF>([&](auto j_) __attribute__((always_inline)) {
         constexpr int J = decltype(j_)::value;
         if constexpr (J + 1 < PF) {
             landed(std::integral_constant<int, PF - 2 - J>{});
@@ -593,7 +571,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream_narrow(co
         dma_1k(gw + W_PLANE, 16u * (unsigned)lane, dst + 5120);
         dma_1k(gw + 2 * W_PLANE, 16u * (unsigned)lane, dst + 6144);
     };
-    f32x4a acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     auto multiply = [&](int q) __attribute__((always_inline)) {
         if (wave >= 2) return;
         const unsigned char* slot = smem_split + (q % SN_RING) * SN_SLOT;
@@ -611,9 +589,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream_narrow(co
             split2(f1.x, f1.y, z0, z1, z2);
             split2(f1.z, f1.w, u0, u1, u2);
             const u32x4 af[3] = {u32x4{x0, y0, z0, u0}, u32x4{x1, y1, z1, u1}, u32x4{x2, y2, z2, u2}};
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-            for (int m = 0; m < 6; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[PA[m]]), fw[PB[m]], acc, 0, 0, 0);
+            acc = mfma6(af, fw, acc);
         }
     };
     // slot q has landed for this wave when at most 7 x `after` newer copies are outstanding; then for everybody — and everybody's
@@ -631,7 +607,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_stream_narrow(co
         issue(q + SN_PF);
         multiply(q);
     }
-    tail_for<SN_PF>([&](auto j_) __attribute__((always_inline)) {
+    static_for<SN_PF>([&](auto j_) __attribute__((always_inline)) {
         constexpr int J = decltype(j_)::value;
         landed(std::integral_constant<int, SN_PF - 1 - J>{});
         multiply(main_steps + J);
@@ -741,11 +717,8 @@ int launch_gemm_split(hipStream_t s, const GemmArgs& g) {
     if (conv && g.taps == 3 && g.k / BK >= 8 && g.lda * g.m < ((int64_t)1 << 29) && ceil_div64(g.m, BM / 2) * ceil_div64(g.n, BN) <= cus / 4) {
         // a single clip's k3 conv: the streamed form (32 x 64 blocks), its A rows by tap
         static PerDeviceOnce configured;
-        if (configured.first()) {
-            L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_stream<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_RING * ST_SLOT));
-            L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_stream<7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_RING * ST_SLOT));
-            configured.done();
-        }
+        L3AC_TRY(raise_dynamic_lds(configured, {{gemm_split_kernel_stream<8, true>, ST_RING * ST_SLOT},
+                                                {gemm_split_kernel_stream<7, true>, ST_RING * ST_SLOT}}));
         const unsigned grid = (unsigned)(ceil_div64(g.m, 32) * ceil_div64(g.n, 64));
         if ((g.k / BK) % 2 == 0)
             hipLaunchKernelGGL((gemm_split_kernel_stream<8, true>), dim3(grid), dim3(THREADS), ST_RING * ST_SLOT, s, g);
@@ -760,12 +733,9 @@ int launch_gemm_split(hipStream_t s, const GemmArgs& g) {
     } else if (g.epi != EPI_GEGLU && !tail && g.k / BK >= 8 && g.lda * g.m < ((int64_t)1 << 29) && ceil_div64(g.m, BM / 2) * ceil_div64(g.n, BN) <= cus / 4) {
         // a single clip, whole k tiles: the streamed form (32 rows x 64 columns per block); PF of the same parity as the k tiles
         static PerDeviceOnce configured;
-        if (configured.first()) {
-            L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_stream<8>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_RING * ST_SLOT));
-            L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_stream<7>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_RING * ST_SLOT));
-            L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_stream_narrow), hipFuncAttributeMaxDynamicSharedMemorySize, SN_RING * SN_SLOT));
-            configured.done();
-        }
+        L3AC_TRY(raise_dynamic_lds(configured, {{gemm_split_kernel_stream<8>, ST_RING * ST_SLOT},
+                                                {gemm_split_kernel_stream<7>, ST_RING * ST_SLOT},
+                                                {gemm_split_kernel_stream_narrow, SN_RING * SN_SLOT}}));
         const unsigned grid = (unsigned)(ceil_div64(g.m, 32) * ceil_div64(g.n, 64));
         if ((g.epi == EPI_BIAS || g.epi == EPI_BIAS_RES) && g.k % (4 * BK) == 0 && g.k / (4 * BK) >= SN_PF && 2 * grid <= (unsigned)cus)
             hipLaunchKernelGGL(gemm_split_kernel_stream_narrow, dim3((unsigned)(ceil_div64(g.m, 32) * ceil_div64(g.n, 16))), dim3(THREADS), SN_RING * SN_SLOT, s, g);

@@ -1,5 +1,5 @@
 // Pieces shared by the bf16x3 GEMM kernels (gemm_split.hip, gemm_split_w256.hip): tile geometry of the pre-split weight image, the
-// accumulator-layout epilogue of the 16x16x32 kernels, a compile-time loop.
+// accumulator-layout epilogue of the 16x16x32 kernels (the compile-time loop they use is split_bf16.hpp's static_for).
 #pragma once
 
 #include <type_traits>
@@ -26,7 +26,6 @@ static_assert(W_TILE == L3AC_SPLIT_TILE_BYTES, "image geometry");
 //     any bijective sigma is conflict-free.
 __host__ __device__ __forceinline__ int tile_off(int row, int chunk) { return row * 64 + ((chunk ^ ((0 - (row >> 2)) & 3)) << 4); }
 
-typedef float f32x4a __attribute__((ext_vector_type(4)));
 // The bf16x3 GEMMs' output stores are non-temporal (bias / residual / snake epilogues): the streamed-out C tile does not
 // push the A panel and the W tiles, which the column blocks of the same XCD re-read, out of L2.  Measured (profiles/r04/wide_nt.md):
 // the step's 14 launches 3.05-3.07 -> 2.99 ms in both of two interleaved rounds (the consumer of the hidden tensor included).
@@ -40,7 +39,7 @@ __device__ __forceinline__ void c_store(float* p, float v) { __builtin_nontempor
 // i.e. whole 128-B lines per half wave, and the lane's column (hence its bias / snake / GRN parameters) is 32 u + (lane & 31) for both.
 // NT column tiles of 16 (8: the whole 128-column block; 2: one 32-column slice, n0 = its first column — not with EPI_GEGLU)
 template <int RG, int NT = 8>
-__device__ __forceinline__ void gemm_epilogue16(const GemmArgs& p, f32x4a (&acc)[RG][NT], int64_t m0, int n0, int wave, int lane) {
+__device__ __forceinline__ void gemm_epilogue16(const GemmArgs& p, f32x4_t (&acc)[RG][NT], int64_t m0, int n0, int wave, int lane) {
     const int c32 = lane & 31, hi = lane >> 5;
     const int64_t mw = m0 + 16 * RG * wave + 8 * hi;  // + 16 h + i (first result), + 16 h + 4 + i (second)
     // (inline asm: with __builtin_amdgcn_permlane16_swap hipcc 7.2 folded the four swaps of a tile pair into one — every row of a
@@ -144,16 +143,15 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, AccAt&& acc_at,
         const int col = n0 + 64 * sq + 4 * eq;  // this lane's four columns of the quarter
         const bool col_ok = col < p.n;
         const int colc = col_ok ? col : 0;
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const f4 bias = p.bias ? *reinterpret_cast<const f4*>(p.bias + colc) : f4{0.f, 0.f, 0.f, 0.f};
-        f4 alpha = {0.f, 0.f, 0.f, 0.f}, inv_alpha = alpha, gamma = alpha, beta = alpha;
+        const f32x4_t bias = p.bias ? *reinterpret_cast<const f32x4_t*>(p.bias + colc) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+        f32x4_t alpha = {0.f, 0.f, 0.f, 0.f}, inv_alpha = alpha, gamma = alpha, beta = alpha;
         if (p.epi == EPI_SNAKE || p.epi == EPI_SNAKE_GRN) {
-            alpha = *reinterpret_cast<const f4*>(p.alpha + colc);
-            inv_alpha = *reinterpret_cast<const f4*>(p.inv_alpha + colc);
+            alpha = *reinterpret_cast<const f32x4_t*>(p.alpha + colc);
+            inv_alpha = *reinterpret_cast<const f32x4_t*>(p.inv_alpha + colc);
         }
         if (p.epi == EPI_SNAKE_GRN) {
-            gamma = *reinterpret_cast<const f4*>(p.gamma + colc);
-            beta = *reinterpret_cast<const f4*>(p.beta + colc);
+            gamma = *reinterpret_cast<const f32x4_t*>(p.gamma + colc);
+            beta = *reinterpret_cast<const f32x4_t*>(p.beta + colc);
         }
 #pragma unroll
         for (int h = 0; h < RG; ++h) {
@@ -165,7 +163,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, AccAt&& acc_at,
 #pragma unroll
             for (int jr = 0; jr < 4; ++jr) {
                 const int64_t m = mw + 16 * h + er + 4 * jr;
-                f4 v = *reinterpret_cast<const f4*>(sb + (er + 4 * jr) * 64 + 4 * eq);
+                f32x4_t v = *reinterpret_cast<const f32x4_t*>(sb + (er + 4 * jr) * 64 + 4 * eq);
                 if (m >= p.m || !col_ok) continue;
                 v = v + bias;
                 if (p.epi == EPI_SNAKE || p.epi == EPI_SNAKE_GRN) {
@@ -174,26 +172,18 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& p, AccAt&& acc_at,
                     if (p.epi == EPI_SNAKE_GRN) {  // layers.py:115, n_x == 1
                         const f32x2 o0 = __builtin_elementwise_fma(f32x2{gamma.x, gamma.y}, s0, f32x2{beta.x, beta.y}) + s0;
                         const f32x2 o1 = __builtin_elementwise_fma(f32x2{gamma.z, gamma.w}, s1, f32x2{beta.z, beta.w}) + s1;
-                        v = f4{o0.x, o0.y, o1.x, o1.y};
+                        v = f32x4_t{o0.x, o0.y, o1.x, o1.y};
                     } else {
-                        v = f4{s0.x, s0.y, s1.x, s1.y};
+                        v = f32x4_t{s0.x, s0.y, s1.x, s1.y};
                     }
                 } else if (p.epi == EPI_BIAS_RES) {
-                    v = *reinterpret_cast<const f4*>(p.res + m * p.ldres + col) + v;
+                    v = *reinterpret_cast<const f32x4_t*>(p.res + m * p.ldres + col) + v;
                 }
-                __builtin_nontemporal_store(v, reinterpret_cast<f4*>(p.c + m * p.ldc + col));
+                __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(p.c + m * p.ldc + col));
             }
         }
     }
 }
-}
-
-template <int N, class F, int I = 0>
-__device__ __forceinline__ void tail_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        tail_for<N, F, I + 1>(static_cast<F&&>(f));
-    }
 }
 
 }  // namespace

@@ -99,13 +99,13 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_w256(const GemmA
     u32x4 af[2][RG][3];
     u32x4 w_reg[W_LOADS];
     bf16x8 bq[2][3];
-    f32x4a acc[2][RG][8];  // [column half][row group][column tile of the half]
+    f32x4_t acc[2][RG][8];  // [column half][row group][column tile of the half]
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int h = 0; h < RG; ++h)
 #pragma unroll
-            for (int t = 0; t < 8; ++t) acc[c][h][t] = f32x4a{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 8; ++t) acc[c][h][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     auto load_a = [&](int kt, int h) __attribute__((always_inline)) {
         raw[h][0] = *reinterpret_cast<const float4*>(a_row[h] + kt * BK);
@@ -169,12 +169,10 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_w256(const GemmA
             };
             SplitPair sp[4];
             unsigned planes[3][4];
-            tail_for<GAPS>([&](auto g_) __attribute__((always_inline)) {
+            static_for<GAPS>([&](auto g_) __attribute__((always_inline)) {
                 constexpr int g = decltype(g_)::value, t = g / TG, r = g % TG, q = r / RG, h = r % RG, win = g / 3;
-                constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
                 if constexpr (g == BAR_GAP) lds_barrier();  // every wave's stores of W(kt + 1) are in LDS; every wave has read the last fragments of W(kt)
-                acc[t >> 3][h][t & 7] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][h][PA[q]]), bq[t & 1][PB[q]],
-                                                                                  acc[t >> 3][h][t & 7], 0, 0, 0);
+                acc[t >> 3][h][t & 7] = mfma_plane<q>(af[0][h], bq[t & 1], acc[t >> 3][h][t & 7]);
                 // fragments of the next column tile (the last tile: column tile 0 of k tile kt + 1, behind the barrier)
                 if constexpr (r % RG == 0 && r / RG < 3) {
                     constexpr int pl = 2 - r / RG;
@@ -232,7 +230,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_split_kernel_w256(const GemmA
         default: k_loop(std::integral_constant<int, 3>{}); break;
     }
     W256_STAMP(2);
-    epilogue_rows<RG, 4>(p, [&](int sq, int h, int tt) __attribute__((always_inline)) -> f32x4a& { return acc[sq >> 1][h][4 * (sq & 1) + tt]; }, m0, n0, wave, lane,
+    epilogue_rows<RG, 4>(p, [&](int sq, int h, int tt) __attribute__((always_inline)) -> f32x4_t& { return acc[sq >> 1][h][4 * (sq & 1) + tt]; }, m0, n0, wave, lane,
                          reinterpret_cast<float*>(smem_split + 2 * W_TILE + 12288 * wave));
     W256_STAMP(3);
 }
@@ -251,10 +249,7 @@ bool gemm_split_w256_ok(const GemmArgs& g) {
 int launch_gemm_split_w256(hipStream_t s, const GemmArgs& g) {
     L3AC_REQUIRE(gemm_split_w256_ok(g), "split gemm (256-column form): unsupported shape or alignment n=%d k=%d", g.n, g.k);
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel_w256<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * W_TILE));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{gemm_split_kernel_w256<3>, 4 * W_TILE}}));
     const int64_t panels = ceil_div64(g.m, 192);
     const int64_t grid = ceil_div64(panels, 8) * 8 * (g.n / 256);
     L3AC_REQUIRE(grid < (int64_t)1 << 31, "split gemm: grid too large (m=%lld n=%d)", (long long)g.m, g.n);

@@ -24,12 +24,10 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FRAMES = 256;  // frames per workgroup
 constexpr int WAVES = 8;
 
-__device__ __forceinline__ int rowmap(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int C>
 struct LGeo {
@@ -137,9 +135,9 @@ __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_kernel(const Legacy
         const float* Pt = Ps + woff;
         if (t0 + m0 < frames) {  // wave-uniform: a wave wholly beyond the clip only takes part in the barriers
             // ---- X[n][m] = b1[n] + sum_{tap,c} W1[n][tap*C + c] S[m + (tap - 3) dil][c] ----------------------
-            f32x16 xacc;
+            f32x16_t xacc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xacc[r] = Pt[4 * rowmap(r, lh) + 2];
+            for (int r = 0; r < 16; ++r) xacc[r] = Pt[4 * split_rowmap(r, lh) + 2];
             // C % 8 == 0: both halves of a k-group of 8 lie in the same tap, so the S address is one per-lane base
             // + a wave-uniform tap offset + an immediate
             const float* sl = Ss + (m0 + lj) * G::SS + 4 * lh;
@@ -158,11 +156,11 @@ __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_kernel(const Legacy
                 }
             }
             // ---- snake on the accumulator, then Y[c][m] = b2[c] + sum_n W2[c][n] X[n][m] -------------------
-            f32x16 yacc;
+            f32x16_t yacc;
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {  // packed fp32 math on adjacent hidden channels
-                const float4 p0 = *reinterpret_cast<const float4*>(Pt + 4 * rowmap(r, lh));
-                const float4 p1 = *reinterpret_cast<const float4*>(Pt + 4 * rowmap(r + 1, lh));
+                const float4 p0 = *reinterpret_cast<const float4*>(Pt + 4 * split_rowmap(r, lh));
+                const float4 p1 = *reinterpret_cast<const float4*>(Pt + 4 * split_rowmap(r + 1, lh));
                 f32x2 hv, al, ia;
                 hv.x = xacc[r]; hv.y = xacc[r + 1];
                 al.x = p0.x; al.y = p1.x;
@@ -234,18 +232,6 @@ struct LSGeo {
     static constexpr int lds_bytes(int dil) { return OFF_S + 3 * (FRAMES + 6 * dil) * PS; }
     static_assert(C % 8 == 0 && C <= 32 && W1_BYTES % 16 == 0, "geometry");
 };
-
-typedef float f32x4_l __attribute__((ext_vector_type(4)));
-// acc += a . b over one k step of 32, operands as their three planes, the six plane products in mfma_split's order
-__device__ __forceinline__ f32x4_l mfma_split16(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4_l acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
-    return acc;
-}
 
 template <int C>
 __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_split_kernel(const LegacyW w, const float* __restrict__ x,
@@ -358,10 +344,10 @@ __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_split_kernel(const 
         if (t0 + m0 < frames) {  // wave-uniform: a wave wholly beyond the clip only takes part in the barriers
             // ---- X^T[n][m] = b1[n] + sum_{tap,c} W1[n][tap][c] S[m + (tap - 3) dil][c] -------------------------
             // xt[hh][fh][i] = hidden row 16 hh + 4 lg + i at frame 16 fh + ln
-            f32x4_l xt[G::NHH][2];
+            f32x4_t xt[G::NHH][2];
 #pragma unroll
             for (int hh = 0; hh < G::NHH; ++hh) {
-                f32x4_l bv;
+                f32x4_t bv;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bv[i] = Pt[4 * (16 * hh + 4 * lg + i) + 2];
                 xt[hh][0] = bv;
@@ -390,13 +376,13 @@ __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_split_kernel(const 
 #pragma unroll
                 for (int hh = 0; hh < G::NHH; ++hh)
 #pragma unroll
-                    for (int fh = 0; fh < 2; ++fh) xt[hh][fh] = mfma_split16(wf[hh], sf[fh], xt[hh][fh]);
+                    for (int fh = 0; fh < 2; ++fh) xt[hh][fh] = mfma6(wf[hh], sf[fh], xt[hh][fh]);
             }
             // ---- snake on the accumulators, split them, then Y^T[c][m] = b2[c] + sum_n W2[c][n] X^T[n][m] -----------
             // the B operand of frame half fh: word 2 hh + ip = hidden rows 16 hh + 4 lg + 2 ip, + 1 (k order sigma(lg, j) = j < 4 ?
             // 4 lg + j : 16 + 4 lg + j - 4, which the W2 image is built in); a missing second tile contributes zeros
             unsigned xw[2][3][4];
-            f32x4_l yt[G::NHH][2];
+            f32x4_t yt[G::NHH][2];
 #pragma unroll
             for (int fh = 0; fh < 2; ++fh)
 #pragma unroll
@@ -435,7 +421,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void legacy_unit_split_kernel(const 
 #pragma unroll
                 for (int p = 0; p < 3; ++p) wf[p] = *reinterpret_cast<const bf16x8*>(W2t + G::off_of(rt, p) + wl[rt]);
 #pragma unroll
-                for (int fh = 0; fh < 2; ++fh) yt[rt][fh] = mfma_split16(wf, xb[fh], yt[rt][fh]);
+                for (int fh = 0; fh < 2; ++fh) yt[rt][fh] = mfma6(wf, xb[fh], yt[rt][fh]);
             }
             // ---- residual + store: lane (frame 16 fh + ln, row group lg) owns channels 16 rt + 4 lg + {0..3} ---------------
             // (round 6: the four residual pieces are requested together, from clamped addresses by every lane, and the stores are predicated —
@@ -532,13 +518,8 @@ int launch_legacy_t(hipStream_t s, const LegacyW& w, const float* x, float* y, i
     using GS = LSGeo<C>;
     const size_t lds = split ? (size_t)GS::lds_bytes(w.dil) : (size_t)G::lds_floats(w.dil) * sizeof(float);
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(legacy_unit_kernel<C>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::lds_floats(9) * sizeof(float))));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(legacy_unit_split_kernel<C>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GS::lds_bytes(9)));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{legacy_unit_kernel<C>, G::lds_floats(9) * sizeof(float)},
+                                            {legacy_unit_split_kernel<C>, GS::lds_bytes(9)}}));
     const double rows = (double)batch * frames;
     const int tiles_per_clip = (int)ceil_div64(frames, FRAMES);
     const int64_t total = (int64_t)tiles_per_clip * batch;

@@ -433,12 +433,7 @@ __global__ __launch_bounds__(LD_RANGE_THREADS) void loudness_range_kernel(int64_
 
 int configure_range_kernel() {
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(loudness_range_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           PAIR_MAX_FRAMES * 8));
-        configured.done();
-    }
-    return L3AC_OK;
+    return raise_dynamic_lds(configured, {{loudness_range_kernel, PAIR_MAX_FRAMES * 8}});
 }
 
 // what the series and the range share with l3ac_loudness: the checks, the staged lengths, the design, phases 1 to 3

@@ -273,11 +273,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void lpc_pair_kernel(const double* __
 
 int configure_frame_kernel() {
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(lpc_frame_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LP_LDS_MAX));
-        configured.done();
-    }
-    return L3AC_OK;
+    return raise_dynamic_lds(configured, {{lpc_frame_kernel, LP_LDS_MAX}});
 }
 
 // the parameters checked, then the frames' four values [batch][F][4] fp64 and the frames' flags [batch][F] int32

@@ -8,24 +8,10 @@
 #pragma once
 
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "lane_sums.hpp"
 #include "split_bf16.hpp"
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// the six plane products of one fragment pair, smallest first (split_bf16.hpp, mfma_split)
-__device__ __forceinline__ f32x4_t mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4_t acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
-    return acc;
-}
 
 // two accumulator tiles (rows 16 t + 4 g + i and 16 (t + 1) + 4 g + i of this lane's column) as the three bf16 planes of one
 // k step of 32 in the order sigma(g, j)
@@ -38,41 +24,6 @@ __device__ __forceinline__ void planes_of(const f32x4_t& lo, const f32x4_t& hi, 
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) out[pl] = __builtin_bit_cast(bf16x8, u32x4{p[pl][0], p[pl][1], p[pl][2], p[pl][3]});
 }
-
-// this wave's quarter (3 KB) of one ring slot: three 1-KB LDS-DMA pieces, lane l copying 16 B (as conv_unit_wide.hip)
-__device__ __forceinline__ void ring_dma_quarter(const unsigned char* base, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(lane_off), "s"(base), "s"(lds_dst)
-        : "memory");
-}
-
-// one 1-KB block of a ring slot (lane l copies 16 B from base + 16 l to lds_dst + 16 l)
-__device__ __forceinline__ void ring_dma_1k(const unsigned char* base, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(lane_off), "s"(base), "s"(lds_dst)
-        : "memory");
-}
-
-template <int N, class F, int I = 0>
-__device__ __forceinline__ void ring_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ring_static_for<N, F, I + 1>(static_cast<F&&>(f));
-    }
-}
-
 
 // the k a lane's j-th value comes from: sigma(g, j) where the other operand is made of accumulator tiles (above), 8 g + j where it is
 // loaded as 8 consecutive k per lane

@@ -209,7 +209,7 @@ void trans_stack_kernel(const TransStackArgs p) {
                 const unsigned char* sb = p.img + (int64_t)image_slot(src) * TS_SLOT + 1024 * dma_wave;
                 const unsigned db = ring_lds + (unsigned)((dma_slot & (L::RING_SLOTS - 1)) * TS_SLOT + 1024 * dma_wave);
 #pragma unroll
-                for (int i = 0; i < L::BPW; ++i) ring_dma_1k(sb + 1024 * L::NDW * i, lane_off, db + 1024u * (unsigned)(L::NDW * i));
+                for (int i = 0; i < L::BPW; ++i) dma_1k(sb + 1024 * L::NDW * i, lane_off, db + 1024u * (unsigned)(L::NDW * i));
             }
             ++dma_slot;
         }
@@ -257,7 +257,7 @@ void trans_stack_kernel(const TransStackArgs p) {
         const unsigned char* a = ring_lane + (slot_no & (L::RING_SLOTS - 1)) * TS_SLOT;
         bf16x8 f[PREF ? 2 : 1][3];
         load_frag(f[0], a);
-        ring_static_for<TS_SLOT_PIECES>([&](auto j_) {
+        static_for<TS_SLOT_PIECES>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
             if constexpr (PREF) {
                 if constexpr (j + 1 < TS_SLOT_PIECES) load_frag(f[(j + 1) & 1], a + (j + 1) * TS_PIECE);
@@ -282,13 +282,13 @@ void trans_stack_kernel(const TransStackArgs p) {
             bf16x8 fa[TS_SLOT_PIECES][3], fb[TS_SLOT_PIECES][3];
 #pragma unroll
             for (int j = 0; j < TS_SLOT_PIECES; ++j) load_frag(fa[j], a + j * TS_PIECE);
-            ring_static_for<TS_SLOT_PIECES>([&](auto j_) {
+            static_for<TS_SLOT_PIECES>([&](auto j_) {
                 constexpr int j = decltype(j_)::value;
                 load_frag(fb[j], a + TS_SLOT + j * TS_PIECE);
                 body(H0{}, j_, fa[j]);
             });
             last(H0{});
-            ring_static_for<TS_SLOT_PIECES>([&](auto j_) { body(H1{}, j_, fb[decltype(j_)::value]); });
+            static_for<TS_SLOT_PIECES>([&](auto j_) { body(H1{}, j_, fb[decltype(j_)::value]); });
             // the issue order, spelled out: left alone hipcc sinks every fragment read next to its use behind a full s_waitcnt (105
             // such waits for 360 MFMAs, ~450 cycles per slot of exposed LDS latency with one wave per SIMD)
             __builtin_amdgcn_sched_group_barrier(0x100, 3 * TS_SLOT_PIECES, 0);  // the first slot's fragments
@@ -568,7 +568,7 @@ void trans_stack_kernel(const TransStackArgs p) {
                 for (int t = 0; t < 8; ++t) tacc[t] = zero4;
             }
             f32x4_t vg[4] = {zero4, zero4, zero4, zero4};  // value tiles 0, 1 then gate tiles 0, 1 of hidden units 32 c .. 32 c + 31
-            ring_static_for<2>([&](auto w_) {  // value tiles 0, 1, then gate tiles 0, 1
+            static_for<2>([&](auto w_) {  // value tiles 0, 1, then gate tiles 0, 1
                 slot_pair([&](auto t_, auto j_, const bf16x8 (&f)[3]) __attribute__((always_inline)) {
                     constexpr int u = 2 * decltype(w_)::value + decltype(t_)::value;
                     vg[u] = mfma6(f, ap[decltype(j_)::value], vg[u]);
@@ -702,15 +702,12 @@ int launch_trans_stack(hipStream_t s, const LocalTransW& w, float* x, int batch,
                      n_layers >= 1 && n_layers <= TS_MAX_LAYERS,
                  "trans_stack: bad arguments (frames=%d window=%d layers=%d)", frames, w.window, n_layers);
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<4>::bytes(TS_MAX_LAYERS)));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<8>::bytes(TS_MAX_LAYERS)));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<12, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<12>::bytes(TS_MAX_LAYERS)));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<4, TS_KS>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<4>::bytes(TS_MAX_LAYERS)));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<8, TS_KS>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<8>::bytes(TS_MAX_LAYERS)));
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trans_stack_kernel<12, TS_KS>), hipFuncAttributeMaxDynamicSharedMemorySize, TsLds<12>::bytes(TS_MAX_LAYERS)));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{trans_stack_kernel<4, 1>, TsLds<4>::bytes(TS_MAX_LAYERS)},
+                                            {trans_stack_kernel<8, 1>, TsLds<8>::bytes(TS_MAX_LAYERS)},
+                                            {trans_stack_kernel<12, 1>, TsLds<12>::bytes(TS_MAX_LAYERS)},
+                                            {trans_stack_kernel<4, TS_KS>, TsLds<4>::bytes(TS_MAX_LAYERS)},
+                                            {trans_stack_kernel<8, TS_KS>, TsLds<8>::bytes(TS_MAX_LAYERS)},
+                                            {trans_stack_kernel<12, TS_KS>, TsLds<12>::bytes(TS_MAX_LAYERS)}}));
     int waves = 2 * (int)ceil_div64(frames, 32);  // even: every key tile a wave reads in pairs has been written by some wave
     if (waves < 4) waves = 4;                      // (the 4-wave instantiation adds its loader wave at the launch)
     // the cooperative form needs its TS_KS workgroups per clip co-resident (they wait for each other), one workgroup per CU

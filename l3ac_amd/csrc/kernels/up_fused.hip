@@ -11,7 +11,7 @@
 // read it back — 0.86 ms of the step for 2 GB of algorithmic traffic.
 //
 // One WAVE owns 16 consecutive input frames of a clip.  The conv is "weights (A) x activations (B)" on v_mfma_f32_16x16x32_bf16 with
-// both operands as exact bf16x3 splits (ring_common.hpp: fp32 accuracy): lane (frame fl, k group g) loads the 8 channels
+// both operands as exact bf16x3 splits (split_bf16.hpp: fp32 accuracy): lane (frame fl, k group g) loads the 8 channels
 // sigma(g, .) of ITS frame for each k step of 32, applies the gate in registers, splits, and multiplies against the weight pieces
 // resident in LDS; the result is in accumulator layout — channel 16 rt + 4 g + i of frame fl in register i of tile rt.  In that
 // layout the linear upsample needs the neighbouring FRAME = the neighbouring lane of the 16-lane row (two DPP row shifts per
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void up_fused_kernel(const U
         // store round trips: most of the 24 us the 256 -> 96 layer took for a single clip, whose four workgroups do little else)
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
         const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_uf;
-        for (int blk = wv; blk < G::RT * G::K1 * 3; blk += WAVES) ring_dma_1k(p.img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
+        for (int blk = wv; blk < G::RT * G::K1 * 3; blk += WAVES) dma_1k(p.img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
     }
     for (int i = tid; i < G::CP; i += 64 * WAVES) {
         par[i] = i < COUT ? p.bias[i] : 0.f;
@@ -281,10 +281,7 @@ template <int CIN, int COUT, int WAVES>
 int launch_uf_waves(hipStream_t s, const UpFusedArgs& a, int tiles_per_clip, int64_t tiles) {
     using G = UfGeo<CIN, COUT>;
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(up_fused_kernel<CIN, COUT, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{up_fused_kernel<CIN, COUT, WAVES>, G::LDS}}));
     int64_t blocks = ceil_div64(tiles, WAVES);
     const int64_t cus = l3ac_device_cu_count();
     if (blocks > cus) blocks = cus;
@@ -349,7 +346,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void down_exact_kernel(const UpFused
     {
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
         const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_uf;
-        for (int blk = wv; blk < G::RT * G::NQ / 2; blk += WAVES) ring_dma_1k(p.img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
+        for (int blk = wv; blk < G::RT * G::NQ / 2; blk += WAVES) dma_1k(p.img + 1024 * blk, 16u * (unsigned)(tid & 63), lds0 + 1024u * (unsigned)blk);
     }
     for (int i = tid; i < COUT; i += 64 * WAVES) {
         par[i] = p.bias[i];
@@ -457,10 +454,7 @@ template <int K, int COUT, int WAVES>
 int launch_dx_waves(hipStream_t s, const UpFusedArgs& a, int tiles_per_clip, int64_t tiles) {
     using G = DxGeo<K, COUT>;
     static PerDeviceOnce configured;
-    if (configured.first()) {
-        L3AC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(down_exact_kernel<K, COUT, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        configured.done();
-    }
+    L3AC_TRY(raise_dynamic_lds(configured, {{down_exact_kernel<K, COUT, WAVES>, G::LDS}}));
     int64_t blocks = ceil_div64(tiles, WAVES);
     const int64_t cus = l3ac_device_cu_count();
     if (blocks > cus) blocks = cus;
