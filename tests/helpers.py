@@ -16,6 +16,24 @@ def seeded_audio(batch, samples, seed=1234):
     return (torch.rand(batch, samples, generator=g) * 2 - 1) * 0.5
 
 
+def seeded_randn(shape, seed, scale=1.0):
+    """Normal draws from a CPU generator, times `scale`: the block tests' inputs."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g) * scale
+
+
+def assert_close(name, got, ref, atol, rtol):
+    """|got - ref| <= atol + rtol |ref| elementwise, in fp64 on the CPU, finite; prints the largest error."""
+    got = got.detach().cpu().double()
+    ref = ref.detach().cpu().double()
+    assert got.shape == ref.shape, f"{name}: shape {tuple(got.shape)} != {tuple(ref.shape)}"
+    err = (got - ref).abs()
+    bound = atol + rtol * ref.abs()
+    print(f"[{name}] max|err|={err.max().item():.3e} max|ref|={ref.abs().max().item():.3e}")
+    assert torch.isfinite(got).all(), f"{name}: non-finite output"
+    assert (err <= bound).all(), f"{name}: max err {err.max().item():.3e} (worst excess {(err - bound).max().item():.3e})"
+
+
 STRUCTURED_KINDS = ("sweep", "sine", "harmonics", "burst_after_silence", "dc_offset", "clipped", "quiet", "loud")
 
 

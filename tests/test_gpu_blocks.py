@@ -10,7 +10,7 @@ import l3ac_amd
 from l3ac_amd import _capi, weights as W
 from oracle import l3ac_oracle as O
 from tests import gpu_ops as G
-from tests.helpers import GOLDEN, index_mismatch_report, load_case, seeded_audio
+from tests.helpers import GOLDEN, assert_close, index_mismatch_report, load_case, seeded_audio, seeded_randn
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +19,7 @@ RTOL_BLOCK = 2e-5
 
 
 def _close(name, got, ref, atol=ATOL_BLOCK, rtol=RTOL_BLOCK):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    assert got.shape == ref.shape, f"{name}: shape {tuple(got.shape)} != {tuple(ref.shape)}"
-    err = (got - ref).abs()
-    bound = atol + rtol * ref.abs()
-    print(f"[{name}] max|err|={err.max().item():.3e} max|ref|={ref.abs().max().item():.3e}")
-    assert torch.isfinite(got).all(), f"{name}: non-finite output"
-    assert (err <= bound).all(), f"{name}: max err {err.max().item():.3e} (worst excess {(err - bound).max().item():.3e})"
+    assert_close(name, got, ref, atol, rtol)
 
 
 @pytest.fixture(scope="module")
@@ -47,9 +40,7 @@ def full():
     return codec, mc, w
 
 
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g) * scale
+_rand = seeded_randn
 
 
 # ---------------------------------------------------------------------------------------------------
