@@ -208,10 +208,8 @@ int set_checked(l3ac_ctx* ctx, const Option& o, int value, const char* who) {
 // ---- ragged batches -------------------------------------------------------------
 // The host's per-clip counts into the workspace's plan array, as kernel arguments (never through a staging buffer the next call could
 // overwrite while a copy is in flight: the caller may reuse its array at once, and a captured graph replays these values), and the
-// context's RaggedPlan pointing at them.  `samples` null: decode (n_tok * hop).
-int ragged_plan(l3ac_ctx* ctx, hipStream_t s, RaggedPlan& p, int batch, int max_tok, const int32_t* n_tok, const int32_t* samples) {
-    p.max_tok = max_tok;
-    p.n_tok.assign(n_tok, n_tok + batch);
+// context's RaggedPlan pointing at them.  The caller has set p.max_tok and p.n_tok; `samples` null: decode (n_tok * hop).
+int ragged_plan(l3ac_ctx* ctx, hipStream_t s, RaggedPlan& p, int batch, const int32_t* samples) {
     p.order.resize(batch);
     for (int i = 0; i < batch; ++i) p.order[i] = i;
     std::stable_sort(p.order.begin(), p.order.end(), [&](int a, int b) { return p.n_tok[a] < p.n_tok[b]; });
@@ -235,6 +233,74 @@ struct RaggedScope {
     RaggedScope(l3ac_ctx* c, const RaggedPlan* p) : ctx(c) { ctx->rag = p; }
     ~RaggedScope() { ctx->rag = nullptr; }
 };
+
+// ---- quantiser arguments --------------------------------------------------------------------------------
+// n tokens of `feat` features at the given levels; the caller adds its input, its outputs and the weights it has
+FsqArgs fsq_args(const int32_t* levels, int n_levels, int feat, int64_t n) {
+    FsqArgs f{};
+    f.n = n; f.feat = feat; f.n_levels = n_levels;
+    for (int d = 0; d < n_levels; ++d) f.levels[d] = levels[d];
+    return f;
+}
+// the context's quantiser (vq/__init__.py:13-14)
+FsqArgs fsq_args(const l3ac_ctx* ctx, int64_t n) {
+    FsqArgs f = fsq_args(ctx->cfg.levels, ctx->cfg.n_levels, ctx->cfg.feature_dim, n);
+    f.w_in = ctx->q_win; f.b_in = ctx->q_bin; f.w_out = ctx->q_wout; f.b_out = ctx->q_bout;
+    return f;
+}
+
+// ---- encode / decode behind the entries' argument checks ---------------------------------------------------
+// `plan`: null, or the ragged call's with max_tok and n_tok set: completed here, once the workspace has its
+// device array, and the context's for the rest of the call.  rag_samples: the clips' lengths (ragged only).
+int encode_body(l3ac_ctx* ctx, hipStream_t s, const float* audio, int batch, int samples, int64_t audio_stride, float* q_feature,
+                int32_t* indices, float* level_indices, RaggedPlan* plan, const int32_t* rag_samples) {
+    L3AC_TRY(workspace_ensure_clip(ctx, batch, samples, s));
+    if (plan) L3AC_TRY(ragged_plan(ctx, s, *plan, batch, rag_samples));
+    RaggedScope scope(ctx, plan);
+    const int frames = (int)round_up64(samples, ctx->hop);  // Codec.preprocess (codec.py:79-84)
+    float* cur = ctx->ws.x0;
+    float* alt = ctx->ws.x1;
+    L3AC_TRY(run_encoder(ctx, s, audio, audio_stride, batch, samples, frames, &cur, &alt));
+    int n_tok = 0;
+    L3AC_TRY(run_en_encoder(ctx, s, batch, frames / ctx->enc_rate, &cur, &alt, &n_tok));
+    FsqArgs f = fsq_args(ctx, (int64_t)batch * n_tok);
+    f.x = cur; f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices;
+    L3AC_TRY(launch_fsq(s, f));
+    if (!plan) return L3AC_OK;
+    // tokens after a clip's own are zero (int32 0 and fp32 0 share their bits)
+    L3AC_TRY(launch_ragged_mask(s, q_feature, batch, n_tok, ctx->cfg.feature_dim, plan->n_dev, 1, n_tok));
+    L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(indices), batch, n_tok, 1, plan->n_dev, 1, n_tok));
+    if (level_indices) L3AC_TRY(launch_ragged_mask(s, level_indices, batch, n_tok, ctx->cfg.n_levels, plan->n_dev, 1, n_tok));
+    return L3AC_OK;
+}
+
+int decode_body(l3ac_ctx* ctx, hipStream_t s, const float* q_feature, const int32_t* indices, int batch, int n_tok, float* audio_out,
+                RaggedPlan* plan) {
+    L3AC_TRY(workspace_ensure_clip(ctx, batch, n_tok * ctx->hop, s));
+    if (plan) L3AC_TRY(ragged_plan(ctx, s, *plan, batch, nullptr));
+    RaggedScope scope(ctx, plan);
+    float* cur = ctx->ws.x0;
+    float* alt = ctx->ws.x1;
+    const int64_t n = (int64_t)batch * n_tok;
+    if (q_feature) {
+        L3AC_HIP_CHECK(hipMemcpyAsync(cur, q_feature, (size_t)n * ctx->cfg.feature_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (plan) L3AC_TRY(launch_ragged_mask(s, cur, batch, n_tok, ctx->cfg.feature_dim, plan->n_dev, 1, n_tok));
+    } else {  // VQEmbed.to_features (vq/__init__.py:20-23)
+        if (plan) {  // tokens after a clip's own become index 0 first: they never reach bad_index_count
+            int32_t* idx = reinterpret_cast<int32_t*>(ctx->ws.a);
+            L3AC_HIP_CHECK(hipMemcpyAsync(idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(idx), batch, n_tok, 1, plan->n_dev, 1, n_tok));
+            indices = idx;
+        }
+        FsqArgs f = fsq_args(ctx, n);
+        f.w_in = f.b_in = nullptr;  // (the indices are the input: nothing to project in)
+        f.idx_in = indices; f.q_feature = cur; f.bad_count = ctx->bad_index_count;
+        L3AC_TRY(launch_fsq(s, f));
+    }
+    int frames = 0;
+    L3AC_TRY(run_en_decoder(ctx, s, batch, n_tok, &cur, &alt, &frames));
+    return run_decoder(ctx, s, batch, frames, &cur, &alt, audio_out);
+}
 
 }  // namespace
 
@@ -353,20 +419,7 @@ int l3ac_encode(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t sample
     L3AC_ENTER_WS(ctx, stream);
     L3AC_REQUIRE(audio && q_feature && indices, "l3ac_encode: null buffer");
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && samples > 0 && audio_stride >= samples, "l3ac_encode: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    L3AC_TRY(workspace_ensure_clip(ctx, batch, samples, s));
-    const int frames = (int)round_up64(samples, ctx->hop);  // Codec.preprocess (codec.py:79-84)
-    float* cur = ctx->ws.x0;
-    float* alt = ctx->ws.x1;
-    L3AC_TRY(run_encoder(ctx, s, audio, audio_stride, batch, samples, frames, &cur, &alt));
-    int n_tok = 0;
-    L3AC_TRY(run_en_encoder(ctx, s, batch, frames / ctx->enc_rate, &cur, &alt, &n_tok));
-    FsqArgs f{};
-    f.x = cur; f.n = (int64_t)batch * n_tok; f.feat = ctx->cfg.feature_dim; f.n_levels = ctx->cfg.n_levels;
-    for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
-    f.w_in = ctx->q_win; f.b_in = ctx->q_bin; f.w_out = ctx->q_wout; f.b_out = ctx->q_bout;
-    f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices;
-    return launch_fsq(s, f);
+    return encode_body(ctx, (hipStream_t)stream, audio, batch, samples, audio_stride, q_feature, indices, level_indices, nullptr, nullptr);
 }
 
 int l3ac_decode(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, int32_t batch, int32_t n_tok,
@@ -374,24 +427,7 @@ int l3ac_decode(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, i
     L3AC_ENTER_WS(ctx, stream);
     L3AC_REQUIRE((q_feature || indices) && audio_out, "l3ac_decode: null buffer");
     L3AC_REQUIRE(batch > 0 && batch <= 65535 && n_tok > 0, "l3ac_decode: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    L3AC_TRY(workspace_ensure_clip(ctx, batch, n_tok * ctx->hop, s));
-    float* cur = ctx->ws.x0;
-    float* alt = ctx->ws.x1;
-    const int64_t n = (int64_t)batch * n_tok;
-    if (q_feature) {
-        L3AC_HIP_CHECK(hipMemcpyAsync(cur, q_feature, (size_t)n * ctx->cfg.feature_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else {  // VQEmbed.to_features (vq/__init__.py:20-23)
-        FsqArgs f{};
-        f.idx_in = indices; f.n = n; f.feat = ctx->cfg.feature_dim; f.n_levels = ctx->cfg.n_levels;
-        for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
-        f.w_out = ctx->q_wout; f.b_out = ctx->q_bout; f.q_feature = cur;
-        f.bad_count = ctx->bad_index_count;
-        L3AC_TRY(launch_fsq(s, f));
-    }
-    int frames = 0;
-    L3AC_TRY(run_en_decoder(ctx, s, batch, n_tok, &cur, &alt, &frames));
-    return run_decoder(ctx, s, batch, frames, &cur, &alt, audio_out);
+    return decode_body(ctx, (hipStream_t)stream, q_feature, indices, batch, n_tok, audio_out, nullptr);
 }
 
 // ragged batches: clip i of the batch gets the bits of clip i alone
@@ -406,31 +442,10 @@ int l3ac_encode_ragged(l3ac_ctx* ctx, const float* audio, int32_t batch, int32_t
     for (int i = 0; i < batch; ++i)
         L3AC_REQUIRE(samples[i] >= 1 && samples[i] <= max_samples, "l3ac_encode_ragged: samples[%d] = %d outside [1, %d]", i, samples[i],
                      max_samples);
-    hipStream_t s = (hipStream_t)stream;
-    L3AC_TRY(workspace_ensure_clip(ctx, batch, max_samples, s));
-    const int max_tok = (int)ceil_div64(max_samples, ctx->hop);
-    std::vector<int32_t> n_tok(batch);
-    for (int i = 0; i < batch; ++i) n_tok[i] = (int32_t)ceil_div64(samples[i], ctx->hop);
     RaggedPlan plan;
-    L3AC_TRY(ragged_plan(ctx, s, plan, batch, max_tok, n_tok.data(), samples));
-    RaggedScope scope(ctx, &plan);
-    const int frames = max_tok * ctx->hop;
-    float* cur = ctx->ws.x0;
-    float* alt = ctx->ws.x1;
-    L3AC_TRY(run_encoder(ctx, s, audio, audio_stride, batch, max_samples, frames, &cur, &alt));
-    int n = 0;
-    L3AC_TRY(run_en_encoder(ctx, s, batch, frames / ctx->enc_rate, &cur, &alt, &n));
-    FsqArgs f{};
-    f.x = cur; f.n = (int64_t)batch * n; f.feat = ctx->cfg.feature_dim; f.n_levels = ctx->cfg.n_levels;
-    for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
-    f.w_in = ctx->q_win; f.b_in = ctx->q_bin; f.w_out = ctx->q_wout; f.b_out = ctx->q_bout;
-    f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices;
-    L3AC_TRY(launch_fsq(s, f));
-    // tokens after a clip's own are zero (int32 0 and fp32 0 share their bits)
-    L3AC_TRY(launch_ragged_mask(s, q_feature, batch, n, ctx->cfg.feature_dim, plan.n_dev, 1, n));
-    L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(indices), batch, n, 1, plan.n_dev, 1, n));
-    if (level_indices) L3AC_TRY(launch_ragged_mask(s, level_indices, batch, n, ctx->cfg.n_levels, plan.n_dev, 1, n));
-    return L3AC_OK;
+    plan.max_tok = (int)ceil_div64(max_samples, ctx->hop);
+    for (int i = 0; i < batch; ++i) plan.n_tok.push_back((int)ceil_div64(samples[i], ctx->hop));
+    return encode_body(ctx, (hipStream_t)stream, audio, batch, max_samples, audio_stride, q_feature, indices, level_indices, &plan, samples);
 }
 
 int l3ac_decode_ragged(l3ac_ctx* ctx, const float* q_feature, const int32_t* indices, int32_t batch, int32_t max_tok,
@@ -447,32 +462,10 @@ int l3ac_decode_ragged(l3ac_ctx* ctx, const float* q_feature, const int32_t* ind
         L3AC_REQUIRE((int64_t)n_tok[i] * rate >= 2, "l3ac_decode_ragged: n_tok[%d] = %d: a clip needs n_tok * en_coder_compress_rate "
                      ">= 2 frames (the first EnhanceBlock's InstanceNorm)", i, n_tok[i]);
     }
-    hipStream_t s = (hipStream_t)stream;
-    L3AC_TRY(workspace_ensure_clip(ctx, batch, max_tok * ctx->hop, s));
     RaggedPlan plan;
-    L3AC_TRY(ragged_plan(ctx, s, plan, batch, max_tok, n_tok, nullptr));
-    RaggedScope scope(ctx, &plan);
-    float* cur = ctx->ws.x0;
-    float* alt = ctx->ws.x1;
-    const int64_t n = (int64_t)batch * max_tok;
-    const int feat = ctx->cfg.feature_dim;
-    if (q_feature) {
-        L3AC_HIP_CHECK(hipMemcpyAsync(cur, q_feature, (size_t)n * feat * sizeof(float), hipMemcpyDeviceToDevice, s));
-        L3AC_TRY(launch_ragged_mask(s, cur, batch, max_tok, feat, plan.n_dev, 1, max_tok));
-    } else {  // tokens after a clip's own become index 0 first: they never reach bad_index_count
-        int32_t* idx = reinterpret_cast<int32_t*>(ctx->ws.a);
-        L3AC_HIP_CHECK(hipMemcpyAsync(idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        L3AC_TRY(launch_ragged_mask(s, reinterpret_cast<float*>(idx), batch, max_tok, 1, plan.n_dev, 1, max_tok));
-        FsqArgs f{};
-        f.idx_in = idx; f.n = n; f.feat = feat; f.n_levels = ctx->cfg.n_levels;
-        for (int d = 0; d < f.n_levels; ++d) f.levels[d] = ctx->cfg.levels[d];
-        f.w_out = ctx->q_wout; f.b_out = ctx->q_bout; f.q_feature = cur;
-        f.bad_count = ctx->bad_index_count;
-        L3AC_TRY(launch_fsq(s, f));
-    }
-    int frames = 0;
-    L3AC_TRY(run_en_decoder(ctx, s, batch, max_tok, &cur, &alt, &frames));
-    return run_decoder(ctx, s, batch, frames, &cur, &alt, audio_out);
+    plan.max_tok = max_tok;
+    plan.n_tok.assign(n_tok, n_tok + batch);
+    return decode_body(ctx, (hipStream_t)stream, q_feature, indices, batch, max_tok, audio_out, &plan);
 }
 
 // ---- quantiser kernels --------------------------------------------------------------------------------
@@ -480,10 +473,8 @@ int l3ac_fsq_forward(const float* x, int64_t n, int32_t feat, const int32_t* lev
                      const float* w_in, const float* b_in, const float* w_out, const float* b_out, float* q_feature,
                      int32_t* indices, float* level_indices, float* latents, void* stream) {
     L3AC_REQUIRE(levels && n_levels >= 1 && n_levels <= L3AC_MAX_LEVELS, "fsq: bad levels");
-    FsqArgs f{};
-    f.x = x; f.n = n; f.feat = feat; f.n_levels = n_levels;
-    for (int d = 0; d < n_levels; ++d) f.levels[d] = levels[d];
-    f.w_in = w_in; f.b_in = b_in; f.w_out = w_out; f.b_out = b_out;
+    FsqArgs f = fsq_args(levels, n_levels, feat, n);
+    f.x = x; f.w_in = w_in; f.b_in = b_in; f.w_out = w_out; f.b_out = b_out;
     f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices; f.latents = latents;
     return launch_fsq((hipStream_t)stream, f);
 }
@@ -491,9 +482,7 @@ int l3ac_fsq_forward(const float* x, int64_t n, int32_t feat, const int32_t* lev
 int l3ac_fsq_quantize_act(const float* act, int64_t n, int32_t feat, const int32_t* levels, int32_t n_levels, const float* w_out,
                           const float* b_out, float* q_feature, int32_t* indices, float* level_indices, void* stream) {
     L3AC_REQUIRE(act && levels && n_levels >= 1 && n_levels <= L3AC_MAX_LEVELS, "fsq_quantize_act: bad arguments");
-    FsqArgs f{};
-    f.n = n; f.feat = feat; f.n_levels = n_levels;
-    for (int d = 0; d < n_levels; ++d) f.levels[d] = levels[d];
+    FsqArgs f = fsq_args(levels, n_levels, feat, n);
     f.w_out = w_out; f.b_out = b_out; f.q_feature = q_feature; f.indices = indices; f.level_indices = level_indices;
     f.latents = const_cast<float*>(act);  // read only in this mode
     f.act_in = true;
@@ -503,10 +492,8 @@ int l3ac_fsq_quantize_act(const float* act, int64_t n, int32_t feat, const int32
 int l3ac_fsq_decode(const int32_t* indices, int64_t n, int32_t feat, const int32_t* levels, int32_t n_levels,
                     const float* w_out, const float* b_out, float* q_feature, void* stream) {
     L3AC_REQUIRE(indices && levels && n_levels >= 1 && n_levels <= L3AC_MAX_LEVELS, "fsq_decode: bad arguments");
-    FsqArgs f{};
-    f.idx_in = indices; f.n = n; f.feat = feat; f.n_levels = n_levels;
-    for (int d = 0; d < n_levels; ++d) f.levels[d] = levels[d];
-    f.w_out = w_out; f.b_out = b_out; f.q_feature = q_feature;
+    FsqArgs f = fsq_args(levels, n_levels, feat, n);
+    f.idx_in = indices; f.w_out = w_out; f.b_out = b_out; f.q_feature = q_feature;
     return launch_fsq((hipStream_t)stream, f);
 }
 
@@ -547,31 +534,13 @@ int l3ac_op_first_block_at(l3ac_ctx* ctx, const float* audio, int32_t batch, int
     return launch_first_block((hipStream_t)stream, ctx->first, audio, audio_stride, batch, samples, frames, y);
 }
 
-// The size limits every block entry shares, asked before the workspace is sized for the call: frame numbers inside a clip are ints with a
-// tile and a halo added (dwconv_ln_kernel, the enhance kernels, the LegacyUnit and head kernels, the stem), and 2^34 rows keep every
-// kernel's tile count -- tiles of 14 frames and more, plus one per clip -- below 2^31 - 65536
-static int op_shape_ok(int batch, int frames) {
-    L3AC_REQUIRE(frames <= L3AC_MAX_CLIP_FRAMES, "block entry: %d frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", frames);
-    L3AC_REQUIRE((int64_t)batch * frames < L3AC_MAX_ROWS, "block entry: batch * frames = %lld, the limit is 2^34 rows (32-bit tile numbers)",
-                 (long long)batch * frames);
-    return L3AC_OK;
-}
-
-// (h: 4C floats per row, or the wide ConvUnit front end's planes of whole 32-frame tiles when that is more)
-#define L3AC_OP_SCRATCH(c_max)                                                                                    \
-    L3AC_TRY(op_shape_ok(batch, frames));                                                                         \
-    L3AC_TRY(workspace_ensure(ctx, (size_t)batch * frames * (c_max), (size_t)batch * frames * (c_max),           \
-                              std::max((size_t)batch * frames * 4 * (c_max),                                      \
-                                       (conv_unit_wide_scratch_bytes((c_max), (int64_t)batch * frames) + 3) / 4), \
-                              (size_t)batch * frames * 4, (size_t)batch, (hipStream_t)stream))
-
 int l3ac_op_conv_unit(l3ac_ctx* ctx, const char* block, const float* x, int32_t batch, int32_t frames, float* y,
                       void* stream) {
     L3AC_ENTER_WS(ctx, stream);
     const ConvUnitW* w = lookup(ctx->by_unit, block, "ConvUnit");
     if (!w) return L3AC_EINVAL;
     L3AC_TRY(conv_unit_shape_ok(ctx, *w, x == y, frames));
-    L3AC_OP_SCRATCH(w->c);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, w->c, (hipStream_t)stream));
     return run_conv_unit(ctx, (hipStream_t)stream, *w, x, y, batch, frames);
 }
 
@@ -599,7 +568,7 @@ int l3ac_op_enhance(l3ac_ctx* ctx, const char* block, const float* x, int32_t ba
     L3AC_ENTER_WS(ctx, stream);
     const EnhW* w = lookup(ctx->by_enh, block, "EnhanceBlock");
     if (!w) return L3AC_EINVAL;
-    L3AC_OP_SCRATCH(w->c);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, w->c, (hipStream_t)stream));
     return run_enhance(ctx, (hipStream_t)stream, *w, x, y, batch, frames);
 }
 
@@ -609,7 +578,7 @@ int l3ac_op_up_layer(l3ac_ctx* ctx, const char* block, const float* x, int32_t b
     const UpW* w = lookup(ctx->by_up, block, "up-layer");
     if (!w) return L3AC_EINVAL;
     L3AC_TRY(up_layer_frames_ok(frames, w->scale));
-    L3AC_OP_SCRATCH(w->cout);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, w->cout, (hipStream_t)stream));
     return run_up(ctx, (hipStream_t)stream, *w, x, ctx->ws.a, y, batch, frames);
 }
 
@@ -622,7 +591,7 @@ int l3ac_op_enhance_up(l3ac_ctx* ctx, const char* enhance_block, const char* up_
     L3AC_REQUIRE(e->c == w->cin, "enhance_up: blocks of different widths (%d vs %d)", e->c, w->cin);
     L3AC_REQUIRE(x != y, "op_enhance_up: x and y must not alias (x is only read)");
     L3AC_TRY(up_layer_frames_ok(frames, w->scale));
-    L3AC_OP_SCRATCH(w->cin > w->cout ? w->cin : w->cout);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, w->cin > w->cout ? w->cin : w->cout, (hipStream_t)stream));
     // the pipeline's fused form: gate applied inside the up conv's A staging; x is only read
     return run_enhance_up(ctx, (hipStream_t)stream, *e, *w, const_cast<float*>(x), ctx->ws.a, y, batch, frames);
 }
@@ -630,7 +599,7 @@ int l3ac_op_enhance_up(l3ac_ctx* ctx, const char* enhance_block, const char* up_
 int l3ac_op_last_block(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t frames, float* audio, void* stream) {
     L3AC_ENTER_WS(ctx, stream);
     const int c = ctx->head.c;
-    L3AC_OP_SCRATCH(c);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, c, (hipStream_t)stream));
     hipStream_t s = (hipStream_t)stream;
     L3AC_HIP_CHECK(hipMemcpyAsync(ctx->ws.x0, x, (size_t)batch * frames * c * sizeof(float), hipMemcpyDeviceToDevice, s));
     return run_last_block(ctx, s, ctx->ws.x0, audio, batch, frames);
@@ -643,7 +612,7 @@ int l3ac_op_legacy_unit(l3ac_ctx* ctx, int32_t unit, const float* x, int32_t bat
     // (the fused kernel cannot run in place: in-place calls are refused instead of silently taking another form)
     L3AC_REQUIRE(x != y, "op_legacy_unit: x and y must not alias");
     const LegacyW& l = ctx->legacy[unit];
-    L3AC_OP_SCRATCH(l.c);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, l.c, (hipStream_t)stream));
     return run_legacy_unit(ctx, (hipStream_t)stream, l, x, y, batch, frames);
 }
 
@@ -651,7 +620,7 @@ int l3ac_op_head(l3ac_ctx* ctx, const float* x, int32_t batch, int32_t frames, f
     L3AC_ENTER_WS(ctx, stream);
     L3AC_REQUIRE(batch > 0 && frames > 0, "op_head: bad shape %d x %d", batch, frames);
     const int c = ctx->head.c;
-    L3AC_OP_SCRATCH(c);
+    L3AC_TRY(workspace_ensure_op(ctx, batch, frames, c, (hipStream_t)stream));
     return run_head(ctx, (hipStream_t)stream, x, audio, batch, frames);
 }
 

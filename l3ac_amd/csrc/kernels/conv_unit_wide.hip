@@ -1049,9 +1049,87 @@ __global__ __launch_bounds__(256, 1) void wide_sliced_out_kernel(const ConvUnitW
 // it is taken by default (measured against the half-tile form: tools/wide_bench.py, profiles/r05/wide_sliced_sweep.txt)
 constexpr int64_t SLICED_MAX_TILES = 256, SLICED_AUTO_TILES = 256;
 __host__ constexpr size_t wide_planes_bytes(int c, int64_t rows) { return (size_t)((rows + 31) / 32) * 32 * (size_t)c * 6; }
+__host__ constexpr size_t wide_hidden_offset(int c, int64_t rows) { return (wide_planes_bytes(c, rows) + 255) / 256 * 256; }  // the hidden image's place
 __host__ constexpr int64_t sliced_tiles_pad(int64_t rows) { return ((rows + 15) / 16 + 3) / 4 * 4; }
-__host__ constexpr bool sliced_exists(int c, int64_t rows) { return (rows + 15) / 16 <= SLICED_MAX_TILES; }
+__host__ constexpr bool sliced_exists(int64_t rows) { return (rows + 15) / 16 <= SLICED_MAX_TILES; }
 __host__ constexpr size_t sliced_hidden_bytes(int c, int64_t rows) { return (size_t)(4 * c / 32) * (size_t)sliced_tiles_pad(rows) * 3072; }
+
+// The form one call takes and the numbers its launches need.  wide_plan decides, launch_wide only executes.
+enum class WideForm { AllSliced, HalfTiles, Passes, PassesSlicedTail, PassesHalfTail, PassesCounter };
+struct WidePlan {
+    WideForm form;
+    int64_t rows_main;  // rows [0, rows_main) go to the fused kernel: none (all sliced), all, or the full passes in front of a sliced tail
+    int64_t blocks;     // the fused kernel's grid
+    int64_t tail_k;     // its tail_tiles argument: tiles run as half tiles behind the passes; by counter, the workgroups' last units
+    bool counter;       // it hands its units out by the context's counters
+    bool hidden;        // rows [rows_main, rows) go to the sliced pair: its hidden image lies behind the planes (wide_hidden_offset)
+};
+
+// wg_per_cu, front, dyn: WGeo's constants of the width; cus: the device's CU count; sliced_mode: launch_conv_unit_wide's
+WidePlan wide_plan(int wg_per_cu, bool front, bool dyn, int64_t rows, int cus, int sliced_mode, bool have_counters) {
+    WidePlan p{WideForm::AllSliced, 0, 0, 0, false, true};
+    if (sliced_exists(rows) && (sliced_mode == 2 || (sliced_mode == 1 && ceil_div64(rows, 16) <= SLICED_AUTO_TILES))) return p;
+    p.rows_main = rows;
+    p.hidden = false;
+    const int64_t tiles = ceil_div64(rows, 32);
+    p.blocks = ceil_div64(tiles, 4);
+    if (2 * p.blocks <= (int64_t)cus * wg_per_cu) {  // half tiles while twice the workgroups still fit one pass
+        p.form = WideForm::HalfTiles;
+        p.blocks = ceil_div64(2 * tiles, 4);
+        return p;
+    }
+    // A large grid runs its tiles in lock-step passes of 4 x 256 and the last pass may be nearly empty (256 x 900 frames at C = 256:
+    // 7 200 tiles = 7 full passes + 32 tiles).
+    const int64_t per_pass = 4LL * 256 * wg_per_cu;
+    const int64_t full = tiles / per_pass * per_pass, rest = tiles - full;
+    p.blocks = std::min<int64_t>(p.blocks, 256 * wg_per_cu);
+    if (!front && full > 0 && rest > 0 && 2 * rest <= SLICED_MAX_TILES) {
+        // SLICED TAIL (round 6): a remainder of at most SLICED_MAX_TILES frame tiles behind the full passes cost 0.7 of a pass as half
+        // tiles on 16 workgroups — a wave's chain of 3 072 MFMAs however few waves run (stamps: 180 k of the kernel's 1 800 k cycles,
+        // ~90 us).  The sliced form (two launches over frame tiles x channel slices, the same bits) does those frames in ~25 us: the
+        // passes run on rows [0, 32 full), the two sliced launches on the rest, from the same plane image.  One box, three interleaved
+        // rounds: the step 13.22 -> 13.11 ms (profiles/r06/sliced_tail_ab.txt).
+        p.form = WideForm::PassesSlicedTail;
+        p.rows_main = 32 * full;
+        p.hidden = true;
+    } else if (dyn && have_counters && tiles > 4 * p.blocks) {
+        // units by counter (conv_unit_wide_kernel, DYN): the last tile's worth per workgroup as groups of half tiles (measured against
+        // 0, 2 and 4 per workgroup: profiles/r06/wide96_sched/dyn_ab.txt)
+        p.form = WideForm::PassesCounter;
+        p.counter = true;
+        p.tail_k = p.blocks;
+    } else if (full > 0 && rest > 0 && 2 * rest <= per_pass) {
+        // a remainder of at most half a pass is left out of the passes and run as HALF tiles by the first workgroups, inside the same
+        // launch (conv_unit_wide_kernel, tail_tiles)
+        p.form = WideForm::PassesHalfTail;
+        p.tail_k = rest;
+    } else {
+        p.form = WideForm::Passes;
+    }
+    return p;
+}
+
+// the sliced pair, hidden kernel then out kernel, on `rows` rows: planes, x and y at the first of them
+template <int C>
+int launch_sliced_pair(hipStream_t s, const ConvUnitW& w, const unsigned char* planes, unsigned char* hid, const float* x, float* y, int64_t rows, int frames) {
+    using G = WGeo<C>;
+    using S = SGeo<C>;
+    char name[64];
+    const int64_t tiles16 = ceil_div64(rows, 16), tiles_pad = sliced_tiles_pad(rows);
+    {
+        std::snprintf(name, sizeof(name), "wide_sliced_hidden_kernel<%d>", C);
+        ProfScope p1(s, name, (double)rows * (8.0 * C * C + (G::FRONT ? 30.0 * C * (G::NT / S::GH) : 0.0)), (double)rows * 30.0 * C);
+        hipLaunchKernelGGL((wide_sliced_hidden_kernel<C>), dim3((unsigned)(tiles_pad / 4 * (G::NT / S::GH))), dim3(256), S::LDS1, s, w, planes, hid,
+                           tiles16, tiles_pad, x, rows, frames);
+        L3AC_LAUNCH_CHECK();
+    }
+    std::snprintf(name, sizeof(name), "wide_sliced_out_kernel<%d>", C);
+    ProfScope p2(s, name, (double)rows * 8.0 * C * C, (double)rows * 32.0 * C);
+    hipLaunchKernelGGL((wide_sliced_out_kernel<C>), dim3((unsigned)(ceil_div64(tiles16, 2) * (G::RT / 2))), dim3(256), S::LDS2, s, w, hid, x, y, rows,
+                       tiles16, tiles_pad);
+    L3AC_LAUNCH_CHECK();
+    return L3AC_OK;
+}
 
 template <int C>
 int launch_wide(hipStream_t s, const ConvUnitW& w, const float* x, float* y, unsigned char* planes, int64_t rows, int frames, int sliced_mode, int* counters) {
@@ -1061,9 +1139,8 @@ int launch_wide(hipStream_t s, const ConvUnitW& w, const float* x, float* y, uns
                                             {conv_unit_wide_kernel<C, 1>, G::LDS},
                                             {wide_sliced_hidden_kernel<C>, SGeo<C>::LDS1},
                                             {wide_sliced_out_kernel<C>, SGeo<C>::LDS2}}));
+    const WidePlan p = wide_plan(G::WG_PER_CU, G::FRONT, G::DYN, rows, l3ac_device_cu_count(), sliced_mode, counters != nullptr);
     char name[64];
-    const int64_t tiles16 = ceil_div64(rows, 16);
-    const bool sliced = sliced_exists(C, rows) && (sliced_mode == 2 || (sliced_mode == 1 && tiles16 <= SLICED_AUTO_TILES));
     if constexpr (!G::FRONT) {
         std::snprintf(name, sizeof(name), "dwconv_ln_split_kernel<%d>", C);
         ProfScope prof(s, name, (double)rows * 30.0 * C, (double)rows * 10.0 * C);
@@ -1071,93 +1148,19 @@ int launch_wide(hipStream_t s, const ConvUnitW& w, const float* x, float* y, uns
         hipLaunchKernelGGL((dwconv_ln_split_kernel<C>), dim3((unsigned)ceil_div64(rows, 32)), dim3(256), IMG, s, w, x, planes, rows, frames);
         L3AC_LAUNCH_CHECK();
     }
-    if (sliced) {
-        using S = SGeo<C>;
-        const int64_t tiles_pad = sliced_tiles_pad(rows);
-        unsigned char* hid = planes + (wide_planes_bytes(C, rows) + 255) / 256 * 256;
-        {
-            std::snprintf(name, sizeof(name), "wide_sliced_hidden_kernel<%d>", C);
-            ProfScope p1(s, name, (double)rows * (8.0 * C * C + (G::FRONT ? 30.0 * C * (G::NT / S::GH) : 0.0)), (double)rows * 30.0 * C);
-            hipLaunchKernelGGL((wide_sliced_hidden_kernel<C>), dim3((unsigned)(tiles_pad / 4 * (G::NT / S::GH))), dim3(256), S::LDS1, s, w, planes, hid,
-                               tiles16, tiles_pad, x, rows, frames);
-            L3AC_LAUNCH_CHECK();
-        }
-        std::snprintf(name, sizeof(name), "wide_sliced_out_kernel<%d>", C);
-        ProfScope p2(s, name, (double)rows * 8.0 * C * C, (double)rows * 32.0 * C);
-        hipLaunchKernelGGL((wide_sliced_out_kernel<C>), dim3((unsigned)(ceil_div64(tiles16, 2) * (G::RT / 2))), dim3(256), S::LDS2, s, w, hid, x, y, rows,
-                           tiles16, tiles_pad);
+    if (p.rows_main > 0) {
+        std::snprintf(name, sizeof(name), "conv_unit_wide_kernel<%d>", C);
+        ProfScope prof(s, name, (double)p.rows_main * (16.0 * C * C + (G::FRONT ? 30.0 * C : 0.0)), (double)p.rows_main * (G::FRONT ? 8.0 : 14.0) * C);
+        if (p.form == WideForm::HalfTiles)
+            hipLaunchKernelGGL((conv_unit_wide_kernel<C, 1>), dim3((unsigned)p.blocks), dim3(256), G::LDS, s, w, planes, x, y, rows, (int64_t)0, frames, (int*)nullptr);
+        else
+            hipLaunchKernelGGL((conv_unit_wide_kernel<C, 2>), dim3((unsigned)p.blocks), dim3(256), G::LDS, s, w, planes, x, y, p.rows_main, p.tail_k, frames,
+                               p.counter ? counters : (int*)nullptr);
         L3AC_LAUNCH_CHECK();
-        return L3AC_OK;
     }
-    const int64_t tiles = ceil_div64(rows, 32);
-    int64_t blocks = ceil_div64(tiles, 4);
-    const int cus = l3ac_device_cu_count();
-    const bool half = 2 * blocks <= (int64_t)cus * G::WG_PER_CU;  // half tiles while twice the workgroups still fit one pass
-    if constexpr (!G::FRONT) {
-        // SLICED TAIL (round 6): a remainder of at most SLICED_MAX_TILES frame tiles behind the full passes (256 x 900 frames at C = 256: 7 full
-        // passes + 32 tiles) cost 0.7 of a pass as half tiles on 16 workgroups — a wave's chain of 3 072 MFMAs however few waves run
-        // (stamps: 180 k of the kernel's 1 800 k cycles, ~90 us).  The sliced form (two launches over frame tiles x channel slices, the same
-        // bits) does those frames in ~25 us: the passes run on rows [0, 32 full), the two sliced launches on the rest, from the same plane
-        // image.  One box, three interleaved rounds: the step 13.22 -> 13.11 ms (profiles/r06/sliced_tail_ab.txt).
-        const int64_t per_pass = 4LL * 256 * G::WG_PER_CU;
-        const int64_t full = tiles / per_pass * per_pass, rest = tiles - full;
-        if (!half && full > 0 && rest > 0 && 2 * rest <= SLICED_MAX_TILES) {
-            using S = SGeo<C>;
-            const int64_t rows_main = 32 * full, rows_t = rows - rows_main;
-            {
-                std::snprintf(name, sizeof(name), "conv_unit_wide_kernel<%d>", C);
-                ProfScope prof(s, name, (double)rows_main * 16.0 * C * C, (double)rows_main * 14.0 * C);
-                hipLaunchKernelGGL((conv_unit_wide_kernel<C, 2>), dim3(256 * G::WG_PER_CU), dim3(256), G::LDS, s, w, planes, x, y, rows_main, (int64_t)0, frames,
-                                   (int*)nullptr);
-                L3AC_LAUNCH_CHECK();
-            }
-            const int64_t tiles16_t = ceil_div64(rows_t, 16), tiles_pad_t = sliced_tiles_pad(rows_t);
-            const unsigned char* planes_t = planes + full * (int64_t)(G::NS1 * 3072);
-            unsigned char* hid = planes + (wide_planes_bytes(C, rows) + 255) / 256 * 256;  // (conv_unit_wide_scratch_bytes reserves it)
-            const float* x_t = x + rows_main * C;
-            float* y_t = y + rows_main * C;
-            {
-                std::snprintf(name, sizeof(name), "wide_sliced_hidden_kernel<%d>", C);
-                ProfScope p1(s, name, (double)rows_t * 8.0 * C * C, (double)rows_t * 30.0 * C);
-                hipLaunchKernelGGL((wide_sliced_hidden_kernel<C>), dim3((unsigned)(tiles_pad_t / 4 * (G::NT / S::GH))), dim3(256), S::LDS1, s, w, planes_t, hid,
-                                   tiles16_t, tiles_pad_t, x_t, rows_t, frames);
-                L3AC_LAUNCH_CHECK();
-            }
-            std::snprintf(name, sizeof(name), "wide_sliced_out_kernel<%d>", C);
-            ProfScope p2(s, name, (double)rows_t * 8.0 * C * C, (double)rows_t * 32.0 * C);
-            hipLaunchKernelGGL((wide_sliced_out_kernel<C>), dim3((unsigned)(ceil_div64(tiles16_t, 2) * (G::RT / 2))), dim3(256), S::LDS2, s, w, hid, x_t, y_t, rows_t,
-                               tiles16_t, tiles_pad_t);
-            L3AC_LAUNCH_CHECK();
-            return L3AC_OK;
-        }
-    }
-    std::snprintf(name, sizeof(name), "conv_unit_wide_kernel<%d>", C);
-    ProfScope prof(s, name, (double)rows * (16.0 * C * C + (G::FRONT ? 30.0 * C : 0.0)), (double)rows * (G::FRONT ? 8.0 : 14.0) * C);
-    if (half) {
-        blocks = ceil_div64(2 * tiles, 4);
-        hipLaunchKernelGGL((conv_unit_wide_kernel<C, 1>), dim3((unsigned)blocks), dim3(256), G::LDS, s, w, planes, x, y, rows, (int64_t)0, frames, (int*)nullptr);
-    } else {
-        // A large grid runs its tiles in lock-step passes of 4 x 256 and the last pass may be nearly empty (256 x 900 frames at C = 256:
-        // 7 200 tiles = 7 full passes + 32 tiles).  A remainder of at most half a pass is left out of the passes and run as HALF tiles
-        // by the first workgroups, inside the same launch (conv_unit_wide_kernel, tail_tiles).
-        const int64_t per_pass = 4LL * 256 * G::WG_PER_CU;
-        const int64_t full = tiles / per_pass * per_pass, rest = tiles - full;
-        const int64_t tail = (full > 0 && 2 * rest <= per_pass) ? rest : 0;
-        if (blocks > 256 * G::WG_PER_CU) blocks = 256 * G::WG_PER_CU;
-
-        int64_t tail_k = tail;
-        int* ctr = nullptr;
-        if (G::DYN && counters && tiles > 4 * blocks) {
-            // units by counter (conv_unit_wide_kernel, DYN): the last tile's worth per workgroup as groups of half tiles (measured against
-            // 0, 2 and 4 per workgroup: profiles/r06/wide96_sched/dyn_ab.txt)
-            ctr = counters;
-            tail_k = blocks;
-            if (tail_k > tiles) tail_k = tiles;
-        }
-        hipLaunchKernelGGL((conv_unit_wide_kernel<C, 2>), dim3((unsigned)blocks), dim3(256), G::LDS, s, w, planes, x, y, rows, tail_k, frames, ctr);
-    }
-    L3AC_LAUNCH_CHECK();
-    return L3AC_OK;
+    if (!p.hidden) return L3AC_OK;
+    return launch_sliced_pair<C>(s, w, planes + p.rows_main / 32 * (int64_t)(G::NS1 * 3072), planes + wide_hidden_offset(C, rows), x + p.rows_main * C,
+                                 y + p.rows_main * C, rows - p.rows_main, frames);
 }
 
 }  // namespace
@@ -1165,13 +1168,11 @@ int launch_wide(hipStream_t s, const ConvUnitW& w, const float* x, float* y, uns
 
 bool conv_unit_wide_supported(int c) { return c == 96 || c == 128 || c == 192 || c == 256; }
 // scratch the kernels need: the split LayerNorm output of `rows` frames (whole 32-frame tiles), 6 bytes per element, and — for row
-// counts at which the sliced form exists — its hidden image behind it
+// counts at which the sliced form exists — its hidden image behind it.  Above them, the widths without the front end in the main kernel
+// (C >= 128) reserve the largest sliced tail's hidden image (wide_plan, PassesSlicedTail), whatever form the row count takes.
 size_t conv_unit_wide_scratch_bytes(int c, int64_t rows) {
-    const size_t planes = wide_planes_bytes(c, rows);
-    // (large row counts, C >= 128: the remainder of the last pass may run in the sliced form — launch_wide, 'sliced tail' — up to
-    // SLICED_MAX_TILES frame tiles of hidden image behind the planes)
-    if (sliced_exists(c, rows)) return (planes + 255) / 256 * 256 + sliced_hidden_bytes(c, rows);
-    return c >= 128 ? (planes + 255) / 256 * 256 + sliced_hidden_bytes(c, 16 * SLICED_MAX_TILES) : planes;
+    if (sliced_exists(rows)) return wide_hidden_offset(c, rows) + sliced_hidden_bytes(c, rows);
+    return c >= 128 ? wide_hidden_offset(c, rows) + sliced_hidden_bytes(c, 16 * SLICED_MAX_TILES) : wide_planes_bytes(c, rows);
 }
 
 // x must not alias y; `planes` = at least conv_unit_wide_scratch_bytes(c, batch * frames) bytes of scratch (checked).

@@ -565,17 +565,18 @@ int workspace_ensure(l3ac_ctx* ctx, size_t x_floats, size_t a_floats, size_t h_f
     return L3AC_OK;
 }
 
+// h as the scratch of the wide ConvUnit's front end, in floats: bf16x3 planes of whole 32-frame tiles of ALL the call's rows
+// (conv_unit_wide_scratch_bytes) — larger than 4C floats per row when there are few rows
+static size_t wide_scratch_floats(int c, int64_t rows) { return (conv_unit_wide_scratch_bytes(c, rows) + 3) / 4; }
+
 int workspace_ensure_clip(l3ac_ctx* ctx, int batch, int samples, hipStream_t s) {
     const l3ac_config& c = ctx->cfg;
-    const int64_t frames0 = round_up64(samples, ctx->hop);
     size_t x = 0, a = 0, h = 0, yi = 0;
     auto upd = [](size_t& m, int64_t v) { if ((size_t)v > m) m = (size_t)v; };
-    int64_t f = frames0;
-    // (h is also the scratch of the wide ConvUnit's front end: bf16x3 planes of whole 32-frame tiles of ALL the batch's
-    // rows, conv_unit_wide_scratch_bytes — larger than 4C floats per row when batch * frames is small)
-    size_t wide_bytes = 0;
+    int64_t f = round_up64(samples, ctx->hop);
+    size_t wide_floats = 0;
     auto wide = [&](int cdim, int64_t fr) {
-        if (conv_unit_wide_supported(cdim)) wide_bytes = std::max(wide_bytes, conv_unit_wide_scratch_bytes(cdim, (int64_t)batch * fr));
+        if (conv_unit_wide_supported(cdim)) wide_floats = std::max(wide_floats, wide_scratch_floats(cdim, (int64_t)batch * fr));
     };
     for (int i = 0; i < c.n_enc; ++i) {
         upd(x, f * c.enc_dims[i]);
@@ -583,7 +584,6 @@ int workspace_ensure_clip(l3ac_ctx* ctx, int batch, int samples, hipStream_t s) 
         wide(c.enc_dims[i], f);
         if (i + 1 < c.n_enc) f /= c.compress_rates[i];
     }
-    const int64_t feat_frames = f;
     upd(x, f * c.feature_dim);
     const int64_t tr_cols = std::max<int64_t>(std::max<int64_t>(3 * ctx->inner, ctx->ff_n), 4 * c.feature_dim);
     upd(h, f * tr_cols);
@@ -598,35 +598,56 @@ int workspace_ensure_clip(l3ac_ctx* ctx, int batch, int samples, hipStream_t s) 
             f *= c.decode_rates[i];
         }
     }
-    (void)feat_frames;
     upd(a, (int64_t)x);
-    return workspace_ensure(ctx, x * batch, a * batch, std::max(h * batch, (wide_bytes + 3) / 4), yi * batch, (size_t)batch, s);
+    return workspace_ensure(ctx, x * batch, a * batch, std::max(h * batch, wide_floats), yi * batch, (size_t)batch, s);
+}
+
+// The size limits every block entry shares, asked before the workspace is sized for the call: frame numbers inside a clip are ints with a
+// tile and a halo added (dwconv_ln_kernel, the enhance kernels, the LegacyUnit and head kernels, the stem), and 2^34 rows keep every
+// kernel's tile count -- tiles of 14 frames and more, plus one per clip -- below 2^31 - 65536
+static int op_shape_ok(int batch, int frames) {
+    L3AC_REQUIRE(frames <= L3AC_MAX_CLIP_FRAMES, "block entry: %d frames per clip, the limit is 2^31 - 65536 (32-bit frame numbers)", frames);
+    L3AC_REQUIRE((int64_t)batch * frames < L3AC_MAX_ROWS, "block entry: batch * frames = %lld, the limit is 2^34 rows (32-bit tile numbers)",
+                 (long long)batch * frames);
+    return L3AC_OK;
+}
+
+// the workspace of one block of at most c_max channels (the l3ac_op_* entries); h: 4C floats per row, or the wide front end's scratch
+int workspace_ensure_op(l3ac_ctx* ctx, int batch, int frames, int c_max, hipStream_t s) {
+    L3AC_TRY(op_shape_ok(batch, frames));
+    const size_t rows = (size_t)batch * frames;
+    return workspace_ensure(ctx, rows * c_max, rows * c_max, std::max(rows * 4 * c_max, wide_scratch_floats(c_max, (int64_t)rows)), rows * 4,
+                            (size_t)batch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // blocks
 // ---------------------------------------------------------------------------------------------------------
-// the wide fused kernel computes on the bf16 matrix cores only (bf16x3): it belongs to the split route
-static bool use_wide(const l3ac_ctx* ctx, const ConvUnitW& w) {
-    return !ctx->cfg.grn_exact && w.wide_img && ctx->gemm_split && conv_unit_wide_supported(w.c);
+static inline void swap_bufs(float** a, float** b) {
+    float* t = *a;
+    *a = *b;
+    *b = t;
 }
 
+// The form of one ConvUnit call: the wide fused kernel, a narrow fused kernel, or row kernel + GEMMs.  Only the last can run in place
+// and only it evaluates the exact GRN; the wide kernel computes on the bf16 matrix cores only (bf16x3), so it belongs to the split route
+enum class UnitForm { Wide, Fused, Rows };
+static UnitForm conv_unit_form(const l3ac_ctx* ctx, const ConvUnitW& w, bool in_place) {
+    if (in_place || ctx->cfg.grn_exact) return UnitForm::Rows;
+    if (w.wide_img && ctx->gemm_split && conv_unit_wide_supported(w.c)) return UnitForm::Wide;
+    return conv_unit_fused_supported(w.c) ? UnitForm::Fused : UnitForm::Rows;
+}
+
+// option "unit_counter": 1 both kernel families hand their units out by the context's counters, 2 the wide ConvUnit only, 3 the
+// LegacyUnit only, 0 neither (null = equal static shares)
+static int* wide_unit_counters(const l3ac_ctx* ctx) { return ctx->unit_counter == 1 || ctx->unit_counter == 2 ? ctx->wide_counters : nullptr; }
+static int* legacy_unit_counters(const l3ac_ctx* ctx) { return ctx->unit_counter == 1 || ctx->unit_counter == 3 ? ctx->wide_counters + 4 : nullptr; }
+
 int conv_unit_step(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, float** cur, float** alt, int batch, int frames) {
-    if (use_wide(ctx, w)) {
-        L3AC_TRY(launch_conv_unit_wide(s, w, *cur, *alt, reinterpret_cast<unsigned char*>(ctx->ws.h), ctx->ws.h_cap * sizeof(float), batch, frames, ctx->wide_sliced, ctx->unit_counter == 1 || ctx->unit_counter == 2 ? ctx->wide_counters : nullptr));
-        float* t = *cur;
-        *cur = *alt;
-        *alt = t;
-        return L3AC_OK;
-    }
-    if (!ctx->cfg.grn_exact && conv_unit_fused_supported(w.c)) {
-        L3AC_TRY(launch_conv_unit_fused(s, w, *cur, *alt, batch, frames, ctx->gemm_split, ctx->narrow_ring));
-        float* t = *cur;
-        *cur = *alt;
-        *alt = t;
-        return L3AC_OK;
-    }
-    return run_conv_unit(ctx, s, w, *cur, *cur, batch, frames);
+    if (conv_unit_form(ctx, w, false) == UnitForm::Rows) return run_conv_unit(ctx, s, w, *cur, *cur, batch, frames);
+    L3AC_TRY(run_conv_unit(ctx, s, w, *cur, *alt, batch, frames));
+    swap_bufs(cur, alt);
+    return L3AC_OK;
 }
 
 // a product with one of the context's weights (g.w) on the context's route: its split image — null on the exact route, which then takes
@@ -678,8 +699,7 @@ static int conv_unit_group(const l3ac_ctx* ctx, const ConvUnitW& w, int batch, i
 int run_conv_units(l3ac_ctx* ctx, hipStream_t s, const std::vector<ConvUnitW>& units, float** cur, float** alt, int batch,
                    int frames) {
     if (units.empty()) return L3AC_OK;
-    const bool fused = (!ctx->cfg.grn_exact && conv_unit_fused_supported(units[0].c)) || use_wide(ctx, units[0]);
-    if (fused || units.size() == 1 || ctx->rag) {
+    if (conv_unit_form(ctx, units[0], false) != UnitForm::Rows || units.size() == 1 || ctx->rag) {
         for (const ConvUnitW& u : units) {
             L3AC_TRY(rag_mask(ctx, s, *cur, batch, frames, u.c, 3));  // dw_conv k7
             L3AC_TRY(conv_unit_step(ctx, s, u, cur, alt, batch, frames));
@@ -696,9 +716,13 @@ int run_conv_units(l3ac_ctx* ctx, hipStream_t s, const std::vector<ConvUnitW>& u
 }
 
 int run_conv_unit(l3ac_ctx* ctx, hipStream_t s, const ConvUnitW& w, const float* x, float* y, int batch, int frames) {
-    if (x != y && use_wide(ctx, w))
-        return launch_conv_unit_wide(s, w, x, y, reinterpret_cast<unsigned char*>(ctx->ws.h), ctx->ws.h_cap * sizeof(float), batch, frames, ctx->wide_sliced, ctx->unit_counter == 1 || ctx->unit_counter == 2 ? ctx->wide_counters : nullptr);
-    if (!ctx->cfg.grn_exact && x != y && conv_unit_fused_supported(w.c)) return launch_conv_unit_fused(s, w, x, y, batch, frames, ctx->gemm_split, ctx->narrow_ring);
+    switch (conv_unit_form(ctx, w, x == y)) {
+        case UnitForm::Wide:  // (planes and hidden image in the hidden tensor's buffer: workspace_ensure_clip, workspace_ensure_op)
+            return launch_conv_unit_wide(s, w, x, y, reinterpret_cast<unsigned char*>(ctx->ws.h), ctx->ws.h_cap * sizeof(float), batch, frames,
+                                         ctx->wide_sliced, wide_unit_counters(ctx));
+        case UnitForm::Fused: return launch_conv_unit_fused(s, w, x, y, batch, frames, ctx->gemm_split, ctx->narrow_ring);
+        case UnitForm::Rows: break;
+    }
     const int group = conv_unit_group(ctx, w, batch, frames);
     for (int b0 = 0; b0 < batch; b0 += group) {
         const int nb = std::min(group, batch - b0);
@@ -737,7 +761,6 @@ int run_down(l3ac_ctx* ctx, hipStream_t s, const DownW& w, const float* x, float
         r.src = SRC_PLAIN; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
         L3AC_TRY(launch_rows(s, r));
     }
-    (void)ctx;
     return L3AC_OK;
 }
 
@@ -746,15 +769,20 @@ int run_conv_k3(l3ac_ctx* ctx, hipStream_t s, const ConvK3W& w, const float* x, 
     g.a = x; g.lda = w.cin; g.taps = 3; g.dil = 1; g.cin = w.cin; g.frames = frames;
     g.w = w.w; g.ldw = 3 * w.cin; g.c = y; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = 3 * w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
-    (void)ctx;
     return gemm_on_route(ctx, s, g);
+}
+
+// the EnhanceBlock's four branch signals of x into ws.yi and their InstanceNorm statistics into ws.stats, each clip over its own frames
+static int enhance_branches_stats(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, int batch, int frames) {
+    Workspace& ws = ctx->ws;
+    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
+    L3AC_TRY(launch_enhance_branches(s, w.t, x, batch, frames, w.c, ws.yi, ctx->rag ? &rc : nullptr));
+    return launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr);
 }
 
 int run_enhance(l3ac_ctx* ctx, hipStream_t s, const EnhW& w, const float* x, float* y, int batch, int frames) {
     Workspace& ws = ctx->ws;
-    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
-    L3AC_TRY(launch_enhance_branches(s, w.t, x, batch, frames, w.c, ws.yi, ctx->rag ? &rc : nullptr));
-    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr));
+    L3AC_TRY(enhance_branches_stats(ctx, s, w, x, batch, frames));
     RowArgs r{};
     r.x = x; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = frames; r.c = w.c;
     r.src = SRC_GATE; r.norm = NORM_NONE; r.yi = ws.yi; r.stats = ws.stats; r.in_w = w.in_w; r.in_b = w.in_b;
@@ -772,9 +800,20 @@ int up_layer_frames_ok(int frames, int scale) {
 
 // The limits of a ConvUnit call that depend on the form it takes (run_conv_unit's choice): conv_unit_ring_kernel's clip length
 int conv_unit_shape_ok(const l3ac_ctx* ctx, const ConvUnitW& w, bool in_place, int frames) {
-    const bool fused = !in_place && !use_wide(ctx, w) && !ctx->cfg.grn_exact && conv_unit_fused_supported(w.c);
-    if (fused && conv_unit_fused_takes_ring(w, ctx->gemm_split, ctx->narrow_ring)) return conv_unit_ring_clip_ok(frames, w.c);
+    if (conv_unit_form(ctx, w, in_place) == UnitForm::Fused && conv_unit_fused_takes_ring(w, ctx->gemm_split, ctx->narrow_ring))
+        return conv_unit_ring_clip_ok(frames, w.c);
     return L3AC_OK;
+}
+
+// Upsample(linear) of x [batch][frames][c] by `scale` into y, and the ChannelNorm (nw, nb) of the result where nw is given.  A ragged call
+// writes x first: the linear upsampling reads each clip's last frame again from the row after it
+static int upsample_rows(l3ac_ctx* ctx, hipStream_t s, float* x, float* y, int batch, int frames, int c, int scale, const float* nw, const float* nb) {
+    L3AC_TRY(rag_dup(ctx, s, x, batch, frames, c));
+    RowArgs r{};
+    r.x = x; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * scale; r.c = c;
+    r.src = SRC_LERP; r.scale = scale;
+    if (nw) { r.norm = NORM_CN; r.nw = nw; r.nb = nb; r.eps = 1e-8f; }
+    return launch_rows(s, r);
 }
 
 int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tmp, float* y, int batch, int frames) {
@@ -783,12 +822,7 @@ int run_up(l3ac_ctx* ctx, hipStream_t s, const UpW& w, const float* x, float* tm
     g.a = x; g.lda = w.cin; g.w = w.w; g.ldw = w.cin; g.c = tmp; g.ldc = w.cout; g.m = (int64_t)batch * frames; g.n = w.cout; g.k = w.cin;
     g.bias = w.b; g.epi = EPI_BIAS;
     L3AC_TRY(gemm_on_route(ctx, s, g));
-    L3AC_TRY(rag_dup(ctx, s, tmp, batch, frames, w.cout));
-    RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
-    r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
-    r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
-    (void)ctx;
-    return launch_rows(s, r);
+    return upsample_rows(ctx, s, tmp, y, batch, frames, w.cout, w.scale, w.nw, w.nb);  // Upsample(linear) + ChannelNorm (modules.py:162-163)
 }
 
 // the one-kernel form of EnhanceBlock gate + up layer (kernels/up_fused.hip): bf16x3 route, the narrow stages' widths
@@ -816,10 +850,8 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
         return run_up(ctx, s, w, gated, tmp, y, batch, frames);
     }
     Workspace& ws = ctx->ws;
-    const RaggedClips rc = ctx->rag ? ctx->rag->clips(frames) : RaggedClips{};
     L3AC_TRY(up_layer_frames_ok(frames, w.scale));
-    L3AC_TRY(launch_enhance_branches(s, e.t, x, batch, frames, e.c, ws.yi, ctx->rag ? &rc : nullptr));
-    L3AC_TRY(launch_enhance_stats(s, ws.yi, batch, frames, ws.stats, ctx->rag ? &rc : nullptr));
+    L3AC_TRY(enhance_branches_stats(ctx, s, e, x, batch, frames));
     if (use_up_fused(ctx, w) && x != y) {  // gate, conv, upsample and ChannelNorm in one kernel; it reads x while it writes y
         // ragged: the kernel's upsampling clamps at the batch's last frame; with the frame after each clip's last a copy of it (x and yi:
         // the gate and the 1x1 conv are per frame) its lerp gives the clamped form's l0 * x[n - 1] + l1 * x[n - 1]
@@ -834,11 +866,7 @@ int run_enhance_up(l3ac_ctx* ctx, hipStream_t s, const EnhW& e, const UpW& w, fl
     g.gate_yi = ws.yi; g.gate_stats = ws.stats; g.gate_in_w = e.in_w; g.gate_in_b = e.in_b; g.gate_w = e.gate_w; g.gate_b = e.gate_b;
     g.gate_frames = frames;
     L3AC_TRY(launch_gemm(s, g));  // (not gemm_on_route: the gated A operand exists in the fp32 kernel only)
-    L3AC_TRY(rag_dup(ctx, s, tmp, batch, frames, w.cout));
-    RowArgs r{};  // Upsample(linear) + ChannelNorm (modules.py:162-163)
-    r.x = tmp; r.y = y; r.batch = batch; r.frames_in = frames; r.frames_out = (int64_t)frames * w.scale; r.c = w.cout;
-    r.src = SRC_LERP; r.scale = w.scale; r.norm = NORM_CN; r.nw = w.nw; r.nb = w.nb; r.eps = 1e-8f;
-    return launch_rows(s, r);
+    return upsample_rows(ctx, s, tmp, y, batch, frames, w.cout, w.scale, w.nw, w.nb);  // Upsample(linear) + ChannelNorm (modules.py:162-163)
 }
 
 // The output stage's form depends on the head's width and the largest dilation only: fused kernels (bf16x3 or exact fp32 by the
@@ -853,7 +881,7 @@ static bool last_block_fused(const l3ac_ctx* ctx) {
 // place; only the unfused form uses ws.a / ws.h.
 int run_legacy_unit(l3ac_ctx* ctx, hipStream_t s, const LegacyW& l, const float* x, float* y, int batch, int frames) {
     if (last_block_fused(ctx))
-        return launch_legacy_unit_fused(s, l, x, y, batch, frames, ctx->gemm_split, ctx->unit_counter == 1 || ctx->unit_counter == 3 ? ctx->wide_counters + 4 : nullptr);
+        return launch_legacy_unit_fused(s, l, x, y, batch, frames, ctx->gemm_split, legacy_unit_counters(ctx));
     Workspace& ws = ctx->ws;
     const int64_t rows = (int64_t)batch * frames;
     L3AC_TRY(launch_snake(s, x, ws.a, rows, l.c, l.a0, l.ia0));
@@ -884,9 +912,7 @@ int run_last_block(l3ac_ctx* ctx, hipStream_t s, float* x, float* audio, int bat
     for (const LegacyW& l : ctx->legacy) {
         L3AC_TRY(rag_mask(ctx, s, cur, batch, frames, l.c, 3 * l.dil));  // k7 at dilation dil
         L3AC_TRY(run_legacy_unit(ctx, s, l, cur, alt, batch, frames));
-        float* t = cur;
-        cur = alt;
-        alt = t;
+        swap_bufs(&cur, &alt);
     }
     L3AC_TRY(rag_mask(ctx, s, cur, batch, frames, ctx->head.c, 3));  // head k7
     L3AC_TRY(run_head(ctx, s, cur, audio, batch, frames));
@@ -901,9 +927,14 @@ static bool use_trans_stack(const l3ac_ctx* ctx, const LocalTransW& w, int frame
 
 static int run_local_trans_layers(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames);
 
+// the whole stack in one launch, one workgroup per clip (six in the cooperative form), at the attention's scale dim_head^-0.5
+static int trans_stack(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames) {
+    return launch_trans_stack(s, w, x, batch, frames, (float)std::pow((double)ctx->dim_head, -0.5), &ctx->coop);
+}
+
 int run_local_trans(l3ac_ctx* ctx, hipStream_t s, const LocalTransW& w, float* x, int batch, int frames) {
-    if (use_trans_stack(ctx, w, frames))  // one launch for the whole stack, one workgroup per clip
-        return launch_trans_stack(s, w, x, batch, frames, (float)std::pow((double)ctx->dim_head, -0.5), &ctx->coop);
+    if (use_trans_stack(ctx, w, frames))
+        return trans_stack(ctx, s, w, x, batch, frames);
     return run_local_trans_layers(ctx, s, w, x, batch, frames);
 }
 
@@ -927,7 +958,7 @@ static int run_local_trans_ragged(l3ac_ctx* ctx, hipStream_t s, const LocalTrans
     float* l = spare + (int64_t)nq * fq * dim;
     if (nq) L3AC_TRY(launch_ragged_gather(s, x, q, r.order_dev, 0, nq, fq, dim, clip, (int64_t)fq * dim, false));
     if (nq < batch) L3AC_TRY(launch_ragged_gather(s, x, l, r.order_dev, nq, batch - nq, fl, dim, clip, (int64_t)fl * dim, false));
-    if (nq) L3AC_TRY(launch_trans_stack(s, w, q, nq, fq, (float)std::pow((double)ctx->dim_head, -0.5), &ctx->coop));
+    if (nq) L3AC_TRY(trans_stack(ctx, s, w, q, nq, fq));
     if (nq < batch) L3AC_TRY(run_local_trans_layers(ctx, s, w, l, batch - nq, fl));
     if (nq) L3AC_TRY(launch_ragged_gather(s, q, x, r.order_dev, 0, nq, fq, dim, clip, (int64_t)fq * dim, true));
     if (nq < batch) L3AC_TRY(launch_ragged_gather(s, l, x, r.order_dev, nq, batch - nq, fl, dim, clip, (int64_t)fl * dim, true));
@@ -975,12 +1006,6 @@ static int run_local_trans_layers(l3ac_ctx* ctx, hipStream_t s, const LocalTrans
 // ---------------------------------------------------------------------------------------------------------
 // sub-modules
 // ---------------------------------------------------------------------------------------------------------
-static inline void swap_bufs(float** a, float** b) {
-    float* t = *a;
-    *a = *b;
-    *b = t;
-}
-
 int run_encoder(l3ac_ctx* ctx, hipStream_t s, const float* audio, int64_t audio_stride, int batch, int samples,
                 int frames, float** cur, float** alt) {
     const l3ac_config& c = ctx->cfg;
@@ -1003,14 +1028,12 @@ int run_encoder(l3ac_ctx* ctx, hipStream_t s, const float* audio, int64_t audio_
 
 int run_en_encoder(l3ac_ctx* ctx, hipStream_t s, int batch, int frames, float** cur, float** alt, int* n_tok) {
     // input (B, C, T) permuted to (B, T, C) by the reference (local_trans.py:162): already frame-major here
+    L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[0], cur, alt, batch, frames));
     if (ctx->en_enc.size() == 2) {
-        L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[0], cur, alt, batch, frames));
         L3AC_TRY(run_down(ctx, s, ctx->en_down, *cur, *alt, batch, frames));
         swap_bufs(cur, alt);
         frames /= ctx->en_down.stride;
         L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[1], cur, alt, batch, frames));
-    } else {
-        L3AC_TRY(local_trans_step(ctx, s, ctx->en_enc[0], cur, alt, batch, frames));
     }
     *n_tok = frames;
     return L3AC_OK;
@@ -1021,11 +1044,7 @@ int run_en_decoder(l3ac_ctx* ctx, hipStream_t s, int batch, int n_tok, float** c
     int f = n_tok;
     if (ctx->en_dec.size() == 2) {
         const int r = ctx->cfg.en_coder_compress_rate;
-        L3AC_TRY(rag_dup(ctx, s, *cur, batch, f, ctx->cfg.feature_dim));  // linear upsampling
-        RowArgs u{};  // UpTransV2.up_layer (local_trans.py:121-124)
-        u.x = *cur; u.y = *alt; u.batch = batch; u.frames_in = f; u.frames_out = (int64_t)f * r; u.c = ctx->cfg.feature_dim;
-        u.src = SRC_LERP; u.scale = r; u.norm = NORM_NONE;
-        L3AC_TRY(launch_rows(s, u));
+        L3AC_TRY(upsample_rows(ctx, s, *cur, *alt, batch, f, ctx->cfg.feature_dim, r, nullptr, nullptr));  // UpTransV2.up_layer (local_trans.py:121-124)
         swap_bufs(cur, alt);
         f *= r;
         L3AC_TRY(local_trans_step(ctx, s, ctx->en_dec[1], cur, alt, batch, f));

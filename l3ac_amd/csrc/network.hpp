@@ -179,6 +179,8 @@ void network_free(l3ac_ctx* ctx);
 int workspace_ensure(l3ac_ctx* ctx, size_t x_floats, size_t a_floats, size_t h_floats, size_t yi_floats, size_t batch,
                      hipStream_t s);
 int workspace_ensure_clip(l3ac_ctx* ctx, int batch, int samples, hipStream_t s);
+// one block of at most c_max channels (the l3ac_op_* entries); first of all the size limits every block entry shares
+int workspace_ensure_op(l3ac_ctx* ctx, int batch, int frames, int c_max, hipStream_t s);
 
 // fused ConvUnit for the narrow stages (kernels/conv_unit_fused.hip); x must not alias y
 bool conv_unit_fused_supported(int c);
